@@ -13,7 +13,10 @@ exchanges when N > 1), with CSR and factors already resident in HBM.  ``value`` 
 For N > 1 the driver launches one process per GPU (torch.distributed.run); users and
 items are row-sharded (lkpy_amd._als_engine) and total work is fixed => "strong".
 
-One JSON line on rank 0.  Extra objects (rank 0, N = 1):
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 (metric,
+value, unit, ms_per_step, dtype, ...).  ``--dump-outputs DIR`` then also writes what the last
+timed step computed (``dump_outputs``).  ``--full`` adds every other measurement below and prints
+two lines: the full objects, then a compact digest LAST.  Extra objects (rank 0, N = 1, --full):
   roofline     -- the dominant kernel (f32 MFMA bound): algorithmic flops per launch
                    / average launch duration from HIP events recorded on the
                   launch stream inside the library; ``frac_executed`` counts the MFMA work
@@ -27,6 +30,7 @@ One JSON line on rank 0.  Extra objects (rank 0, N = 1):
                   end (matrix preparation, upload, relabel + transpose in HBM, plans, epochs,
                   download), with the per-epoch times of the reference's own log line.
   topk / knn   -- the other two legs of the metric, each with roofline + cpu_baseline.
+  (also: summation_order, recommend, cg, k128, cfg5; with N > 1 collectives and sharded legs)
 """
 
 from __future__ import annotations
@@ -886,7 +890,7 @@ def knn_recommend_cpu_and_parity(sims, r_ptr, r_idx, r_val, means, hits, got_i, 
     }
 
 
-def cfg5_run(args, dev, world, rank, steps, warmup, topk_users=0):
+def cfg5_run(args, dev, world, rank, steps, warmup, topk_users=0, full=True, dump_dir=None):
     """
     BASELINE.json configs[4] / SURVEY.md 8d "cfg5 concrete input": U = 10^7, I = 10^6,
     nnz = 10^8 generated in HBM from seed 5 (Philox; csrc/synth.hip), values 40, als-implicit
@@ -894,7 +898,9 @@ def cfg5_run(args, dev, world, rank, steps, warmup, topk_users=0):
     slice x ALL items with the history excluded.  ``args.scale`` shrinks users, items and nnz
     together.  With world > 1 the users / items are row-sharded as for cfg2; on one GPU the
     whole problem runs on that GPU.  Returns the result object (a bench line of its own under
-    ``--config cfg5``, the ``cfg5`` leg of the default line otherwise).
+    ``--config cfg5``, the ``cfg5`` leg of the default line otherwise).  Without ``full`` only
+    the timed epochs (and ``dump_dir``'s outputs): no roofline, collectives, summation order,
+    parity, CPU baseline or top-K.
     """
     import torch
     import torch.distributed as dist
@@ -938,28 +944,11 @@ def cfg5_run(args, dev, world, rank, steps, warmup, topk_users=0):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    try:
-        coll = collective_times(eng, min(steps, 3), dev, world)
-    except Exception as exc:  # noqa: BLE001
-        coll = {"error": f"{type(exc).__name__}: {exc}"}
-    # kernel times: one more epoch with HIP events on the launch stream
-    eng.u_plan.enable_timing(True)
-    eng.i_plan.enable_timing(True)
-    eng.train_epoch()
-    barrier()
-    cu, su, nu = eng.u_plan.get_timing()
-    ci, si, ni = eng.i_plan.get_timing()
-    eng.u_plan.enable_timing(False)
-    eng.i_plan.enable_timing(False)
+    deltas = [float(du.item()), float(di.item())]
+    if dump_dir is not None:
+        dump_outputs(eng, deltas, dump_dir)
     ulen = np.diff(eng.u_plan.csr.h_indptr)
     ilen = np.diff(eng.i_plan.csr.h_indptr)
-    uwb, iwb = bool(eng.u_plan.use_wb), bool(eng.i_plan.use_wb)
-    fu, fuc = half_flops(ulen, k, uwb)
-    fi, fic = half_flops(ilen, k, iwb)
-    # per epoch: both solve launches + both chunk launches
-    ep_ms = (su + si + cu + ci) / max(nu, 1)
-    ep_flops = fu + fi + fuc + fic
-    ex_flops = half_mfma_flops(ulen, backend.kp, uwb) + half_mfma_flops(ilen, backend.kp, iwb)
     out = {
         "metric": "ALS-implicit epochs/sec (cfg5 synthetic %.3gM x %.3gM x %.3gM, k=%d)"
         % (n_users / 1e6, n_items / 1e6, nnz / 1e6, k),
@@ -984,34 +973,58 @@ def cfg5_run(args, dev, world, rank, steps, warmup, topk_users=0):
             "parallelism": ("row-sharded x%d, %d row slices per half-epoch (gathers under the solve)"
                             % (world, getattr(eng, "slices", 1))) if world > 1 else "single GPU",
         },
-        "final_deltas": [float(du.item()), float(di.item())],
+        "final_deltas": deltas,
         "generate_seconds": round(gen_seconds, 3),
         "setup_seconds": round(setup_seconds, 3),
-        "roofline": {
-            "kernel": "als_blk_solve_kernel%d + als_blk_chunk_kernel" % (backend.kp // 16)
-            + (" + als_wb / als_wb64 / als_wb128 kernels (rows <= 128 entries)" if (uwb or iwb) else ""),
-            "bound": "mfma",
-            "achieved": round(ep_flops / (ep_ms * 1e-3) / 1e12, 3),
-            "peak": F32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-            "frac": round(ep_flops / (ep_ms * 1e-3) / 1e12 / F32_MFMA_PEAK_TFLOPS, 4),
-            "frac_executed": round(ex_flops / ((su + si) / max(nu, 1) * 1e-3) / 1e12
-                                   / F32_MFMA_PEAK_TFLOPS, 4),
-            "kernel_ms_per_epoch": {"user_solve": round(su / max(nu, 1), 3),
-                                    "item_solve": round(si / max(ni, 1), 3),
-                                    "user_chunk": round(cu / max(nu, 1), 3),
-                                    "item_chunk": round(ci / max(ni, 1), 3)},
-            "algorithmic_flops_per_epoch": ep_flops,
-            "reference_flops_per_epoch": reference_half_flops(ulen, k)
-            + reference_half_flops(ilen, k),
-            "woodbury_rows": {"user": int(eng.u_plan.woodbury_rows) if uwb else 0,
-                              "item": int(eng.i_plan.woodbury_rows) if iwb else 0},
-            "algorithmic_bytes_per_epoch": half_bytes(ulen, k) + half_bytes(ilen, k),
-            "traffic": None, "traffic_source": None,
-            "note": "rows with <= 128 entries are rank-n updates of OtOr and are solved through "
-            "the Woodbury identity (same solution, O(n^2 k) flops): algorithmic_flops counts "
-            "what this path needs for them; reference_flops = a dense k^3/3 solve for every "
-            "row, as the reference does (SURVEY 8d)",
-        },
+    }
+    if not full:
+        del eng
+        torch.cuda.empty_cache()
+        return out
+    try:
+        coll = collective_times(eng, min(steps, 3), dev, world)
+    except Exception as exc:  # noqa: BLE001
+        coll = {"error": f"{type(exc).__name__}: {exc}"}
+    # kernel times: one more epoch with HIP events on the launch stream
+    eng.u_plan.enable_timing(True)
+    eng.i_plan.enable_timing(True)
+    eng.train_epoch()
+    barrier()
+    cu, su, nu = eng.u_plan.get_timing()
+    ci, si, ni = eng.i_plan.get_timing()
+    eng.u_plan.enable_timing(False)
+    eng.i_plan.enable_timing(False)
+    uwb, iwb = bool(eng.u_plan.use_wb), bool(eng.i_plan.use_wb)
+    fu, fuc = half_flops(ulen, k, uwb)
+    fi, fic = half_flops(ilen, k, iwb)
+    # per epoch: both solve launches + both chunk launches
+    ep_ms = (su + si + cu + ci) / max(nu, 1)
+    ep_flops = fu + fi + fuc + fic
+    ex_flops = half_mfma_flops(ulen, backend.kp, uwb) + half_mfma_flops(ilen, backend.kp, iwb)
+    out["roofline"] = {
+        "kernel": "als_blk_solve_kernel%d + als_blk_chunk_kernel" % (backend.kp // 16)
+        + (" + als_wb / als_wb64 / als_wb128 kernels (rows <= 128 entries)" if (uwb or iwb) else ""),
+        "bound": "mfma",
+        "achieved": round(ep_flops / (ep_ms * 1e-3) / 1e12, 3),
+        "peak": F32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+        "frac": round(ep_flops / (ep_ms * 1e-3) / 1e12 / F32_MFMA_PEAK_TFLOPS, 4),
+        "frac_executed": round(ex_flops / ((su + si) / max(nu, 1) * 1e-3) / 1e12
+                               / F32_MFMA_PEAK_TFLOPS, 4),
+        "kernel_ms_per_epoch": {"user_solve": round(su / max(nu, 1), 3),
+                                "item_solve": round(si / max(ni, 1), 3),
+                                "user_chunk": round(cu / max(nu, 1), 3),
+                                "item_chunk": round(ci / max(ni, 1), 3)},
+        "algorithmic_flops_per_epoch": ep_flops,
+        "reference_flops_per_epoch": reference_half_flops(ulen, k)
+        + reference_half_flops(ilen, k),
+        "woodbury_rows": {"user": int(eng.u_plan.woodbury_rows) if uwb else 0,
+                          "item": int(eng.i_plan.woodbury_rows) if iwb else 0},
+        "algorithmic_bytes_per_epoch": half_bytes(ulen, k) + half_bytes(ilen, k),
+        "traffic": None, "traffic_source": None,
+        "note": "rows with <= 128 entries are rank-n updates of OtOr and are solved through "
+        "the Woodbury identity (same solution, O(n^2 k) flops): algorithmic_flops counts "
+        "what this path needs for them; reference_flops = a dense k^3/3 solve for every "
+        "row, as the reference does (SURVEY 8d)",
     }
 
     if world == 1 and args.scale == 1.0:
@@ -1208,11 +1221,14 @@ def main_cfg5(args):
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     _native.require_gpu()
     dev, dry = init_ranks(world, local_rank)
-    out = cfg5_run(args, dev, world, rank, args.steps, args.warmup, args.topk_users)
+    out = cfg5_run(args, dev, world, rank, args.steps, args.warmup, args.topk_users,
+                   full=args.full, dump_dir=args.dump_outputs if rank == 0 else None)
     if dry and world > 1:
         out["dryrun"] = True
-    if rank == 0:
+    if rank == 0 and args.full:
         emit(out)
+    elif rank == 0:
+        print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -1331,13 +1347,41 @@ def collective_times(eng, steps, dev, world):
                     "separate pass after the timed region)"}
 
 
-def als_timed(ui, P0, Q0, k, reg, steps, warmup, dev, world, scale):
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(eng, deltas, out_dir):
+    """
+    ``--dump-outputs DIR``: what a caller of the timed path receives from its last step, as
+    ``DIR/<name>.npy`` -- ``user_embeddings`` and ``item_embeddings`` (float32, the original
+    labelling, as ``ImplicitALSEngine.user_embeddings()`` / ``item_embeddings()`` return them)
+    and ``epoch_deltas`` (float64 |dP|, |dQ| of ``train_epoch``).  When the two matrices together
+    exceed 64 MB, each is written as the same share of its rows: row numbers drawn by
+    ``np.random.default_rng(0)`` from the shape alone (sorted), so every build writes the same rows.
+    """
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    n_u, n_i = len(eng.u_new), len(eng.i_new)
+    room = (DUMP_BYTES - 4096) // (4 * eng.k)  # rows that fit beside the deltas
+    share = min(1.0, room / (n_u + n_i))
+    rng = np.random.default_rng(0)
+    for name, mat, new, n in (("user_embeddings", eng.P, eng.u_new, n_u),
+                              ("item_embeddings", eng.Q, eng.i_new, n_i)):
+        rows = np.arange(n) if share == 1.0 else np.sort(
+            rng.choice(n, int(n * share), replace=False))
+        host = eng.backend.download_rows(mat, new[rows])
+        np.save(out_dir / f"{name}.npy", np.ascontiguousarray(host, dtype=np.float32))
+    np.save(out_dir / "epoch_deltas.npy", np.asarray(deltas, dtype=np.float64))
+
+
+def als_timed(ui, P0, Q0, k, reg, steps, warmup, dev, world, scale, extras=True, dump_dir=None):
     """
     Set up the engine (one upload, relabel + transpose in HBM), run ``warmup`` untimed and
-    ``steps`` timed epochs bracketed by barrier + synchronize (maximum over ranks), and build the
+    ``steps`` timed epochs bracketed by barrier + synchronize (maximum over ranks), write the
+    last step's outputs to ``dump_dir`` (if given), and -- with ``extras`` (--full) -- build the
     roofline object of the solve kernel from the HIP-event launch durations recorded on the
-    launch stream inside the library.  Returns (engine, backend, seconds, roofline, set-up
-    seconds, final deltas).
+    launch stream inside the library, the collective times and the summation-order comparison.
+    Returns (engine, backend, seconds, roofline, set-up seconds, final deltas).
     """
     import torch
     import torch.distributed as dist
@@ -1371,6 +1415,11 @@ def als_timed(ui, P0, Q0, k, reg, steps, warmup, dev, world, scale):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    deltas = (float(du.item()), float(di.item()))
+    if dump_dir is not None:
+        dump_outputs(eng, deltas, dump_dir)
+    if not extras:
+        return eng, backend, elapsed, None, setup_seconds, deltas
     try:
         eng.collectives = collective_times(eng, min(steps, 10), dev, world)
     except Exception as exc:  # noqa: BLE001 -- reported in place, never costs the headline
@@ -1460,7 +1509,7 @@ def als_timed(ui, P0, Q0, k, reg, steps, warmup, dev, world, scale):
             eng, lambda mode: ImplicitALSEngine(ui, k, reg, reg, P0, Q0,
                                                 HipBackend(k, dev, _native.SOLVER_AUTO, mode)),
             min(steps, 20), elapsed / steps * 1e3, dev)
-    return eng, backend, elapsed, roof, setup_seconds, (float(du.item()), float(di.item()))
+    return eng, backend, elapsed, roof, setup_seconds, deltas
 
 
 def _pick(d, *keys):
@@ -1715,6 +1764,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=None, help="default 3 (cfg5: 1)")
     ap.add_argument("--k", type=int, default=64)
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the dataset (debug only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline (roofline, summation "
+                    "order, parity + cpu_baseline, top-K, CG, fit, recommend, kNN, k128, cfg5; "
+                    "N > 1: collectives and the sharded legs); the --no-* options below drop "
+                    "legs of a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (at most "
+                    "64 MB in all; see dump_outputs)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the parity + cpu_baseline legs")
     ap.add_argument("--no-knn", action="store_true", help="skip the item-kNN build leg")
     ap.add_argument("--no-topk", action="store_true", help="skip the dense top-N scoring leg")
@@ -1749,6 +1806,8 @@ def main():
         args.steps = 3 if args.config == "cfg5" else 50
     if args.warmup is None:
         args.warmup = 1 if args.config == "cfg5" else 3
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.config == "cfg5":
         return main_cfg5(args)
 
@@ -1783,7 +1842,8 @@ def main():
     P0 *= P0
 
     eng, backend, elapsed, roof, setup_seconds, deltas = als_timed(
-        ui, P0, Q0, k, reg, args.steps, args.warmup, dev, world, args.scale)
+        ui, P0, Q0, k, reg, args.steps, args.warmup, dev, world, args.scale, extras=args.full,
+        dump_dir=args.dump_outputs if rank == 0 else None)
     ms_per_step = elapsed / args.steps * 1e3
 
     def barrier():
@@ -1828,6 +1888,13 @@ def main():
         out["summation_order"] = eng.summation_order
     if getattr(eng, "collectives", None):
         out["collectives"] = eng.collectives
+    if not args.full:  # the headline alone: one line
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # The secondary legs must never cost the headline line: a failure is reported in place.
     def leg(name, fn):

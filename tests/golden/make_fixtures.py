@@ -14,6 +14,9 @@ Outputs (all under tests/golden/):
   ``rating`` (ratings.csv order) and ``all_item_ids`` (every movies.csv id; the
   modern MovieLens loader registers *all* of them as items,
   ``src/lenskit/data/sources/movielens.py:327-345``, so empty item rows exist).
+* ``ml-latest-small.zip`` -- the same distribution as MovieLens ships it (``ratings.csv``,
+  ``movies.csv`` and the ``README.txt`` with its licence, under an ``ml-latest-small/`` top
+  directory), the input of the loader test (tests/test_host_logic.py).
 * ``pipelines/als-implicit.toml``, ``iknn-explicit.toml``, ``als-explicit.toml`` -- verbatim copies of the
   reference's pipeline definitions (``pipelines/*.toml``), test INPUTS: the backend must load
   and run them unchanged (tests/test_gpu_pipeline.py, tests/test_host_logic.py).
@@ -27,6 +30,7 @@ Outputs (all under tests/golden/):
 from __future__ import annotations
 
 import shutil
+import zipfile
 from pathlib import Path
 
 import numpy as np
@@ -34,6 +38,17 @@ import pandas as pd
 
 REF = Path("/root/reference")
 OUT = Path(__file__).resolve().parent
+
+
+def write_ml_zip():
+    "the raw ml-latest-small files, stored with a fixed timestamp so that a rerun is byte-identical"
+    src = REF / "data/ml-latest-small"
+    with zipfile.ZipFile(OUT / "ml-latest-small.zip", "w") as z:
+        z.writestr(zipfile.ZipInfo("ml-latest-small/", (2018, 9, 26, 0, 0, 0)), "")
+        for name in ("README.txt", "movies.csv", "ratings.csv"):
+            info = zipfile.ZipInfo("ml-latest-small/" + name, (2018, 9, 26, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            z.writestr(info, (src / name).read_bytes(), compresslevel=9)
 
 
 def main():
@@ -46,6 +61,7 @@ def main():
         rating=ratings["rating"].to_numpy(np.float32),
         all_item_ids=movies["movieId"].to_numpy(np.int32),
     )
+    write_ml_zip()
     shutil.copyfile(REF / "tests/models/item-item-preds.csv", OUT / "item-item-preds.csv")
     # the reference's golden user-kNN predictions (tests/models/user-user-preds.csv, consumed by
     # tests/models/test_knn_user_user.py:204-237): UserKNNScorer(k=30, min_sim=1e-6)

@@ -394,20 +394,24 @@ def test_load_movielens_zip_and_directory(tmp_path):
         load_movielens(tmp_path / "absent")
 
 
-def test_load_movielens_equals_the_committed_fixture():
-    "the loader on the reference checkout's ml-latest-small == tests/golden/ml_small.npz"
+def test_load_movielens_equals_the_committed_fixture(tmp_path):
+    """the loader on the ml-latest-small distribution (tests/golden/ml-latest-small.zip, unpacked
+    and as the zip itself) == tests/golden/ml_small.npz"""
+    import zipfile
     from pathlib import Path
 
     from lkpy_amd.data import load_movielens, load_movielens_npz
 
-    src = Path("/root/reference/data/ml-latest-small")
-    if not src.exists():
-        pytest.skip("reference checkout not present (GPU box)")
-    ds = load_movielens(src)
-    g = load_movielens_npz(Path(__file__).parent / "golden" / "ml_small.npz")
-    assert ds.users == g.users and ds.items == g.items
-    assert np.array_equal(ds._cols, g._cols) and np.array_equal(ds._indptr, g._indptr)
-    assert np.array_equal(ds._attrs["rating"], g._attrs["rating"])
+    golden = Path(__file__).parent / "golden"
+    archive = golden / "ml-latest-small.zip"
+    with zipfile.ZipFile(archive) as z:
+        z.extractall(tmp_path)
+    g = load_movielens_npz(golden / "ml_small.npz")
+    for src in (tmp_path / "ml-latest-small", archive):
+        ds = load_movielens(src)
+        assert ds.users == g.users and ds.items == g.items
+        assert np.array_equal(ds._cols, g._cols) and np.array_equal(ds._indptr, g._indptr)
+        assert np.array_equal(ds._attrs["rating"], g._attrs["rating"])
 
 
 def test_item_list_collection_mirrors_the_reference_api():

@@ -1,10 +1,11 @@
-# One gpurun call's worth of work (rewritten per call during development).
-# Usage: gpurun --timeout 2400 -- 'bash tools/gpu_round.sh'
-mkdir -p gpurun_out
-timeout 1500 python -m pytest tests -m gpu -q -s > gpurun_out/gputest.log 2>&1; echo "pytest rc=$?" >> gpurun_out/gputest.log
-grep -E "passed|failed|error" gpurun_out/gputest.log | tail -n 5
-grep -E "^FAILED|^k = |at-scale" gpurun_out/gputest.log | head -20
-timeout 900 python bench.py > gpurun_out/bench.log 2> gpurun_out/bench.err; echo "bench rc=$?" >> gpurun_out/bench.err
-tail -n 2 gpurun_out/bench.err
-tail -n 1 gpurun_out/bench.log | head -c 6500
-python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > gpurun_out/smoke.log 2>&1; tail -n 3 gpurun_out/smoke.log
+# The record of a build on the GPU box: pytest -m gpu, bench.py --full, smoke().
+# Usage: bash tools/gpu_round.sh [LOG_DIR]   (logs go to LOG_DIR, default: logs)
+OUT=${1:-logs}
+mkdir -p "$OUT"
+timeout 1500 python -m pytest tests -m gpu -q -s > "$OUT"/gputest.log 2>&1; echo "pytest rc=$?" >> "$OUT"/gputest.log
+grep -E "passed|failed|error" "$OUT"/gputest.log | tail -n 5
+grep -E "^FAILED|^k = |at-scale" "$OUT"/gputest.log | head -20
+timeout 900 python bench.py --full > "$OUT"/bench.log 2> "$OUT"/bench.err; echo "bench rc=$?" >> "$OUT"/bench.err
+tail -n 2 "$OUT"/bench.err
+tail -n 1 "$OUT"/bench.log | head -c 6500
+python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > "$OUT"/smoke.log 2>&1; tail -n 3 "$OUT"/smoke.log

@@ -4,7 +4,7 @@ R=${1:-tmp}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/prof_${R}_cfg5
 mkdir -p $OUT
-CMD="python bench.py --config cfg5 --steps 2 --warmup 1 --no-cpu --no-topk"
+CMD="python bench.py --full --config cfg5 --steps 2 --warmup 1 --no-cpu --no-topk"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o cfg5 -- $CMD > $OUT/stats.log 2>&1
 python tools/summarize_prof.py $OUT gpurun_out/${R}_cfg5
 python - <<PY

@@ -4,7 +4,7 @@
 #   tools/prof_round.sh r04
 set -u
 R=${1:-r06}
-BASE="--no-cpu --no-knn --no-topk --no-fit --no-k128 --no-cfg5 --no-cg --no-order-ab"
+BASE="--full --no-cpu --no-knn --no-topk --no-fit --no-k128 --no-cfg5 --no-cg --no-order-ab"
 # cfg2 headline (k = 64): all passes
 PROF_PASSES=all bash tools/prof_als.sh ${R}_als_k64 > /dev/null 2>&1
 python tools/summarize_prof.py gpurun_out/prof_${R}_als_k64 gpurun_out/${R}_als_k64
@@ -15,7 +15,7 @@ python tools/summarize_prof.py gpurun_out/prof_${R}_k128 gpurun_out/${R}_k128
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/prof_${R}_cfg5
 mkdir -p $OUT
-CMD="python bench.py --config cfg5 --steps 2 --warmup 1 --no-cpu --no-topk --no-order-ab"
+CMD="python bench.py --full --config cfg5 --steps 2 --warmup 1 --no-cpu --no-topk --no-order-ab"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o cfg5 -- $CMD > $OUT/stats.log 2>&1
 # (round 5: the SQ groups for cfg5 as well -- VERDICT r4 #4)
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU \
