@@ -124,7 +124,7 @@ struct Cfg {
     static constexpr int OFF_ZB = OFF_X + KP;       // z of the current block, double buffered
     static constexpr int OFF_SP = OFF_ZB + 32;      // back substitution: partial sums of 2 waves
     static constexpr int OFF_RED = OFF_SP + 32;     // delta reduction
-    // LK_BLK_TWIN: the leader wave's multipliers, column by column, for the other panel waves
+    // (the next three fields served a retired variant; kept so that the kernels' LDS stays put)
     static constexpr int OFF_COL = OFF_RED + 8;     // [16 columns][16]: L_bb[c][j] at j * 16 + c
     static constexpr int OFF_CRINV = OFF_COL + 256; // 1 / L_jj of the current block
     static constexpr int OFF_FLAG = OFF_CRINV + 16; // int: 16 b + (columns of block b published)
@@ -180,19 +180,16 @@ __device__ __forceinline__ void ops_issue(Ops<NT> &o, int g, int col_reg, float 
 // tiles of the matrix ("phantom": computed like the others, never read): 4 of its 10 Gram MFMAs
 // per entry group at k = 128, 8 of 36 at k = 256, while the other three waves have no slack --
 // every SIMD issues T MFMAs per group for 36 (136) useful tiles out of 40 (144).  With
-// LK_BLK_DONATE the three other waves each leave NL / 4 of their tiles -- local (d, NL - 1),
+// donation the three other waves each leave NL / 4 of their tiles -- local (d, NL - 1),
 // d < NL / 4 -- to the phantom wave, which accumulates them in its phantom slots (it holds every
 // feature block as one of its two operands: odd blocks as qa, even blocks as qb): T - NL / 4
 // MFMAs per group for every wave (9 instead of 10, 34 instead of 36).  The solve kernel hands the
 // tiles over through LDS after the Gram phase; the chunk kernels store them straight into the
 // owner's part of the slab.  Same products, same accumulation chains: bit-identical results.
-#ifndef LK_BLK_DONATE
-#define LK_BLK_DONATE 1
-#endif
 template <int NT>
 struct Don {
     static constexpr int NL = NT / 2;
-    static constexpr int PER = LK_BLK_DONATE ? NL / 4 : 0;  // tiles each of the 3 donors leaves
+    static constexpr int PER = NL / 4;  // tiles each of the 3 donors leaves
     static constexpr int ND = 3 * PER;                      // phantom slots in use: lt(p, p), p < ND
     // donor of phantom slot p: 0 = wave (0,0), 1 = wave (0,1), 2 = wave (1,1)
     __host__ __device__ static constexpr int donor(int p) { return p / (PER ? PER : 1); }
@@ -260,9 +257,6 @@ __device__ __forceinline__ void ops_consume(f32x4 (&acc)[Cfg<NT>::T], float (&ya
 // Measured per ML-25M-shaped epoch (tools/blk_variants.py): k = 256: D = 0 81.8 ms, 1: 80.8,
 // 2: 75.5, 4: 80.9 (spills); k = 128: D = 0 19.15, 2: 18.80, 4: 19.29, 8 at 3 waves/SIMD: 20.4
 // -- at k = 128 the four resident workgroups already cover most of each other's gather latency.
-#ifndef LK_BLK_SOLVE_PRIO
-#define LK_BLK_SOLVE_PRIO 0
-#endif
 #ifndef LK_BLK_RING8
 #define LK_BLK_RING8 2   // k = 128: 9 registers per step (4 spills 150 B more and gains nothing)
 #endif
@@ -638,21 +632,12 @@ __device__ __forceinline__ void chol_step(f32x4 (&acc)[Cfg<NT>::T], float *__res
     const bool phantom = wr > wc;
     const int vwave = (wave + rot) & 3;  // role in the panel phase
     const int vtid = vwave * 64 + lane;
-#ifndef LK_BLK_TWIN
-#define LK_BLK_TWIN 0  // 1: the diagonal block is factored by the leader wave only (see phase 2)
-#endif
-#ifndef LK_BLK_SKIP
-#define LK_BLK_SKIP 1  // 0: every wave runs the chain (rounds 1-3; A/B timing, tools/blk_variants.py)
-#endif
-    const bool has_rows = !LK_BLK_SKIP || vwave * 64 < R;  // wave-uniform
+    const bool has_rows = vwave * 64 < R;  // wave-uniform
 
     // (1) the owners of block row b publish A'(b-block rows, columns >= b) = -acc, transposed
     // by symmetry into panel rows: tile (b, tj), lane (j = sub, slot) holds
     // D[i = 4 slot + r][j] = A'[16 tj + j][16 b + 4 slot + r] -> panel row 16 (tj - b) + j,
     // columns 4 slot .. 4 slot + 3 = k-group `slot`
-    if constexpr (LK_BLK_TWIN && b == 0) {  // the twins' column counter starts at 0 for every row
-        if (tid == 0) *reinterpret_cast<volatile int *>(&lds[C::OFF_FLAG]) = 0;
-    }
     if (wr == (b & 1)) {
         sfor<Ib, NL>([&](auto Jc) {
             constexpr int J = decltype(Jc)::value;
@@ -677,14 +662,6 @@ __device__ __forceinline__ void chol_step(f32x4 (&acc)[Cfg<NT>::T], float *__res
 #ifdef LK_BLK_PHASES
     unsigned long long bp2 = bp1;
 #endif
-    // LK_BLK_TWIN: the waves with panel rows other than the leader (vwave 0) do not factor the
-    // diagonal block again (136 v_readlane + 136 FMAs each, a third of the chain): the leader
-    // publishes column j of L_bb and 1 / L_jj in LDS as it gets them and raises a counter; a
-    // twin follows one column behind, its multipliers LDS broadcasts.  (A wave's LDS operations
-    // are performed in order, so data before counter needs only a compiler barrier.)  Same
-    // multipliers, same FMAs in the same order: bit-identical.
-    constexpr bool TWINS = LK_BLK_TWIN && R > 64;  // some wave besides the leader has panel rows
-    const bool twin = TWINS && vwave != 0;         // wave-uniform
     if (has_rows) {
     {
         const int prow = vtid < R ? vtid : R - 1;
@@ -695,83 +672,32 @@ __device__ __forceinline__ void chol_step(f32x4 (&acc)[Cfg<NT>::T], float *__res
             a[4 * g + 1] = t.y;
             a[4 * g + 2] = t.z;
             a[4 * g + 3] = t.w;
-            if (!twin) {
-                const f32x4 u = *reinterpret_cast<const f32x4 *>(&P[g * C::P_SUB + sub * 4]);
-                d[4 * g + 0] = u.x;
-                d[4 * g + 1] = u.y;
-                d[4 * g + 2] = u.z;
-                d[4 * g + 3] = u.w;
-            }
+            const f32x4 u = *reinterpret_cast<const f32x4 *>(&P[g * C::P_SUB + sub * 4]);
+            d[4 * g + 0] = u.x;
+            d[4 * g + 1] = u.y;
+            d[4 * g + 2] = u.z;
+            d[4 * g + 3] = u.w;
         }
         if (vtid == 0) {
 #pragma unroll
             for (int c = 0; c < 16; ++c) a[c] = lds[C::OFF_Y + 16 * b + c];
         }
     }
-    if (!twin) {
-        sfor<0, 16>([&](auto jc) {
-            constexpr int j = decltype(jc)::value;
-            const float piv = bcast(d[j], j);
-            minpiv = fminf(minpiv, piv);
-            const float rinv = __builtin_amdgcn_rsqf(piv);
-            myrinv = (sub == j) ? rinv : myrinv;
-            d[j] *= rinv;  // lanes >= j: L[lane][j] (lane j: sqrt(pivot))
-            if constexpr (TWINS) {
-                // every row group holds the same d: four lanes store the same value
-                lds[C::OFF_COL + j * 16 + sub] = d[j];
-                lds[C::OFF_CRINV + j] = rinv;
-                asm volatile("" ::: "memory");
-                *reinterpret_cast<volatile int *>(&lds[C::OFF_FLAG]) = 16 * b + j + 1;
-            }
-            a[j] *= rinv;  // own row: x_j = (a_j - sum_{c<j} x_c L[j][c]) / L[j][j]
-            sfor<j + 1, 16>([&](auto cc) {
-                constexpr int c = decltype(cc)::value;
-                const float m = bcast(d[j], c);  // L[c][j]
-                d[c] = fmaf(-d[j], m, d[c]);
-                a[c] = fmaf(-a[j], m, a[c]);
-            });
+    sfor<0, 16>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        const float piv = bcast(d[j], j);
+        minpiv = fminf(minpiv, piv);
+        const float rinv = __builtin_amdgcn_rsqf(piv);
+        myrinv = (sub == j) ? rinv : myrinv;
+        d[j] *= rinv;  // lanes >= j: L[lane][j] (lane j: sqrt(pivot))
+        a[j] *= rinv;  // own row: x_j = (a_j - sum_{c<j} x_c L[j][c]) / L[j][j]
+        sfor<j + 1, 16>([&](auto cc) {
+            constexpr int c = decltype(cc)::value;
+            const float m = bcast(d[j], c);  // L[c][j]
+            d[c] = fmaf(-d[j], m, d[c]);
+            a[c] = fmaf(-a[j], m, a[c]);
         });
-    } else {
-        const unsigned flag_addr = (unsigned)(uintptr_t) reinterpret_cast<void *>(&lds[C::OFF_FLAG]);
-        sfor<0, 16>([&](auto jc) {
-            constexpr int j = decltype(jc)::value;
-            // wait for column j.  ONE asm statement, not a C loop: a loop in the middle of this
-            // straight-line code makes the register allocator spill the accumulators around it
-            // (scratch 20 -> 816 B at k = 128).  Bounded: a wait that gives up reports the row.
-            int seen, sval, spins;
-            asm volatile(
-                "s_mov_b32 %2, 0\n"
-                "1:\n\t"
-                "ds_read_b32 %0, %3\n\t"
-                "s_waitcnt lgkmcnt(0)\n\t"
-                "v_readfirstlane_b32 %1, %0\n\t"
-                "s_cmp_ge_i32 %1, %4\n\t"
-                "s_cbranch_scc1 2f\n\t"
-                "s_add_u32 %2, %2, 1\n\t"
-                "s_cmp_lt_u32 %2, 0x10000\n\t"
-                "s_cbranch_scc1 1b\n"
-                "2:"
-                : "=&v"(seen), "=&s"(sval), "=&s"(spins)
-                : "v"(flag_addr), "s"(16 * b + j + 1)
-                : "memory", "scc");
-            if (spins >= 0x10000) minpiv = -1.0f;  // (never: reported as a failed solve)
-            const float rinv = lds[C::OFF_CRINV + j];
-            float m[16];
-#pragma unroll
-            for (int q = (j + 1) / 4; q < 4; ++q) {
-                const f32x4 t = *reinterpret_cast<const f32x4 *>(&lds[C::OFF_COL + j * 16 + 4 * q]);
-                m[4 * q + 0] = t.x;
-                m[4 * q + 1] = t.y;
-                m[4 * q + 2] = t.z;
-                m[4 * q + 3] = t.w;
-            }
-            a[j] *= rinv;
-            sfor<j + 1, 16>([&](auto cc) {
-                constexpr int c = decltype(cc)::value;
-                a[c] = fmaf(-a[j], m[c], a[c]);
-            });
-        });
-    }
+    });
 
 #ifdef LK_BLK_PHASES
     bp2 = __builtin_amdgcn_s_memtime();
@@ -943,12 +869,6 @@ __device__ __forceinline__ void back_all(const f32x4 (&acc)[Cfg<NT>::T], float *
     (back_step<NT, NT - 1 - Bs>(acc, lds, lane, wave, wr, wc, rot), ...);
 }
 
-#ifndef LK_ALS_BLK_ATTR16
-#define LK_ALS_BLK_ATTR16 __attribute__((amdgpu_waves_per_eu(2)))
-#endif
-#ifndef LK_ALS_BLK_ATTR8
-#define LK_ALS_BLK_ATTR8 __attribute__((amdgpu_waves_per_eu(4)))
-#endif
 
 // ---- solve kernel: one workgroup per row ------------------------------------------------------
 template <int NT, bool IS64, bool EXPL, bool CTL>
@@ -1111,27 +1031,13 @@ __device__ __forceinline__ void als_blk_solve_body(
     float minpiv = 3.0e38f;
     LK_BP_T(bp_gram);
     LK_BP_ADD(0, bp_begin, bp_gram);
-#if LK_BLK_SOLVE_PRIO
-    __builtin_amdgcn_s_setprio(LK_BLK_SOLVE_PRIO);  // see als_chol.hip, LK_ALS_SOLVE_PRIO
-#endif
-#ifndef LK_BLK_ROTATE
-#define LK_BLK_ROTATE 1
-#endif
-    const int rot = LK_BLK_ROTATE ? (int)(t & 3) : 0;
+    const int rot = (int)(t & 3);
     chol_all<NT>(acc, lds, tid, lane, wave, wr, wc, rot, minpiv LK_BP_PASS,
                  std::make_integer_sequence<int, NT>{});
     LK_BP_T(bp_chol);
 
     // -- phase 3: back substitution ----------------------------------------------------------
-#ifdef LK_BLK_NO_BACK  // TIMING EXPERIMENT ONLY (wrong results): what the back substitution costs
-    if (tid < KP) lds[C::OFF_X + tid] = lds[C::OFF_Z + tid];
-    __syncthreads();
-#else
     back_all<NT>(acc, lds, lane, wave, wr, wc, rot, std::make_integer_sequence<int, NT>{});
-#endif
-#if LK_BLK_SOLVE_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
     LK_BP_T(bp_back);
     LK_BP_ADD(5, bp_chol, bp_back);
 
@@ -1187,8 +1093,8 @@ __device__ __forceinline__ void als_blk_solve_body(
                                                  (int64_t)blockIdx.x, y_ref, chunk_rt, n_yref); \
     }
 
-LK_BLK_KERNEL(als_blk_solve_kernel16, 16, LK_ALS_BLK_ATTR16)
-LK_BLK_KERNEL(als_blk_solve_kernel8, 8, LK_ALS_BLK_ATTR8)
+LK_BLK_KERNEL(als_blk_solve_kernel16, 16, __attribute__((amdgpu_waves_per_eu(2))))
+LK_BLK_KERNEL(als_blk_solve_kernel8, 8, __attribute__((amdgpu_waves_per_eu(4))))
 #undef LK_BLK_KERNEL
 
 // Dense solve of the rows [t_begin, t_end) of the plan order IF status[1] != 0, i.e. when the
@@ -1229,7 +1135,7 @@ __global__ __launch_bounds__(256) void als_blk_fallback_kernel(
 constexpr int WB128_N = 128;  // system size = Cfg<8>::KP
 
 template <bool IS64>
-__global__ __launch_bounds__(256) LK_ALS_BLK_ATTR8 void als_wb128_kernel(
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void als_wb128_kernel(
     const typename IndPtr<IS64>::type *__restrict__ indptr, const int32_t *__restrict__ indices,
     const float *__restrict__ values, const int32_t *__restrict__ order, int64_t n_tasks,
     const float *__restrict__ other, const float *__restrict__ z, float *__restrict__ this_,
@@ -1538,10 +1444,8 @@ static int launch_blk(const lk_als_plan *p, const void *indptr, const int32_t *i
     {
         // hybrid plans: the ordered slab sums (pure HBM streaming) go to the chains' stream and
         // run under the Woodbury kernels; the dense launch joins that stream anyway
-        // (LK_ALS_REDUCE_SIDE=0: launch stream)
         hipStream_t sg = st;
-        const char *e = getenv("LK_ALS_REDUCE_SIDE");
-        if (p->hybrid && n_yhyb > 0 && p->n_groups > 0 && p->side_rhs && !(e && e[0] == '0')) {
+        if (p->hybrid && n_yhyb > 0 && p->n_groups > 0 && p->side_rhs) {
             const char *s = getenv("LK_ALS_SIDE_STREAM");
             if (!(s && s[0] == '0')) {
                 int rc = plan_rhs_wait_main(p, st);

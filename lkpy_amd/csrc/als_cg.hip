@@ -463,12 +463,6 @@ __global__ __launch_bounds__(256, (NW == 1 && KP <= 128) ? 3 : 2) void als_cg_ke
     }
 }
 
-static bool cg_wave_rows_enabled()
-{
-    const char *e = getenv("LK_ALS_CG_WAVE_ROWS");  // 0: every CG row by a workgroup (A-B knob)
-    return !(e && e[0] == '0');
-}
-
 template <int KP, bool IS64>
 static int launch_cg(const lk_als_plan *p, const void *indptr, const int32_t *indices,
                      const float *values, int64_t n_rows, int k, float *this_,
@@ -488,7 +482,7 @@ static int launch_cg(const lk_als_plan *p, const void *indptr, const int32_t *in
     const int max_iter = p->cg_max_iter > 0 ? p->cg_max_iter : k;
     // rows that fit ONE wave's registers (<= 4096 / KP entries: tasks [t_cg1, n_rows)) take the
     // wave-per-row instance; not with a task-control block (the cancel poll is a workgroup matter)
-    int64_t t_w1 = p->ctl || !cg_wave_rows_enabled() ? n_rows : p->t_cg1;
+    int64_t t_w1 = p->ctl ? n_rows : p->t_cg1;
     if (t_w1 < t_begin) t_w1 = t_begin;
     const size_t lds = KP <= 128 ? (size_t)KP * KP * sizeof(float) : 0;  // OtOr resident
     auto k4 = als_cg_kernel<KP, IS64, 4>;

@@ -21,11 +21,10 @@
 // 4*k contiguous bytes).  The CSR (indices, values) stream is read coalesced, 64
 // entries per wave-load, and broadcast with ds_bpermute.
 //
-// Solve: the accumulator tiles are transposed through a wave-private LDS region
-// so that lane R holds row R of A' (primed order == a symmetric permutation of A,
-// which leaves the solution unchanged); an in-register right-looking Cholesky
-// with v_readlane broadcasts (no LDS traffic in the O(k^3) loop), forward
-// substitution in registers, back substitution against L^T staged in LDS.
+// Solve: the hybrid Cholesky (below) factors A' (primed order == a symmetric permutation of A,
+// which leaves the solution unchanged) in the accumulator tiles: panels of four columns in
+// lane = row layout, MFMA updates of the rest; forward substitution rides along, back
+// substitution against L^T staged in LDS.
 //
 // Roofline: f32 MFMA bound for k = 64 (nnz*(2k^2+2k) +
 // rows*(k^3/3 + 2k^2) flop per half-epoch); HBM traffic is the CSR stream plus
@@ -43,39 +42,6 @@
 
 #ifndef LK_ALS_RING
 #define LK_ALS_RING 4  // gather ring slots (8 costs 20 more registers: no gain at 3 waves/SIMD)
-#endif
-#ifndef LK_ALS_LOOKAHEAD
-#define LK_ALS_LOOKAHEAD 8  // multiplier groups read ahead in chol_step
-#endif
-#ifndef LK_ALS_GRAM_DMA
-#define LK_ALS_GRAM_DMA 1  // k = 64: gathered rows prefetched into LDS (global_load_lds)
-#endif
-#ifndef LK_ALS_DMA_PIPE
-#define LK_ALS_DMA_PIPE 1  // operands of group g+1 fetched from the ring before group g's MFMAs
-#endif
-#ifndef LK_ALS_GRAM_FENCE
-#define LK_ALS_GRAM_FENCE 1
-#endif
-#ifndef LK_ALS_SLAB_NT
-#define LK_ALS_SLAB_NT 1
-#endif
-#ifndef LK_ALS_SOLVE_PRIO
-#define LK_ALS_SOLVE_PRIO 0  // s_setprio level of a wave while it factors / substitutes (0: unchanged)
-#endif
-#ifndef LK_ALS_PANEL
-#define LK_ALS_PANEL 2  // 2: hybrid Cholesky (panels in lane = row layout + MFMA updates);
-                        // 0: the round-1 lane = row Cholesky (bit-identical results; A/B timing)
-#endif
-#ifndef LK_ALS_SOLVE_ATTR
-#if LK_ALS_PANEL
-// the hybrid solver keeps the matrix in its 40 accumulator registers: 4 waves per SIMD
-#define LK_ALS_SOLVE_ATTR __attribute__((amdgpu_waves_per_eu(4)))
-#endif
-#endif
-#ifndef LK_ALS_SOLVE_ATTR
-// At least 3 waves per SIMD: the k = 64 kernel then fits 168 registers with 13 dwords of
-// scratch instead of 248 registers (2 waves per SIMD): +14 % epochs/s (tools/als_variants.py)
-#define LK_ALS_SOLVE_ATTR __attribute__((amdgpu_waves_per_eu(3)))
 #endif
 
 namespace lk {
@@ -280,11 +246,9 @@ __device__ __forceinline__ void gram_accumulate(Gram<NT> &G, const int32_t *__re
                 ring_issue<NT>(R, g % RING, g + RING, rd_cur, other);
             else
                 ring_issue<NT>(R, g % RING, g + RING - 16, rd_nxt, other);
-#if LK_ALS_GRAM_FENCE
             // keep the scheduler from hoisting later groups' gathers over this point: the ring
             // depth (and with it the register count) is RING, not whatever fits
             __builtin_amdgcn_sched_barrier(0);
-#endif
         }
         float *tw = wr_cur;
         wr_cur = wr_nxt;
@@ -464,7 +428,6 @@ __device__ __forceinline__ void gram_accumulate_dma(Gram<4> &G, const int32_t *_
             nxt_col = cols[e];
             nxt_val = vals[e];
         }
-#if LK_ALS_DMA_PIPE
         // operands one group ahead: group g+1 is read out of the ring (its load is the next
         // one to land) before the 10 MFMAs of group g are issued, so the ds_read latency
         // hides behind them.  (Group 0's operands of the NEXT batch are fetched by that
@@ -490,22 +453,6 @@ __device__ __forceinline__ void gram_accumulate_dma(Gram<4> &G, const int32_t *_
             cur = nxt;
             __builtin_amdgcn_sched_barrier(0);
         }
-#else
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {
-            wait_vm<RING - 1>();
-            dma_consume<false, SEQY>(G, ring, g % RING, g, 64, rd_cur, expl);
-            if (g == 16 - RING - 2) {
-                wr_nxt[0] = __builtin_bit_cast(float, nxt_col);
-                wr_nxt[64] = nxt_val;
-            }
-            if (g < 16 - RING)
-                dma_issue(ring_lds, g % RING, g + RING, rd_cur, other);
-            else
-                dma_issue(ring_lds, g % RING, g + RING - 16, rd_nxt, other);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#endif
         if (slab && ((g0 + 16) & 63) == 0) {  // (wave-uniform) a 256-entry block is complete
             slab_store<4>(G, slab);
             slab += slab_floats<4>();
@@ -569,9 +516,6 @@ __device__ __forceinline__ void gram_accumulate_dma(Gram<4> &G, const int32_t *_
 // shrink); for a 256-entry chunk that is a quarter of the work.  Here the batch loop is unrolled
 // over the four batches, so every guard and every wait count is a compile-time constant.  Same
 // operations in the same order: bit-identical to gram_accumulate_dma on the same range.
-#ifndef LK_ALS_CHUNK256_FAST
-#define LK_ALS_CHUNK256_FAST 1
-#endif
 __device__ __forceinline__ void gram_accumulate_dma_256(Gram<4> &G, const int32_t *__restrict__ cols,
                                                         const float *__restrict__ vals, int64_t beg,
                                                         const float *__restrict__ other,
@@ -644,16 +588,11 @@ template <int NT>
 __device__ __forceinline__ void slab_store(const Gram<NT> &G, float *__restrict__ slab)
 {
     const int lane = lane_id();
-    // (LK_ALS_SLAB_NT: streaming stores -- a slab is written once and read once by another
-    // kernel; kept out of the L2 it would otherwise share with the gathered factor rows)
+    // (streaming stores -- a slab is written once and read once by another kernel; kept out of
+    // the L2 it would otherwise share with the gathered factor rows)
 #pragma unroll
-    for (int e = 0; e < als_tiles(NT); ++e) {
-#if LK_ALS_SLAB_NT
+    for (int e = 0; e < als_tiles(NT); ++e)
         __builtin_nontemporal_store(G.t[e], reinterpret_cast<f32x4 *>(slab + (e * 64 + lane) * 4));
-#else
-        *reinterpret_cast<f32x4 *>(slab + (e * 64 + lane) * 4) = G.t[e];
-#endif
-    }
 #pragma unroll
     for (int t = 0; t < NT; ++t) slab[als_tiles(NT) * 256 + lane * NT + t] = G.y[t];
 }
@@ -723,11 +662,9 @@ int launch_slab_group_reduce(const lk_als_plan *p, float *slabs, size_t slab_flo
 template <int NT>
 __host__ __device__ constexpr int chunk_lds_floats()
 {
-    return GRAM_STAGE_WORDS + ((LK_ALS_GRAM_DMA && NT == 4) ? GRAM_DMA_WORDS : 0);
+    return GRAM_STAGE_WORDS + (NT == 4 ? GRAM_DMA_WORDS : 0);
 }
 
-// (body + thin __global__ wrapper: the fused kernel below runs chunk blocks and solve blocks in
-// ONE launch)
 template <int NT, bool EXPL>
 __device__ __forceinline__ void als_chunk_body(
     const int32_t *__restrict__ indices, const float *__restrict__ values,
@@ -736,7 +673,7 @@ __device__ __forceinline__ void als_chunk_body(
     const int64_t blk, float *__restrict__ lds_flat,
     const int32_t *__restrict__ chunk_slab = nullptr, const int block_len = 0)
 {
-    constexpr bool DMA = LK_ALS_GRAM_DMA && NT == 4;
+    constexpr bool DMA = NT == 4;
     float(*stage_all)[chunk_lds_floats<NT>()] =
         reinterpret_cast<float(*)[chunk_lds_floats<NT>()]>(lds_flat);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -753,7 +690,7 @@ __device__ __forceinline__ void als_chunk_body(
             gram_accumulate_dma(G, indices, values, beg, beg + len, other, EXPL,
                                 stage_all[wave] + GRAM_STAGE_WORDS, stage_all[wave], slab);
             slab += (size_t)((len - 1) >> 8) * slab_floats<NT>();  // the last block is still in G
-        } else if (LK_ALS_CHUNK256_FAST && len == 256)  // a full reference-order block
+        } else if (len == 256)  // a full reference-order block
             gram_accumulate_dma_256(G, indices, values, beg, other, EXPL,
                                     stage_all[wave] + GRAM_STAGE_WORDS, stage_all[wave]);
         else
@@ -777,16 +714,7 @@ __global__ __launch_bounds__(256) void als_chunk_kernel(
                              (int64_t)blockIdx.x, lds_flat, chunk_slab, block_len);
 }
 
-// ---- solve: lane R owns row R of the (primed) normal matrix -----------------
-//
-// Right-looking Cholesky with the matrix rows in registers (lane i: a[c] = A'[i][c]).
-// Step j: pivot broadcast (v_readlane), rinv = rsq(pivot), column j of L
-// (strictly lower: zero on and above the diagonal, so later updates need no lane
-// masks) is written to a packed LDS image; the NEXT pivot's update uses a
-// v_readlane fast path, the bulk of the trailing update reads L_cj back as
-// wave-uniform ds_read_b128 broadcasts (4 multipliers per LDS instruction), which
-// keeps the O(k^3/3) loop at one v_fma per element.  Forward substitution runs on
-// the register rows, back substitution on the LDS image (column access).
+// ---- solve: the packed L image ---------------------------------------------------------------
 //
 // Packed strictly-lower image: column j holds rows c in [c0(j), KP), c0 = (j+1)&~3
 // (16-byte aligned segments); off(j) = 4*KP*m - 8m^2 + 4m + r*(KP - 4m), j = 4m + r.
@@ -801,150 +729,7 @@ struct LPack {
     static constexpr int SIZE = KP * KP / 2 + KP;
 };
 
-// Row storage: KP floats as KP/2 register PAIRS so the trailing update can use
-// v_pk_fma_f32 (two FMAs per VALU issue).  AT(a, c) is element c.
-#define AT(a, c) ((a)[(c) >> 1][(c) & 1])
-
-// One pipelined factorisation step (J compile-time): with column J of L in `lj`,
-// (1) finish column J+1 through the v_readlane fast path and start ITS pivot chain
-// (readlane -> rsq -> scale -> LDS write) while (2) the bulk of step J's trailing
-// update (c >= J+2) streams its multipliers back from LDS.  The two are independent,
-// so the v_pk_fma stream covers the pivot latency.
-template <int KP, int J>
-__device__ __forceinline__ void chol_step(f32x2 (&a)[KP / 2], float &lj, float &dinv,
-                                          float &minpiv, float *__restrict__ lds)
-{
-    using P = LPack<KP>;
-    const int lane = lane_id();
-    const float ln = bcast(lj, J + 1);
-    AT(a, J + 1) = fmaf(-lj, ln, AT(a, J + 1));
-    const float ajj = bcast(AT(a, J + 1), J + 1);
-    minpiv = fminf(minpiv, ajj);
-    const float rinv = __builtin_amdgcn_rsqf(ajj);
-    // 1/L_jj goes to a small LDS array (read back once, per lane, after the factorisation):
-    // a per-step `dinv = lane == j ? rinv : dinv` select is sunk by the compiler to the end,
-    // which keeps all k rinv values alive in registers
-    if (lane == 0) lds[P::SIZE + J + 1] = rinv;
-    const float lnext = (lane > J + 1) ? AT(a, J + 1) * rinv : 0.f;
-    AT(a, J + 1) = lnext;
-    if constexpr (J + 2 < KP) {
-        if (lane >= P::c0(J + 1) && lane < KP) lds[P::off(J + 1) + lane - P::c0(J + 1)] = lnext;
-    }
-    // multipliers L_cJ, c >= J+2, as wave-uniform ds_read_b128 broadcasts; the reads run
-    // LOOKAHEAD groups ahead of the FMAs that use them
-    constexpr int C0 = (J + 2) & ~3;
-    constexpr int NG = (KP - C0) / 4;
-    constexpr int LOOKAHEAD = LK_ALS_LOOKAHEAD;
-    if constexpr (NG > 0) {
-        const float *col = lds + P::off(J) - P::c0(J);
-        const f32x2 nl = f32x2{-lj, -lj};
-        f32x4 lq[NG];
-#pragma unroll
-        for (int g = 0; g < NG && g < LOOKAHEAD; ++g)
-            lq[g] = *reinterpret_cast<const f32x4 *>(col + C0 + 4 * g);
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            if (g + LOOKAHEAD < NG)
-                lq[g + LOOKAHEAD] =
-                    *reinterpret_cast<const f32x4 *>(col + C0 + 4 * (g + LOOKAHEAD));
-            const int c4 = C0 + 4 * g;
-            // a_ic -= L_iJ * L_cJ for c = c4 .. c4+3, c >= J+2
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int c = c4 + 2 * h;
-                const f32x2 m = f32x2{lq[g][2 * h], lq[g][2 * h + 1]};
-                if (c >= J + 2)
-                    a[c >> 1] = __builtin_elementwise_fma(nl, m, a[c >> 1]);
-                else if (c + 1 >= J + 2)
-                    AT(a, c + 1) = fmaf(-lj, m[1], AT(a, c + 1));
-            }
-            // pin the updates here: without it the compiler sinks every FMA chain down to
-            // the step that first reads a[c] (a left-looking schedule that keeps all
-            // multipliers alive and spills hundreds of registers)
-            asm volatile("" : "+v"(a[c4 >> 1]), "+v"(a[(c4 >> 1) + 1]));
-        }
-    }
-    lj = lnext;
-    __builtin_amdgcn_sched_barrier(0);
-}
-
-template <int KP, int... Js>
-__device__ __forceinline__ void chol_steps(f32x2 (&a)[KP / 2], float &lj, float &dinv,
-                                           float &minpiv, float *__restrict__ lds,
-                                           std::integer_sequence<int, Js...>)
-{
-    (chol_step<KP, Js>(a, lj, dinv, minpiv, lds), ...);
-}
-
-// a: row `lane` of A' (entries c <= lane valid, anything above), b = rhs.  On return
-// b = solution for primed row `lane`; returns the smallest pivot seen (<= 0 or a
-// non-finite solution => not SPD).
-template <int KP>
-__device__ __forceinline__ float chol_solve(f32x2 (&a)[KP / 2], float &b,
-                                            float *__restrict__ lds
-#ifdef LK_ALS_PHASES
-                                            ,
-                                            unsigned long long *tmid
-#endif
-)
-{
-    using P = LPack<KP>;
-    const int lane = lane_id();
-    float minpiv = 3.0e38f;
-    float dinv = 0.f;  // lane j keeps 1 / L_jj
-
-    // column 0
-    float lj;
-    {
-        const float ajj = bcast(AT(a, 0), 0);
-        minpiv = fminf(minpiv, ajj);
-        const float rinv = __builtin_amdgcn_rsqf(ajj);
-        if (lane == 0) lds[P::SIZE] = rinv;
-        lj = (lane > 0) ? AT(a, 0) * rinv : 0.f;  // strictly-lower column 0
-        AT(a, 0) = lj;
-        if (lane < KP) lds[P::off(0) + lane - P::c0(0)] = lj;
-    }
-    chol_steps<KP>(a, lj, dinv, minpiv, lds, std::make_integer_sequence<int, KP - 1>{});
-#ifdef LK_ALS_PHASES
-    asm volatile("" : "+v"(lj), "+v"(b));
-    *tmid = __builtin_amdgcn_s_memtime();
-#endif
-    dinv = (lane < KP) ? lds[P::SIZE + lane] : 0.f;
-    // forward: L z = y.  a[j] is zero for lanes <= j, so no masks: lane i only
-    // receives the terms j < i; z_i = b_i * dinv_i.
-#pragma unroll
-    for (int j = 0; j < KP; ++j) {
-        const float zj = bcast(b * dinv, j);
-        b = fmaf(-AT(a, j), zj, b);
-    }
-    b *= dinv;
-    // backward: L^T x = z.  Lane i needs L[j][i] (j > i) = column i of the LDS image,
-    // read four rows at a time (ds_read_b128; rows <= i inside the column are stored
-    // zeros, rows below c0(i) are outside it).
-    const int my_c0 = (lane + 1) & ~3;
-    int my_off = P::off(lane) - my_c0;
-    // tie the column address to the finished forward pass: otherwise all 16 ds_read_b128 of
-    // the back substitution are hoisted above it and sit on 64 VGPRs next to the 64 of `a`
-    asm volatile("" : "+v"(my_off), "+v"(b));
-    const float *mycol = lds + my_off;
-#pragma unroll
-    for (int j4 = KP / 4 - 1; j4 >= 0; --j4) {
-        f32x4 l4 = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (lane < KP - 1 && 4 * j4 >= my_c0) l4 = *reinterpret_cast<const f32x4 *>(mycol + 4 * j4);
-#pragma unroll
-        for (int u = 3; u >= 0; --u) {
-            const int j = 4 * j4 + u;
-            if (j >= 1) {
-                const float xj = bcast(b * dinv, j);
-                b = fmaf(-l4[u], xj, b);
-            }
-        }
-    }
-    b *= dinv;
-    return minpiv;
-}
-
-// ---- hybrid Cholesky (LK_ALS_PANEL == 2) -------------------------------------------------------
+// ---- hybrid Cholesky ---------------------------------------------------------------------------
 //
 // The matrix stays in the accumulator tiles; panels of FOUR columns J .. J+3 are
 //   E. extracted into the lane = row layout (lane i: A'[i][J .. J+3]; by symmetry these are the
@@ -966,10 +751,6 @@ __host__ __device__ constexpr int hybrid_lds_floats()
     return LPack<NT * 16>::SIZE + NT * 16 + 256;
 }
 
-
-#ifndef LK_ALS_NOBRANCH
-#define LK_ALS_NOBRANCH 1
-#endif
 template <int NT, int M>
 __device__ __forceinline__ void hybrid_step(Gram<NT> &G, float &b, float &minpiv,
                                             float *__restrict__ lds, const int lane)
@@ -997,7 +778,6 @@ __device__ __forceinline__ void hybrid_step(Gram<NT> &G, float &b, float &minpiv
         const float piv = bcast(pr[s0], j);
         minpiv = fminf(minpiv, piv);
         const float rinv = __builtin_amdgcn_rsqf(piv);
-#if LK_ALS_NOBRANCH
         // (no exec-mask round trips in the column loop: rinv is wave-uniform, every lane stores
         // the same value to the same word; lanes outside the stored segment of column j aim at
         // their own word of the extraction scratch, which is dead until the next panel)
@@ -1008,13 +788,6 @@ __device__ __forceinline__ void hybrid_step(Gram<NT> &G, float &b, float &minpiv
             float *dst = in ? &lds[P::off(j) + lane - P::c0(j)] : &scr[lane];
             *dst = lj;
         }
-#else
-        if (lane == 0) rinvarr[j] = rinv;
-        const float lj = (lane > j) ? pr[s0] * rinv : 0.f;  // strictly-lower column j
-        if (j + 1 < KP) {
-            if (lane >= P::c0(j) && lane < KP) lds[P::off(j) + lane - P::c0(j)] = lj;
-        }
-#endif
         // forward substitution: z_j = y_j / L_jj, y -= L[:, j] z_j
         const float zj = bcast(b, j) * rinv;
         b = fmaf(-lj, zj, b);
@@ -1097,36 +870,6 @@ __device__ __forceinline__ float hybrid_solve(Gram<NT> &G, float &b, float *__re
     return minpiv;
 }
 
-// transposition buffer: row R' (tile row tr = R' >> 4) keeps its (tr+1)*16 lower
-// entries; stride inside tile row tr is (tr+1)*16 + 4 floats (16-byte aligned).  For NT = 4
-// the transposition runs in TWO passes (tile rows 0..2, then tile row 3 alone, both from
-// offset 0): 6.9 KiB instead of 11 KiB, so that the wave's LDS is the 8.7 KiB of the L image
-// and FOUR workgroups fit a CU.
-template <int NT>
-struct TPack {
-    static constexpr int SPLIT = NT == 4 ? 3 : NT;  // tile rows of the first pass
-    __host__ __device__ static constexpr int stride(int tr) { return (tr + 1) * 16 + 4; }
-    __host__ __device__ static constexpr int base(int tr)
-    {
-        int b = 0;
-        for (int t = (tr >= SPLIT ? SPLIT : 0); t < tr; ++t) b += 16 * stride(t);
-        return b;
-    }
-    static constexpr int SIZE = base(SPLIT) > 16 * stride(NT - 1) ? base(SPLIT)
-                                                                  : (NT > SPLIT ? 16 * stride(NT - 1) : base(NT));
-};
-
-template <int NT>
-__host__ __device__ constexpr int solve_lds_floats()
-{
-#if LK_ALS_PANEL
-    return hybrid_lds_floats<NT>();
-#endif
-    // the L image is followed by the k reciprocal pivots
-    return TPack<NT>::SIZE > LPack<NT * 16>::SIZE + NT * 16 ? TPack<NT>::SIZE
-                                                            : LPack<NT * 16>::SIZE + NT * 16;
-}
-
 // EXPL: explicit-feedback model (explicit.rs) instead of the implicit one (implicit.rs); a
 // template parameter so that the implicit instantiation carries nothing of it
 // CTL: poll the task-control block (cancel) before the row and count it when done; a
@@ -1150,8 +893,8 @@ __device__ __forceinline__ void als_solve_body(
     const int64_t blk, float *__restrict__ lds_flat)
 {
     constexpr int KP = NT * 16;
-    float(*lds_all)[solve_lds_floats<NT>()] =
-        reinterpret_cast<float(*)[solve_lds_floats<NT>()]>(lds_flat);
+    float(*lds_all)[hybrid_lds_floats<NT>()] =
+        reinterpret_cast<float(*)[hybrid_lds_floats<NT>()]>(lds_flat);
 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = lane_id();
@@ -1210,12 +953,10 @@ __device__ __forceinline__ void als_solve_body(
     } else {
         // (the solver's LDS is idle while the normal matrix is built: it stages the CSR
         // batches and, for k = 64, holds the ring of prefetched factor rows)
-#if LK_ALS_GRAM_DMA && LK_ALS_PANEL == 2
         if constexpr (NT == 4)
             gram_accumulate_dma<SEQY && !YREF>(G, indices, values, beg, end, other, EXPL, lds,
                                                lds + LPack<KP>::SIZE + KP);
         else
-#endif
             gram_accumulate<NT, SEQY && !YREF>(G, indices, values, beg, end, other, ld_other,
                                                EXPL, lds);
     }
@@ -1252,7 +993,6 @@ __device__ __forceinline__ void als_solve_body(
 #pragma unroll
         for (int tt = 0; tt < NT; ++tt) G.y[tt] = y_ref[(int64_t)t * KP + sub * NT + tt];
     }
-#if LK_ALS_PANEL
     const float old = my_valid ? xrow[my_f] : 0.f;
     float b;
 #ifdef LK_ALS_PHASES
@@ -1262,79 +1002,7 @@ __device__ __forceinline__ void als_solve_body(
     asm volatile("" : "+v"(b));
     LK_PHASE_T(ph5);
 #else
-    // The factorisation is one long dependent chain (v_readlane -> rsq -> mul -> fma per column):
-    // a wave in it has ONE ready instruction at a time, while the co-resident waves in their
-    // normal-matrix loops always have several.  LK_ALS_SOLVE_PRIO > 0 lets the chain win the
-    // SIMD's issue arbitration for its duration.
-#if LK_ALS_SOLVE_PRIO
-    __builtin_amdgcn_s_setprio(LK_ALS_SOLVE_PRIO);
-#endif
     const float minpiv = hybrid_solve<NT>(G, b, lds);
-#if LK_ALS_SOLVE_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
-#endif
-#else
-    // tile (ti,tj): lane holds D[i = slot*4+r][j = sub] = A'[ti*16+i][tj*16+j]
-    //             = A'[row' = tj*16+sub][col' = ti*16 + slot*4 + r]  (symmetry)
-    // lane = primed row: tile row slot (= lane >> 4), row-in-tile sub
-    f32x2 a[KP / 2];
-    float b = 0.f;
-    {
-        using T = TPack<NT>;
-        int rowoff = 0;
-#pragma unroll
-        for (int tr = 0; tr < NT; ++tr)
-            rowoff = (slot == tr) ? T::base(tr) + sub * T::stride(tr) : rowoff;
-#pragma unroll
-        for (int pass = 0; pass < (T::SPLIT < NT ? 2 : 1); ++pass) {
-            const int t0 = pass == 0 ? 0 : T::SPLIT, t1 = pass == 0 ? T::SPLIT : NT;
-#pragma unroll
-            for (int tj = t0; tj < t1; ++tj)
-#pragma unroll
-                for (int ti = 0; ti <= tj; ++ti)
-                    *reinterpret_cast<f32x4 *>(
-                        &lds[T::base(tj) + sub * T::stride(tj) + ti * 16 + slot * 4]) =
-                        G.t[tidx(ti, tj)];
-            // the wave's LDS operations complete in order: no barrier between the passes
-            const bool mine = lane < KP && slot >= t0 && slot < t1;
-#pragma unroll
-            for (int c4 = 0; c4 < KP / 4; ++c4) {
-                if ((c4 >> 2) >= t1) continue;  // beyond this pass's widest row
-                f32x4 v = pass == 0 ? f32x4{0.f, 0.f, 0.f, 0.f}
-                                    : f32x4{a[c4 * 2][0], a[c4 * 2][1], a[c4 * 2 + 1][0],
-                                            a[c4 * 2 + 1][1]};
-                if (mine && (c4 >> 2) <= slot)
-                    v = *reinterpret_cast<const f32x4 *>(&lds[rowoff + c4 * 4]);
-                a[c4 * 2 + 0] = f32x2{v.x, v.y};
-                a[c4 * 2 + 1] = f32x2{v.z, v.w};
-            }
-            if (pass == 0 && T::SPLIT < NT) {
-                // columns only the last tile row has: defined (zero) before pass 2 merges
-#pragma unroll
-                for (int c4 = T::SPLIT * 4; c4 < KP / 4; ++c4) {
-                    a[c4 * 2 + 0] = f32x2{0.f, 0.f};
-                    a[c4 * 2 + 1] = f32x2{0.f, 0.f};
-                }
-            }
-        }
-    }
-    // rhs for primed row `lane`: tile lane>>4, sub lane&15 -> G.y[lane>>4] of this lane
-#pragma unroll
-    for (int tt = 0; tt < NT; ++tt) b = (slot == tt) ? G.y[tt] : b;
-    if (lane >= KP) b = 0.f;
-
-    const float old = my_valid ? xrow[my_f] : 0.f;
-#ifdef LK_ALS_PHASES
-    asm volatile("" : "+v"(a[0]), "+v"(a[KP / 2 - 1]), "+v"(b));
-    LK_PHASE_T(ph3);
-    unsigned long long ph4 = 0;
-    const float minpiv = chol_solve<KP>(a, b, lds, &ph4);
-    asm volatile("" : "+v"(b));
-    LK_PHASE_T(ph5);
-#else
-    const float minpiv = chol_solve<KP>(a, b, lds);
-#endif
 #endif
     // not SPD: a non-positive pivot, or NaN/Inf anywhere in the solution
     const bool bad = !(minpiv > 0.f) || (my_valid && !(fabsf(b) <= 3.0e38f));
@@ -1362,8 +1030,9 @@ __device__ __forceinline__ void als_solve_body(
 #endif
 }
 
+// the hybrid solver keeps the matrix in its 40 accumulator registers: 4 waves per SIMD
 template <int NT, bool IS64, bool EXPL, bool CTL, bool YREF = false, bool SEQY = false>
-__global__ __launch_bounds__(256) LK_ALS_SOLVE_ATTR void als_solve_kernel(
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void als_solve_kernel(
     const typename IndPtr<IS64>::type *__restrict__ indptr, const int32_t *__restrict__ indices,
     const float *__restrict__ values, const int32_t *__restrict__ order, int64_t n_rows,
     const int32_t *__restrict__ row_slab, const float *__restrict__ other, int ld_other,
@@ -1372,56 +1041,11 @@ __global__ __launch_bounds__(256) LK_ALS_SOLVE_ATTR void als_solve_kernel(
     int k, float reg, TaskCtlDev ctl, const float *__restrict__ y_ref = nullptr,
     int chunk_rt = 0)
 {
-    __shared__ __attribute__((aligned(16))) float lds_flat[4 * solve_lds_floats<NT>()];
+    __shared__ __attribute__((aligned(16))) float lds_flat[4 * hybrid_lds_floats<NT>()];
     als_solve_body<NT, IS64, EXPL, CTL, YREF, SEQY>(indptr, indices, values, order, n_rows,
                                                     row_slab, other, ld_other, this_, ld_this,
                                                     otor_p, slabs, row_delta, status, k, reg, ctl,
                                                     y_ref, chunk_rt, (int64_t)blockIdx.x, lds_flat);
-}
-
-// ---- chunk blocks and short-row solve blocks in ONE launch (round 4; an experiment, off by
-// default: see als_fused_enabled) -----------------------------------------------------------------
-// The chunk kernel is pure matrix-core work (one wave per 1024-entry chunk, no factorisation); the
-// solve kernel alternates matrix-core work with a latency-bound v_readlane chain and keeps the
-// matrix cores 58-62 % busy.  Launched one after the other they never overlap -- and a second
-// stream does not help, the first launch fills every wave slot.  Here the chunk blocks are
-// INTERLEAVED with the solve blocks of the rows that need no chunks (block b is a chunk block
-// when b % stride == 0, until the chunks run out), so at any time the resident waves are a mix of
-// both: the chunk waves' MFMAs fill the issue slots the factorisation chains leave.  No
-// dependency between the two kinds of blocks: the rows that DO consume slabs (a prefix of the
-// longest-first order: rows [0, n_long)) are solved by a small launch afterwards, behind the
-// slab-group reduction -- same arithmetic, same bits as the separate launches.
-template <int NT>
-__host__ __device__ constexpr int fused_lds_floats()
-{
-    return 4 * (solve_lds_floats<NT>() > chunk_lds_floats<NT>() ? solve_lds_floats<NT>()
-                                                                : chunk_lds_floats<NT>());
-}
-
-template <int NT, bool IS64, bool EXPL>
-__global__ __launch_bounds__(256) LK_ALS_SOLVE_ATTR void als_fused_kernel(
-    const typename IndPtr<IS64>::type *__restrict__ indptr, const int32_t *__restrict__ indices,
-    const float *__restrict__ values, const int32_t *__restrict__ order, int64_t n_short,
-    const int32_t *__restrict__ row_slab, const float *__restrict__ other, int ld_other,
-    float *__restrict__ this_, int ld_this, const float *__restrict__ otor_p,
-    float *__restrict__ slabs, float *__restrict__ row_delta, int *__restrict__ status, int k,
-    float reg, const int64_t *__restrict__ chunk_beg, const int32_t *__restrict__ chunk_len,
-    int64_t n_chunks, int n_cb, int stride)
-{
-    __shared__ __attribute__((aligned(16))) float lds_flat[fused_lds_floats<NT>()];
-    const int b = blockIdx.x;
-    const int q = b / stride;
-    const bool slot0 = (b - q * stride) == 0;  // wave-uniform: the whole block takes one role
-    if (slot0 && q < n_cb) {
-        als_chunk_body<NT, EXPL>(indices, values, chunk_beg, chunk_len, n_chunks, other, ld_other,
-                                 slabs, (int64_t)q, lds_flat);
-    } else {
-        const int before = slot0 ? n_cb : (q + 1 < n_cb ? q + 1 : n_cb);  // chunk blocks below b
-        als_solve_body<NT, IS64, EXPL, false, false>(
-            indptr, indices, values, order, n_short, row_slab, other, ld_other, this_, ld_this,
-            otor_p, slabs, row_delta, status, k, reg, TaskCtlDev{}, nullptr, 0,
-            (int64_t)(b - before), lds_flat);
-    }
 }
 
 // ---- Woodbury row solve for rows with 17..64 entries at padded k = 128 / 256 -----------------
@@ -1710,29 +1334,6 @@ int launch_delta_reduce(const float *row_delta, int64_t n_rows, float *partial, 
     return LK_OK;
 }
 
-// LK_ALS_FUSED=1: chunk blocks and short-row solve blocks in one launch (als_fused_kernel).
-// OFF by default -- measured (tools/fused_ab.py, ML-25M shape, same bits): k = 64 3.35 vs 3.12
-// ms/epoch, k = 32 1.28 vs 1.19: the chunk waves' MFMAs do not fill "idle" matrix-core time of the
-// factorisation chains, they compete with them for the SIMD's issue slots (user half 1.89 vs
-// 1.70 ms, item half 1.38 vs 1.37).  Kept as a knob so that the experiment can be repeated.
-static bool als_fused_enabled()
-{
-    const char *e = getenv("LK_ALS_FUSED");
-    return e && e[0] == '1';
-}
-
-static bool seqy_enabled()
-{
-    const char *e = getenv("LK_ALS_SEQY");
-    return !(e && e[0] == '0');
-}
-
-static bool reduce_on_side()
-{
-    const char *e = getenv("LK_ALS_REDUCE_SIDE");
-    return !(e && e[0] == '0');
-}
-
 template <int NT, bool IS64, bool EXPL = false>
 static int launch_chol(const lk_als_plan *p, const void *indptr, const int32_t *indices,
                        const float *values, int64_t n_rows, int k, float *this_, int ld_this,
@@ -1769,113 +1370,81 @@ static int launch_chol(const lk_als_plan *p, const void *indptr, const int32_t *
                             : (p->ctl ? nullptr : p->d_yref);
     const int64_t n_y = !yref ? 0 : (p->hybrid ? std::min<int64_t>(p->n_long, n_solve) : n_solve);
     const int ref_chunk = (p->ref_order || p->hybrid) ? p->chunk : 0;
-    // one launch for the chunks AND the rows that need none (als_fused_kernel): the plain exact
-    // half-epoch only -- no task control, no reference order, not the CG hybrid's prefix
-    const bool fused = als_fused_enabled() && p->n_chunks > 0 && !p->ctl && !yref &&
-                       !ref_chunk && p->dense_limit < 0 && p->n_long < n_rows;
     using IT = typename IndPtr<IS64>::type;
-    if (fused) {
-        const int64_t n_short = n_rows - p->n_long;  // tasks [n_long, n_rows) of the order
-        const int64_t n_cb = (p->n_chunks + 3) / 4, n_sb = (n_short + 3) / 4;
-        int64_t stride = (n_cb + n_sb) / n_cb;
-        if (stride < 1) stride = 1;
-        hipLaunchKernelGGL((als_fused_kernel<NT, IS64, EXPL>), dim3((unsigned)(n_cb + n_sb)),
-                           dim3(256), 0, st, static_cast<const IT *>(indptr), indices, values,
-                           p->d_order + p->n_long, n_short, p->d_row_slab, other, ld_other, this_,
-                           ld_this, otor_p, slabs, row_delta, status, k, reg, p->d_chunk_beg,
-                           p->d_chunk_len, p->n_chunks, (int)n_cb, (int)stride);
-        int rc = launch_slab_group_reduce(p, slabs, slab_floats<NT>(), st);
+    // The chains run on the plan's second stream, beside the chunk kernel and the solve of
+    // the other rows; only the (small) solve launch of the long rows waits for them.  They are
+    // ENQUEUED BEHIND the chunk kernel (the fork point is in front of it): the chain kernel is
+    // LDS-heavy and latency-bound; enqueued first it takes every CU's LDS for its first round
+    // of workgroups and the MFMA-bound chunk kernel waits (measured: +0.25 ms per cfg2 item
+    // half); enqueued second it trickles in as chunk workgroups retire and does most of its
+    // work under the solve of the short rows.
+    hipStream_t sr = st;
+    if (n_y > 0) {
+        int rc = plan_fork_rhs(p, st, &sr);
         if (rc != LK_OK) return rc;
-        if (tm) LK_HIP_CHECK(hipEventRecord(p->ev[p->timing_n][1], st));
-        if (p->n_long > 0)  // the rows that consume the slabs
-            hipLaunchKernelGGL((als_solve_kernel<NT, IS64, EXPL, false>),
-                               dim3((unsigned)((p->n_long + 3) / 4)), dim3(256), 0, st,
-                               static_cast<const IT *>(indptr), indices, values, p->d_order,
-                               p->n_long, p->d_row_slab, other, ld_other, this_, ld_this, otor_p,
-                               slabs, row_delta, status, k, reg, TaskCtlDev{});
-    } else {
-        // The chains run on the plan's second stream, beside the chunk kernel and the solve of
-        // the other rows; only the (small) solve launch of the long rows waits for them.  They are
-        // ENQUEUED BEHIND the chunk kernel (the fork point is in front of it): the chain kernel is
-        // LDS-heavy and latency-bound; enqueued first it takes every CU's LDS for its first round
-        // of workgroups and the MFMA-bound chunk kernel waits (measured: +0.25 ms per cfg2 item
-        // half); enqueued second it trickles in as chunk workgroups retire and does most of its
-        // work under the solve of the short rows.  LK_ALS_CHAIN_FIRST=1: the old order.
-        hipStream_t sr = st;
-        const char *cf = getenv("LK_ALS_CHAIN_FIRST");
-        const bool chain_first = cf && cf[0] == '1';
-        auto launch_chains = [&]() -> int {
-            return launch_rhs_reference(p, indptr, IS64 ? 1 : 0, indices, values, p->d_order, n_y,
-                                        other, EXPL, yref, sr);
-        };
-        if (n_y > 0) {
-            int rc = plan_fork_rhs(p, st, &sr);
+    }
+    if (p->n_chunks > 0) {
+        hipLaunchKernelGGL((als_chunk_kernel<NT, EXPL>),
+                           dim3((unsigned)((p->n_chunks + 3) / 4)), dim3(256), 0, st, indices,
+                           values, p->d_chunk_beg, p->d_chunk_len, p->n_chunks, other,
+                           ld_other, slabs, p->d_chunk_slab,
+                           p->unit > p->chunk ? (int)p->chunk : 0);
+    }
+    if (n_y > 0) {
+        int rc = launch_rhs_reference(p, indptr, IS64 ? 1 : 0, indices, values, p->d_order, n_y,
+                                      other, EXPL, yref, sr);
+        if (rc != LK_OK) return rc;
+    }
+    if (p->n_chunks > 0) {
+        // the ordered slab sums of reference-order rows are pure HBM streaming: on the second
+        // stream (behind the chains) they run under the solve of the rows that need no slabs
+        hipStream_t sg = st;
+        if (n_y > 0 && sr != st) {
+            int rc = plan_rhs_wait_main(p, st);
             if (rc != LK_OK) return rc;
-            if (chain_first && (rc = launch_chains()) != LK_OK) return rc;
+            sg = sr;
         }
-        if (p->n_chunks > 0) {
-            hipLaunchKernelGGL((als_chunk_kernel<NT, EXPL>),
-                               dim3((unsigned)((p->n_chunks + 3) / 4)), dim3(256), 0, st, indices,
-                               values, p->d_chunk_beg, p->d_chunk_len, p->n_chunks, other,
-                               ld_other, slabs, p->d_chunk_slab,
-                               p->unit > p->chunk ? (int)p->chunk : 0);
-        }
-        if (n_y > 0 && !chain_first) {
-            int rc = launch_chains();
-            if (rc != LK_OK) return rc;
-        }
-        if (p->n_chunks > 0) {
-            // the ordered slab sums of reference-order rows are pure HBM streaming: on the second
-            // stream (behind the chains) they run under the solve of the rows that need no slabs
-            // (LK_ALS_REDUCE_SIDE=0: launch stream)
-            hipStream_t sg = st;
-            if (n_y > 0 && sr != st && reduce_on_side()) {
-                int rc = plan_rhs_wait_main(p, st);
-                if (rc != LK_OK) return rc;
-                sg = sr;
-            }
-            int rc = launch_slab_group_reduce(p, slabs, slab_floats<NT>(), sg);
-            if (rc != LK_OK) return rc;
-        }
-        if (tm) LK_HIP_CHECK(hipEventRecord(p->ev[p->timing_n][1], st));
-        const IT *ip = static_cast<const IT *>(indptr);
-#define LK_SOLVE_LAUNCH(CTLV, YREFV, T0, NTASKS, YPTR)                                            \
+        int rc = launch_slab_group_reduce(p, slabs, slab_floats<NT>(), sg);
+        if (rc != LK_OK) return rc;
+    }
+    if (tm) LK_HIP_CHECK(hipEventRecord(p->ev[p->timing_n][1], st));
+    const IT *ip = static_cast<const IT *>(indptr);
+#define LK_SOLVE_LAUNCH(CTLV, YREFV, T0, NTASKS, YPTR)                                        \
     LK_SOLVE_LAUNCH_S(CTLV, YREFV, false, T0, NTASKS, YPTR)
-#define LK_SOLVE_LAUNCH_S(CTLV, YREFV, SEQV, T0, NTASKS, YPTR)                                    \
-    hipLaunchKernelGGL((als_solve_kernel<NT, IS64, EXPL, CTLV, YREFV, SEQV>),                      \
-                       dim3((unsigned)(((NTASKS) + 3) / 4)), dim3(256), 0, st, ip, indices,        \
-                       values, p->d_order + (T0), (NTASKS), p->d_row_slab, other, ld_other, this_, \
-                       ld_this, otor_p, slabs, row_delta, status, k, reg,                          \
+#define LK_SOLVE_LAUNCH_S(CTLV, YREFV, SEQV, T0, NTASKS, YPTR)                                \
+    hipLaunchKernelGGL((als_solve_kernel<NT, IS64, EXPL, CTLV, YREFV, SEQV>),                  \
+                       dim3((unsigned)(((NTASKS) + 3) / 4)), dim3(256), 0, st, ip, indices,    \
+                       values, p->d_order + (T0), (NTASKS), p->d_row_slab, other, ld_other,    \
+                       this_, ld_this, otor_p, slabs, row_delta, status, k, reg,               \
                        (CTLV) ? p->ctl->dev() : TaskCtlDev{}, (YPTR), ref_chunk)
-        // the rows that take their own right-hand side first (longest-first inside the launch) ...
-        // (hybrid / reference-order plans: these rows form y in the reference's order inside
-        // their Gram loop -- SEQY; LK_ALS_SEQY=0: the four-slot sums of the accurate mode)
-        const bool seqy = (p->hybrid || p->ref_order) && seqy_enabled();
-        if (n_solve > n_y) {
-            if (p->ctl) {
-                if (seqy)
-                    LK_SOLVE_LAUNCH_S(true, false, true, n_y, n_solve - n_y, nullptr);
-                else
-                    LK_SOLVE_LAUNCH(true, false, n_y, n_solve - n_y, nullptr);
-            } else {
-                if (seqy)
-                    LK_SOLVE_LAUNCH_S(false, false, true, n_y, n_solve - n_y, nullptr);
-                else
-                    LK_SOLVE_LAUNCH(false, false, n_y, n_solve - n_y, nullptr);
-            }
-        }
-        // ... then the rows of the chains (hybrid plans: the long rows -- one slab + one solve each)
-        if (n_y > 0) {
-            int rc = plan_join_rhs(p, st);
-            if (rc != LK_OK) return rc;
-            if (p->ctl)
-                LK_SOLVE_LAUNCH(true, true, 0, n_y, yref);
+    // the rows that take their own right-hand side first (longest-first inside the launch) ...
+    // (hybrid / reference-order plans: these rows form y in the reference's order inside
+    // their Gram loop -- SEQY; the accurate mode keeps the four-slot sums)
+    const bool seqy = p->hybrid || p->ref_order;
+    if (n_solve > n_y) {
+        if (p->ctl) {
+            if (seqy)
+                LK_SOLVE_LAUNCH_S(true, false, true, n_y, n_solve - n_y, nullptr);
             else
-                LK_SOLVE_LAUNCH(false, true, 0, n_y, yref);
+                LK_SOLVE_LAUNCH(true, false, n_y, n_solve - n_y, nullptr);
+        } else {
+            if (seqy)
+                LK_SOLVE_LAUNCH_S(false, false, true, n_y, n_solve - n_y, nullptr);
+            else
+                LK_SOLVE_LAUNCH(false, false, n_y, n_solve - n_y, nullptr);
         }
+    }
+    // ... then the rows of the chains (hybrid plans: the long rows -- one slab + one solve each)
+    if (n_y > 0) {
+        int rc = plan_join_rhs(p, st);
+        if (rc != LK_OK) return rc;
+        if (p->ctl)
+            LK_SOLVE_LAUNCH(true, true, 0, n_y, yref);
+        else
+            LK_SOLVE_LAUNCH(false, true, 0, n_y, yref);
+    }
 #undef LK_SOLVE_LAUNCH
 #undef LK_SOLVE_LAUNCH_S
-    }
     if (tm) {
         LK_HIP_CHECK(hipEventRecord(p->ev[p->timing_n][2], st));
         p->timing_n++;
@@ -2217,9 +1786,8 @@ extern "C" int lk_als_plan_create_ex(lk_als_plan **out, const void *h_indptr, in
     // a chunk)
     const char *dma_off = getenv("LK_BLK_CHUNK_DMA");
     const bool units256 = KP == 256 && !(dma_off && dma_off[0] == '0');
-    // (padded k = 64: only the LDS-DMA Gram accumulation flushes a slab per 256-entry block; a
-    // -DLK_ALS_GRAM_DMA=0 build stores one slab per unit, so there a unit must be a chunk)
-    if (p->hybrid && ((KP == 64 && LK_ALS_GRAM_DMA) || units256)) {
+    // (padded k = 64: the LDS-DMA Gram accumulation flushes a slab per 256-entry block)
+    if (p->hybrid && (KP == 64 || units256)) {
         const char *e = getenv("LK_ALS_REF_UNIT");
         int u = e ? atoi(e) : LK_ALS_CHUNK;
         if (u < p->chunk) u = p->chunk;

@@ -92,27 +92,17 @@ __global__ __launch_bounds__(256) void als_wb_kernel(
     const float sv = __builtin_sqrtf(v);     // v < 0: NaN -> reported as not positive definite
 
     f32x4 mq[NQ], zq[NQ];
-#ifndef LK_WB_MASK_LOADS
-#define LK_WB_MASK_LOADS 0  // measured (cfg5, round 4): 1 = 247.0 ms/epoch, 0 = 238.4
-#endif
     {
         const f32x4 *mp = reinterpret_cast<const f32x4 *>(other + (int64_t)col * KP + s * QF);
         const f32x4 *zp = reinterpret_cast<const f32x4 *>(z + (int64_t)col * KP + s * QF);
         // Entry slots >= n carry zero weights and re-read the last entry's rows (L1 hits: 32 KiB
         // through the texture path per row whatever n).  Putting ONE branch around the batch of
-        // loads so that idle slots issue no request (LK_WB_MASK_LOADS=1) is SLOWER -- cfg5 247.0 vs
-        // 238.4 ms/epoch: the divergent region costs more than the redundant L1 hits.
+        // loads so that idle slots issue no request was measured SLOWER -- cfg5 247.0 vs 238.4
+        // ms/epoch: the divergent region costs more than the redundant L1 hits.
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            mq[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-            zq[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        if (!LK_WB_MASK_LOADS || c < n) {
+        for (int q = 0; q < NQ; ++q) mq[q] = mp[q];
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) mq[q] = mp[q];
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) zq[q] = zp[q];
-        }
+        for (int q = 0; q < NQ; ++q) zq[q] = zp[q];
     }
     // S0[i][j] = q_i . z_j : lane (s', c') register r = S0[4 s' + r][c']
     f32x4 S0 = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -331,12 +321,6 @@ __global__ __launch_bounds__(256) void als_wb4_kernel(
     }
     float b = lds[256 + (lane & 15)];
     float dinv = 0.f, mypiv = 1.0f;
-#ifdef LK_WB4_DEBUG
-    const float dbg_rhs = b;
-    float dbg_diag = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) dbg_diag = (lane == j) ? a[j] : dbg_diag;
-#endif
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
         const float piv = bcast(a[j], j);
@@ -372,21 +356,6 @@ __global__ __launch_bounds__(256) void als_wb4_kernel(
     }
     b *= dinv;  // u' of S u' = sv o r0, lane j < 16
     float g = w - sv * b;  // lanes 0..15 hold entry slot j = lane
-#ifdef LK_WB4_DEBUG
-    {  // dump of the wave's system into the x row of the wave's first task
-        float *dbg = this_ + (int64_t)__builtin_amdgcn_readfirstlane(row) * KP;
-        if (lane < 16) {
-            dbg[lane] = b;
-            dbg[16 + lane] = dbg_rhs;
-            dbg[32 + lane] = mypiv;
-            dbg[48 + lane] = sv;
-            dbg[64 + lane] = w;
-            dbg[80 + lane] = dinv;
-            dbg[96 + lane] = dbg_diag;
-        }
-        return;
-    }
-#endif
     g = __shfl(g, c, 64);
     // not positive definite / NaN: reported with the row of the slot's block
     {

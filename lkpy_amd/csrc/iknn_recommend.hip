@@ -84,11 +84,7 @@ __device__ __forceinline__ int cidx(int t) { return t + t / TPL; }
 // [5] score sweep, [6] copy-out, [7] tasks
 __device__ unsigned long long *lk_rec_phase_buf;
 #define LK_RP_T(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
-#ifdef LK_REC_WALKPH  // (the slots hold walk_acc's inner phases instead: a one-off diagnostic)
-#define LK_RP_ADD(i, a, b) (void)(a)
-#else
 #define LK_RP_ADD(i, a, b) ph[i] += (b) - (a)
-#endif
 #else
 #define LK_RP_T(var)
 #define LK_RP_ADD(i, a, b)
@@ -282,7 +278,7 @@ __device__ __forceinline__ void walk(unsigned *__restrict__ c, const int64_t *__
 // the hits of a TARGET in history order: stream order is history order, batches follow each other
 // in program order, and inside a batch two lanes that hit the same target take their cursor
 // values in LANE order -- the LDS resolves same-address atomics of one instruction in ascending
-// lane order on this hardware; `lds_atomic_order_probe_kernel` checks exactly that on the device
+// lane order on this hardware; `lds_add_order_probe_kernel` checks exactly that on the device
 // before the packed walk is ever used, and without it the walk above serves (LK_REC_PACKED=0
 // forces that).  Scores stay the reference accumulator's, bit for bit (tests/
 // test_gpu_iknn_recommend.py, the bench's recommend parity).
@@ -474,19 +470,8 @@ __device__ __forceinline__ DescCache walk_acc(
     const int32_t *__restrict__ s_idx, const float *__restrict__ s_val,
     const unsigned *__restrict__ woff, int nwin, int win, int64_t n_items,
     const int32_t *__restrict__ ref_items, const float *__restrict__ ref_rates, int64_t rb,
-    int64_t re, int *__restrict__ status, int lane, DescCache dc, bool mark_own
-#ifdef LK_REC_WALKPH
-    , unsigned long long *wph
-#endif
-    )
+    int64_t re, int *__restrict__ status, int lane, DescCache dc, bool mark_own)
 {
-#ifdef LK_REC_WALKPH
-#define WPH_T(v) unsigned long long v = 0; if (MODE == WALK_ADD_W) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)"); v = __builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt lgkmcnt(0)"); }
-#define WPH_ADD(i, a, b) if (MODE == WALK_ADD_W) wph[i] += (b) - (a)
-#else
-#define WPH_T(v)
-#define WPH_ADD(i, a, b)
-#endif
     static_assert(MODE != WALK_FILL, "the accumulating kernel keeps no lists");
     const int w0 = win * RW;
     // wave-private LDS: [0..127] (piece address - first position) of the rows with entries, by
@@ -495,7 +480,7 @@ __device__ __forceinline__ DescCache walk_acc(
     float *d_rt = reinterpret_cast<float *>(dsc + 128);
     unsigned *d_bm = dsc + 192;
     // `ds_add_f32` costs the LDS ~2.3 cycles per ACTIVE LANE (144 per full instruction; an integer
-    // atomic, a read or a write of 64 random cells: 6 ... 7 -- tools/probes/lds_atomic_rate.hip), so a
+    // atomic, a read or a write of 64 random cells: 6 ... 7 -- tools/probes/lds_add_rate.hip), so a
     // float walk adds with it only where it must: where two lanes of the instruction may hit the same
     // cell.  Every lane posts (batch number, lane) to a slot of a small tag table chosen by its target
     // (`ds_max_u32`) and reads the slot back: the lane that finds its own stamp is the HIGHEST lane
@@ -546,7 +531,6 @@ __device__ __forceinline__ DescCache walk_acc(
     }
     int k = 0;
     for (int64_t r0 = rb; r0 < re; r0 += 64, ++k) {
-        WPH_T(w0_);
         ChunkDesc nxt{0, 0, 0.f};
         int ri2 = -1;
         float rt2 = 0.f;
@@ -597,11 +581,8 @@ __device__ __forceinline__ DescCache walk_acc(
                 atomicOr(&d_bm[sx >> 5], 1u << (sx & 31u));  // ds_or_b32, no return
             }
             wave_lds_sync();
-            WPH_T(w1_);
-            WPH_ADD(0, w0_, w1_);
             unsigned before = 0u;  // ones at positions < the batch's start
             for (unsigned p0 = 0; p0 < sub_total; p0 += 64u * RDP) {
-                WPH_T(w2_);
                 int t_[RDP];
                 float s_[RDP], r_[RDP];
                 bool live_[RDP];
@@ -649,7 +630,6 @@ __device__ __forceinline__ DescCache walk_acc(
                     t_[d] = s_idx[e] - w0;
                     if (MODE != WALK_COUNT) s_[d] = s_val[e];
                 }
-                WPH_T(w3_);
 #pragma unroll
                 for (int d = 0; d < RDP; ++d) {
                     if (p0 + 64u * d >= sub_total) break;  // (wave-uniform)
@@ -679,12 +659,6 @@ __device__ __forceinline__ DescCache walk_acc(
                         }
                     }
                 }
-                WPH_T(w4_);
-                WPH_ADD(1, w2_, w3_);
-                WPH_ADD(2, w3_, w4_);
-#ifdef LK_REC_WALKPH
-                if (MODE == WALK_ADD_W) wph[4] += 1;
-#endif
             }
             done_pos = sub_end;
             j0 = j1;
@@ -692,22 +666,17 @@ __device__ __forceinline__ DescCache walk_acc(
         cur = nxt;
         ri1 = ri2;
         rt1 = rt2;
-#ifdef LK_REC_WALKPH
-        if (MODE == WALK_ADD_W) wph[3] += 1;
-#endif
     }
     if (MODE == WALK_ADD_W && __ballot(nan_seen) != 0ull) {
         if (lane == 0) atomicCAS(status, 0, 1);  // "similarity is null" (accum.rs:146-151)
     }
     return dc;
-#undef WPH_T
-#undef WPH_ADD
 }
 
 // Does the LDS hand out the old values of same-address `ds_add_rtn_u32`s of ONE instruction in
 // ascending lane order?  (What walk_packed's fill pass relies on.)  Several conflict patterns;
 // *ok = 0 as soon as a lane's old value differs from the number of lower lanes with its address.
-__global__ void lds_atomic_order_probe_kernel(int *__restrict__ ok)
+__global__ void lds_add_order_probe_kernel(int *__restrict__ ok)
 {
     __shared__ unsigned cell[64];
     const int lane = threadIdx.x;
@@ -1178,11 +1147,7 @@ void iknn_score_acc_kernel(
         // ---- walk 1: hits per target --------------------------------------------------------
         const DescCache dc = walk_acc<WALK_COUNT, EXPL, 1>(
             c, dsc, s_ptr, s_idx, s_val, woff, nwin, win, n_items, ref_items, ref_rates, rb, re,
-            status, lane, DescCache{0, 0, 0, 0, 0, 0, 0, 0, 0.f, 0.f, 0.f, 0.f}, exclude_refs != 0
-#ifdef LK_REC_WALKPH
-            , ph
-#endif
-            );
+            status, lane, DescCache{0, 0, 0, 0, 0, 0, 0, 0, 0.f, 0.f, 0.f, 0.f}, exclude_refs != 0);
         wave_lds_sync();
         LK_RP_T(p3);
 
@@ -1242,11 +1207,7 @@ void iknn_score_acc_kernel(
 
         // ---- walk 2: total weights, in history order by construction ------------------------------
         (void)walk_acc<WALK_ADD_W, EXPL, 2>(c, dsc, s_ptr, s_idx, s_val, woff, nwin, win, n_items,
-                                            ref_items, ref_rates, rb, re, status, lane, dc, false
-#ifdef LK_REC_WALKPH
-                                            , ph
-#endif
-                                            );
+                                            ref_items, ref_rates, rb, re, status, lane, dc, false);
         wave_lds_sync();
         LK_RP_T(p5);
         float4 tw[NG];
@@ -1263,11 +1224,7 @@ void iknn_score_acc_kernel(
             // ---- walk 3: weighted sums ------------------------------------------------------------
             (void)walk_acc<WALK_ADD_WV, EXPL, 2>(c, dsc, s_ptr, s_idx, s_val, woff, nwin, win,
                                                  n_items, ref_items, ref_rates, rb, re, status, lane,
-                                                 dc, false
-#ifdef LK_REC_WALKPH
-                                                 , ph
-#endif
-                                                 );
+                                                 dc, false);
             wave_lds_sync();
         }
         LK_RP_T(p6);
@@ -1844,7 +1801,7 @@ extern "C" int lk_iknn_recommend(const int64_t *d_sim_indptr, const int32_t *d_s
             if (!done) {
                 int one = 1, got = 0;
                 LK_HIP_CHECK(hipMemcpyAsync(status + 3, &one, sizeof(int), hipMemcpyHostToDevice, st));
-                hipLaunchKernelGGL(lds_atomic_order_probe_kernel, dim3(1), dim3(64), 0, st, status + 3);
+                hipLaunchKernelGGL(lds_add_order_probe_kernel, dim3(1), dim3(64), 0, st, status + 3);
                 LK_HIP_CHECK(hipMemcpyAsync(&got, status + 3, sizeof(int), hipMemcpyDeviceToHost, st));
                 LK_HIP_CHECK(hipStreamSynchronize(st));
                 good = got == 1;

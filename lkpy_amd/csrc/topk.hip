@@ -413,10 +413,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void s
 }
 #undef LK_SCORE_ARGS
 
-#ifndef LK_TOPK_DMA
-#define LK_TOPK_DMA 2  // operands by global_load_lds: 1 = k 64 only (score_filter64_kernel), 2 = also
-                       // k 32 / 128 / 256 (score_filter_slab_kernel); 0: never (register-staged)
-#endif
 // ---- the fused filter for 64 features: operands straight into LDS ------------------------------
 //
 // Same tile (128 users x 256 items per workgroup, 64 x 128 per wave, 128 accumulators), same
@@ -646,8 +642,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void s
         if (u0 + rr < n_users) cand_cnt[(u0 + rr) * t_step + t_lo] = s_cnt[rr];
 }
 
-#if LK_TOPK_DMA >= 2
-// ---- the same DMA staging for the other feature counts (LK_TOPK_DMA >= 2, the default) ----------
+// ---- the same DMA staging for the other feature counts --------------------------------------------
 // Round 3, first run on a GPU (tools/topk_variants.py, 162 541 x 62 423, n = 100, list checksums
 // over all rows identical to the register-staged kernel): k = 32: 9.11 -> 9.00 ms, k = 128:
 // 25.08 -> 24.44 ms (106 TF), k = 256: 46.23 -> 45.02 ms (115 TF = 0.73 of the MFMA peak).
@@ -822,7 +817,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void s
     for (int rr = tid; rr < UB; rr += 256)
         if (u0 + rr < n_users) cand_cnt[(u0 + rr) * t_step + t_lo] = s_cnt[rr];
 }
-#endif  // LK_TOPK_DMA >= 2
 
 
 
@@ -2035,12 +2029,6 @@ __global__ __launch_bounds__(256) void cand_merge_kernel(
     if (lane == 0) cnt[b] = total;
 }
 
-static bool tau_mask()
-{
-    const char *e = getenv("LK_TOPK_TAU_MASK");  // A/B knob (read per call)
-    return !(e && e[0] == '0');
-}
-
 // LK_TOPK_STAGE1=panel: the round-4 stage 1 (sample panel written, sample_tau_kernel sweeps it);
 // default: class maxima from the sample GEMM's epilogue (sample_cmax_kernel + cmax_tau_kernel)
 static bool stage1_cmax()
@@ -2170,7 +2158,6 @@ constexpr int FUSED_BIG_CAP = 32768;  // rows per batch the second tier takes (m
 struct FusedLayout {
     size_t off_sub, off_tau, off_cnt, off_cand, off_flags, off_qs, off_parts, off_pcnt, bytes;
     int parts, part_cap;  // item-split launches of a small batch (parts <= 1: none)
-    int tail_parts;       // ... of the partial last round of a large batch
 };
 // candidates per (row, part) sub-list: twice a row's whole list divided by the parts (the tiles are
 // interleaved, so a part holds ~1/S of a row's candidates; a part that overflows sends the row to
@@ -2189,32 +2176,12 @@ static int filter_parts(int64_t rows, int64_t n_items, int kp)
 {
     const int64_t wgs = (rows + 2 * SC_UB - 1) / (2 * SC_UB);
     const int64_t n_itiles = (n_items + SC_IB - 1) / SC_IB;
-    const bool dma_kernel = (LK_TOPK_DMA && kp == 64) ||
-                            (LK_TOPK_DMA >= 2 && (kp == 32 || kp == 128 || kp == 256));
+    const bool dma_kernel = kp == 32 || kp == 64 || kp == 128 || kp == 256;
     if (!dma_kernel || !topk_split() || wgs >= 2 * 256 || n_itiles < 8) return 1;
     int64_t parts = (2 * 256) / wgs;
     if (parts > n_itiles / 4) parts = n_itiles / 4;
     if (parts > 64) parts = 64;  // (cand_merge_kernel: a lane per part)
     return parts < 2 ? 1 : (int)parts;
-}
-
-// rows of the partial LAST round of a batch of several rounds of filter workgroups (0: the batch
-// is whole rounds, or a single round)
-static int64_t tail_rows(int64_t rows)
-{
-    const int64_t wgs = (rows + 2 * SC_UB - 1) / (2 * SC_UB), round = 2 * 256;
-    if (!topk_overlap() || wgs <= round || wgs % round == 0) return 0;
-    return rows - (wgs / round) * round * (2 * SC_UB);
-}
-// LK_TOPK_SPLIT_TAIL=1 (default 0): the partial last round of a large batch is item-split as a
-// small batch is (its workgroups otherwise sit one per CU).  Measured twice on the cfg2 call (1270
-// workgroups = two rounds + 246): 13.1 against 12.3 ms with global counters, 12.1 against 11.9 ms
-// with per-part sub-lists -- the lone workgroups of the last round run at 0.55 of a paired one's
-// time, which splitting them does not beat.  Kept as a knob, off.
-static bool topk_split_tail()
-{
-    const char *e = getenv("LK_TOPK_SPLIT_TAIL");
-    return e && e[0] == '1';
 }
 
 // stage 1 as class maxima (sample_cmax_kernel + cmax_tau_kernel): unless switched off, and as long
@@ -2251,21 +2218,11 @@ static FusedLayout fused_layout(int64_t n_users, int64_t n_items, int32_t n, int
     L.parts = filter_parts(rows, n_items, kp);
     L.part_cap = filter_part_cap(L.parts);
     L.off_parts = L.off_pcnt = off;
-    int maxp = filter_parts(rows, n_items, 64);
-    int64_t sub_rows = rows;
-    // ... or the partial last round of a batch of several rounds (its rows only)
-    L.tail_parts = 1;
-    const int64_t tr = tail_rows(rows);
-    if (maxp <= 1 && tr > 0 && topk_split_tail()) {
-        L.tail_parts = filter_parts(tr, n_items, kp);
-        maxp = filter_parts(tr, n_items, 64);
-        sub_rows = tr;
-        L.part_cap = filter_part_cap(L.tail_parts);
-    }
+    const int maxp = filter_parts(rows, n_items, 64);
     if (maxp > 1) {
-        off += align_up((size_t)sub_rows * maxp * filter_part_cap(maxp) * 8, 256);
+        off += align_up((size_t)rows * maxp * filter_part_cap(maxp) * 8, 256);
         L.off_pcnt = off;
-        off += align_up((size_t)sub_rows * maxp * 4, 256);
+        off += align_up((size_t)rows * maxp * 4, 256);
     }
     L.bytes = off;
     return L;
@@ -2469,16 +2426,12 @@ extern "C" int lk_score_topk(const float *d_users, int32_t ld_users, int64_t n_u
                                        (const float *)nullptr, (unsigned long long *)nullptr,
                                        (unsigned *)nullptr, 0);
                     // LK_TOPK_TAU_EXACT=1 (r = n, a certain bound): every dirty class is repaired --
-                    // a row must keep n classes.  LK_TOPK_DROP_MAX: A/B knob.
+                    // a row must keep n classes.
                     lk::TauRanks ranks;
                     for (int d = 0; d <= lk::CMAX_RANKS - 1; ++d)
                         ranks.r[d] =
                             (unsigned char)lk::fused_tau_rank(n_items, n, (256 - d) / 256.0);
-                    int drop_max = lk::tau_exact() ? 0 : lk::CMAX_DROP_MAX;
-                    if (const char *e = getenv("LK_TOPK_DROP_MAX")) {
-                        const int v = atoi(e);
-                        if (v >= 0 && v < drop_max) drop_max = v;
-                    }
+                    const int drop_max = lk::tau_exact() ? 0 : lk::CMAX_DROP_MAX;
                     const int repair_max = lk::tau_exact() ? 256 : lk::CMAX_REPAIR_MAX;
                     hipLaunchKernelGGL(lk::cmax_tau_kernel, dim3((unsigned)((nr + 3) / 4)),
                                        dim3(256), cmax_lds, s, cm, uu, ld_users, qs, KP, n_sub, ranks,
@@ -2493,9 +2446,9 @@ extern "C" int lk_score_topk(const float *d_users, int32_t ld_users, int64_t n_u
                                    nr, qs, KP, n_sub, KP, sp, ld_sub, (const float *)nullptr,
                                    (unsigned long long *)nullptr, (unsigned *)nullptr, 0);
                 // exclusions are struck out of the sample inside sample_tau_kernel (per-wave LDS
-                // bitmap) when 4 bitmaps fit 64 KiB of LDS; LK_TOPK_TAU_MASK=0 or a huge sample:
-                // the separate score_mask_kernel pass over the panel
-                const bool tau_mask = d_excl_ptr && lk::tau_mask() && (size_t)words * 16 <= 65536;
+                // bitmap) when 4 bitmaps fit 64 KiB of LDS; a huge sample: the separate
+                // score_mask_kernel pass over the panel
+                const bool tau_mask = d_excl_ptr && (size_t)words * 16 <= 65536;
                 if (d_excl_ptr && !tau_mask)
                     hipLaunchKernelGGL(lk::score_mask_kernel, dim3((unsigned)nr), dim3(64), 0, s,
                                        d_excl_ptr, d_excl_items, ub + r0, nr, n_items, sp, ld_sub,
@@ -2527,8 +2480,6 @@ extern "C" int lk_score_topk(const float *d_users, int32_t ld_users, int64_t n_u
             // (measured on the 1270-workgroup cfg2 call: splitting its partial last round of 246
             // in two made the call slower, 13.1 against 12.3 ms)
             const int parts = batches == 1 ? L.parts : 1;
-            // (LK_TOPK_SPLIT_TAIL=1: the partial last round split as well -- measured slower, off)
-            const int tail_parts = batches == 1 ? L.tail_parts : 1;
             auto filter = [&](int64_t r0, int64_t nr, hipStream_t s, int parts = 1) {
                 dim3 ugrid((unsigned)((nr + 2 * lk::SC_UB - 1) / (2 * lk::SC_UB)));
                 const float *uu = ub_users + r0 * ld_users;
@@ -2545,11 +2496,10 @@ extern "C" int lk_score_topk(const float *d_users, int32_t ld_users, int64_t n_u
                     cand_r = pcand;
                     cnt_r = pcnt;
                 }
-                if (LK_TOPK_DMA && KP == 64)
+                if (KP == 64)
                     hipLaunchKernelGGL(lk::score_filter64_kernel, ugrid, dim3(256), 0, s, uu, nr,
                                        d_items, n_items, tau_r, cand_r, cnt_r, cap_arg,
                                        tiles_per_wg);
-#if LK_TOPK_DMA >= 2
                 else if (KP == 32)
                     hipLaunchKernelGGL(lk::score_filter_slab_kernel<32>, ugrid, dim3(256), 0, s, uu,
                                        nr, d_items, n_items, tau_r, cand_r, cnt_r, cap_arg,
@@ -2562,7 +2512,6 @@ extern "C" int lk_score_topk(const float *d_users, int32_t ld_users, int64_t n_u
                     hipLaunchKernelGGL(lk::score_filter_slab_kernel<256>, ugrid, dim3(256), 0, s, uu,
                                        nr, d_items, n_items, tau_r, cand_r, cnt_r, cap_arg,
                                        tiles_per_wg);
-#endif
                 else
                     hipLaunchKernelGGL(lk::score_filter_kernel, ugrid, dim3(256), 0, s, uu, ld_users,
                                        nr, d_items, ld_items, n_items, KP, (float *)nullptr,
@@ -2622,7 +2571,7 @@ extern "C" int lk_score_topk(const float *d_users, int32_t ld_users, int64_t n_u
                 filter(0, rows_a, st);
                 LK_HIP_CHECK(hipEventRecord(sd.fork, st));  // range A filtered
                 LK_HIP_CHECK(hipStreamWaitEvent(sd.stream, sd.fork, 0));
-                filter(rows_a, rows - rows_a, st, tail_parts);
+                filter(rows_a, rows - rows_a, st);
                 // both tiers of range A's selection beside the partial round
                 select(0, rows_a, sd.stream, big);
                 tier2(rows_a, sd.stream, big);

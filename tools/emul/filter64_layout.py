@@ -25,7 +25,7 @@ def place_users(U):
 def place_slab(I, s):
     """
     I: [rows, KP], features 16 s .. 16 s + 15 -> LDS image [rows * 16]; instruction n moves rows
-    16 n ..  (256 item rows; also the 128 user rows of score_filter_slab_kernel, -DLK_TOPK_DMA=2)
+    16 n ..  (256 item rows; also the 128 user rows of score_filter_slab_kernel)
     """
     lds = np.full(I.shape[0] * 16, -1, dtype=I.dtype)
     for n in range(I.shape[0] // 16):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """
-Lane-level NumPy model of the hybrid Cholesky of als_chol.hip (LK_ALS_PANEL=2): panels of four
+Lane-level NumPy model of the hybrid Cholesky of als_chol.hip: panels of four
 columns are factored in the lane = row layout (registers + v_readlane only), turned into MFMA
 operands by a 4 x 4 (register x row-group) transposition made of v_permlane32_swap /
 v_permlane16_swap, and the trailing update is one v_mfma_f32_16x16x4_f32 per tile.

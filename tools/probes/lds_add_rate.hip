@@ -3,7 +3,7 @@
 // back-to-back LDS operations on its own 4096 cells; reports CU cycles per wave instruction for
 //   ds_add_f32 / ds_add_u32 / ds_write_b32 / ds_read_b32  x  (distinct consecutive cells, random
 //   cells, 8 lanes per cell).
-//   hipcc --offload-arch=gfx950 -O3 -o lds_atomic_rate lds_atomic_rate.hip && ./lds_atomic_rate
+//   hipcc --offload-arch=gfx950 -O3 -o lds_add_rate lds_add_rate.hip && ./lds_add_rate
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
