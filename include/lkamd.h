@@ -490,6 +490,43 @@ int lk_iknn_score_batch(const int64_t *d_sim_indptr, const int32_t *d_sim_indice
                         void *d_ws, float *d_out_scores, int32_t *d_out_counts, void *stream);
 
 /* ------------------------------------------------------------------------
+ * The rating-predictor tail of std:topn-predict for a BATCH of queries (csrc/predict_merge.hip);
+ * `batch.predict` calls it after lk_iknn_score_batch so that no score, count or flag goes back
+ * to the host one query at a time.  Both calls are asynchronous on `stream`.
+ *
+ * lk_bias_user_offsets replaces, for a whole batch, the user bias that
+ * `BiasModel.compute_for_items` takes from the query's training ratings
+ * (src/lenskit/basic/bias.py:166-240): query q's history is row d_user_nums[q] of the training
+ * matrix (offsets i32/i64, item numbers, ratings f32; -1 or out of range: no training row);
+ *   uoff_j = (double)r_j - global_bias [- (double)d_item_biases[item_j]]  (d_item_biases NULL:
+ *   no item term), ub = sum_j uoff_j / ((double)count of finite uoff_j + damping_user), a NaN
+ *   ub becomes 0, rounded to float32 at the end.  The sum is NumPy's `np.sum` of a contiguous
+ *   float64 array, its pairwise order included (blocks of 8192 in sequence, 8-accumulator leaves
+ *   of <= 128 elements), so ub is the host's bit for bit.  d_out_ub [n_queries] = ub (0 without
+ *   a row); d_out_add [n_queries] = 1 where the query has a training row (the host adds ub only
+ *   then: -0.0 + 0.0 is +0.0), 0 elsewhere.  One wave per query.
+ *
+ * lk_predict_merge replaces the item-mean add-back of `ItemKNNScorer.__call__`
+ * (src/lenskit/knn/item.py:282) and `FallbackScorer` (src/lenskit/basic/composite.py) over a
+ * `BiasScorer`: for every entry e of query q (d_tgt_ptr [n_queries + 1] int64 offsets into
+ * d_tgt_items / d_scores, n_entries = d_tgt_ptr[n_queries]; negative or >= n_items targets are
+ * unknown items) in float32:  s = d_scores[e] (+ d_item_means[t] when not NULL and t is known);
+ * with `fallback` != 0, a NaN s becomes (float)global_bias (+ d_item_biases[t] when not NULL
+ * and t is known) (+ d_user_bias[q] where d_user_add[q] != 0; d_user_add NULL: never) and
+ * d_out_is_fallback[e] = 1 (0 elsewhere; the flags may be NULL).  d_scores is updated in place.
+ * ---------------------------------------------------------------------- */
+int lk_bias_user_offsets(const void *d_indptr, int indptr_is_64, const int32_t *d_indices,
+                         const float *d_values, int64_t n_users, int64_t n_items,
+                         int64_t n_queries, const int32_t *d_user_nums, double global_bias,
+                         const float *d_item_biases, double damping_user, float *d_out_ub,
+                         uint8_t *d_out_add, void *stream);
+int lk_predict_merge(int64_t n_queries, const int64_t *d_tgt_ptr, const int32_t *d_tgt_items,
+                     int64_t n_entries, int64_t n_items, float *d_scores,
+                     const float *d_item_means, int fallback, double global_bias,
+                     const float *d_item_biases, const float *d_user_bias,
+                     const uint8_t *d_user_add, uint8_t *d_out_is_fallback, void *stream);
+
+/* ------------------------------------------------------------------------
  * User-kNN scoring for a BATCH of queries.
  * Replaces `_accel.knn.user_score_items_explicit / _implicit(tgt_items, nbr_rows, nbr_sims,
  * ratings, max_nbrs, min_nbrs)` (src/accel/knn/user_score.rs:21-98): query q has neighbours

@@ -782,6 +782,62 @@ def iknn_score_batch(sims: DeviceCSR, ref_ptr, ref_items, ref_rates, tgt_ptr, tg
     return out_s, out_c
 
 
+def bias_user_offsets(hist: DeviceCSR, user_nums: torch.Tensor, global_bias: float,
+                      item_biases: torch.Tensor | None, damping_user: float):
+    """
+    User biases of a batch of queries from their training ratings (lk_bias_user_offsets):
+    ``BiasModel.compute_for_items`` with the query's history (src/lenskit/basic/bias.py:166-240)
+    for every query at once, bit for bit.  ``hist``: the training matrix in HBM (users x items,
+    f32 ratings); ``user_nums``: device int32 [B], -1 = no training row; ``item_biases``: device
+    f32 [n_items] or None.  Returns device (ub f32 [B], add uint8 [B]: 1 where the host would add
+    ub, i.e. the query has a training row).
+    """
+    lib = _native.require_gpu()
+    dev = hist.indices.device
+    B = int(user_nums.shape[0])
+    ub = torch.empty(B, dtype=torch.float32, device=dev)
+    add = torch.empty(B, dtype=torch.uint8, device=dev)
+    assert user_nums.dtype == torch.int32 and hist.values is not None
+    check(
+        lib.lk_bias_user_offsets(
+            _ptr(hist.indptr), 1 if hist.is64 else 0, _ptr(hist.indices), _ptr(hist.values),
+            hist.shape[0], hist.shape[1], B, _ptr(user_nums), float(global_bias),
+            _ptr(item_biases), float(damping_user), _ptr(ub), _ptr(add), _stream()
+        ),
+        "lk_bias_user_offsets",
+    )  # fmt: skip
+    return ub, add
+
+
+def predict_merge(tgt_ptr: torch.Tensor, tgt_items: torch.Tensor, n_items: int,
+                  scores: torch.Tensor, item_means: torch.Tensor | None, *,
+                  fallback: bool = False, global_bias: float = 0.0,
+                  item_biases: torch.Tensor | None = None, user_bias: torch.Tensor | None = None,
+                  user_add: torch.Tensor | None = None, out_is_fallback: torch.Tensor | None = None):
+    """
+    The rating-predictor tail for a batch (lk_predict_merge), in place on ``scores`` (the
+    :func:`iknn_score_batch` output over ``tgt_ptr`` / ``tgt_items``): the item means added back
+    (item.py:282), and with ``fallback`` the NaN scores replaced by the ``BiasScorer`` score
+    mu + b_i (+ ``user_bias`` where ``user_add``) as ``FallbackScorer`` does
+    (basic/composite.py).  ``out_is_fallback``: device uint8 [entries] or None.
+    """
+    lib = _native.require_gpu()
+    n = int(tgt_items.shape[0])
+    assert scores.dtype == torch.float32 and int(scores.shape[0]) == n
+    assert tgt_ptr.dtype == torch.int64 and tgt_items.dtype == torch.int32
+    assert out_is_fallback is None or (out_is_fallback.dtype == torch.uint8
+                                       and int(out_is_fallback.shape[0]) >= n)
+    check(
+        lib.lk_predict_merge(
+            int(tgt_ptr.shape[0]) - 1, _ptr(tgt_ptr), _ptr(tgt_items), n, int(n_items),
+            _ptr(scores), _ptr(item_means), 1 if fallback else 0, float(global_bias),
+            _ptr(item_biases), _ptr(user_bias), _ptr(user_add), _ptr(out_is_fallback), _stream()
+        ),
+        "lk_predict_merge",
+    )  # fmt: skip
+    return scores
+
+
 def iknn_recommend(sims: DeviceCSR, ref_ptr, ref_items, ref_rates, item_bias, max_nbrs: int,
                    min_nbrs: int, n: int, query_hits: np.ndarray, exclude_refs: bool = True):
     """

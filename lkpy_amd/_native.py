@@ -126,6 +126,16 @@ def _declare(lib):
             c_int,
             [vp, vp, vp, c_int64, c_int64, vp, vp, vp, vp, vp, c_int32, c_int32, vp, vp, vp, vp],
         ),
+        "lk_bias_user_offsets": (
+            c_int,
+            [vp, c_int, vp, vp, c_int64, c_int64, c_int64, vp, ctypes.c_double, vp,
+             ctypes.c_double, vp, vp, vp],
+        ),
+        "lk_predict_merge": (
+            c_int,
+            [c_int64, vp, vp, c_int64, c_int64, vp, vp, c_int, ctypes.c_double, vp, vp, vp, vp,
+             vp],
+        ),
         "lk_uknn_score_batch": (
             c_int,
             [vp, vp, vp, c_int64, c_int64, c_int64, vp, vp, vp, vp, vp, c_int32, c_int32, vp, vp,

@@ -307,6 +307,53 @@ class BiasScorer(Component):
         scores, _ = self.model.compute_for_items(items, query.user_id, query.history_items)
         return ItemList(items, scores=scores)
 
+    # -- whole batches of queries (batch.predict) ---------------------------------------------
+    def __getstate__(self):
+        st = dict(self.__dict__)
+        st.pop("_dev", None)
+        return st
+
+    def _device_model(self):
+        "The item biases in HBM (f32; None without an item term), uploaded once, never pickled."
+        st = self.__dict__.get("_dev")
+        if st is None or st["model"] is not self.model:
+            import torch
+
+            from . import _device as D
+
+            ib = self.model.item_biases
+            st = {"model": self.model,
+                  "item_biases": None if ib is None else torch.from_numpy(
+                      np.ascontiguousarray(ib, dtype=np.float32)).to(D.device())}
+            self._dev = st
+        return st
+
+    def user_offsets_batch(self, batch: "HistoryBatch"):
+        """
+        The user-bias part of ``__call__`` for a whole :class:`HistoryBatch`: what
+        ``BiasModel.compute_for_items`` computes from each query's training ratings
+        (src/lenskit/basic/bias.py:166-240), by one ``lk_bias_user_offsets`` call that reads the
+        rows straight from the lookup's HBM-resident training matrix.  Returns device
+        (ub f32 [B], add uint8 [B]): ``add`` is 1 where the host path adds ub to the scores (the
+        model has user biases and the query has a training row).
+        """
+        import torch
+
+        from . import _device as D
+
+        st = self._device_model()
+        mat = batch.lookup._device_matrix()
+        dev = mat["device"]
+        B = len(batch)
+        if self.model.users is None:  # no user term: nothing is added
+            return (torch.zeros(B, dtype=torch.float32, device=dev),
+                    torch.zeros(B, dtype=torch.uint8, device=dev))
+        if not mat["has_ratings"]:
+            raise ValueError("user biases from the history need ratings")
+        nums = torch.from_numpy(np.ascontiguousarray(batch.user_nums, dtype=np.int32)).to(dev)
+        return D.bias_user_offsets(mat["csr"], nums, self.model.global_bias,
+                                   st["item_biases"], _damping(self.model.damping, "user"))
+
 
 class FallbackScorer(Component):
     "Primary scores, back-filled from the backup where missing (basic/composite.py)."

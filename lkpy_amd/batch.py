@@ -8,6 +8,7 @@ rank 1): the reference's ``batch.recommend`` / ``batch.predict`` loop queries in
 from __future__ import annotations
 
 import numpy as np
+import pandas as pd
 
 from .data import ItemList, ItemListCollection, RecQuery
 from .pipeline import Pipeline
@@ -54,9 +55,185 @@ def recommend(pipe: Pipeline, users, n: int, *, batch_size: int = 16384) -> Item
     return ItemListCollection.from_dict(out, key=("user_id",))
 
 
-def predict(pipe: Pipeline, pairs: dict) -> ItemListCollection:
-    """Scores for each user's items (``rating-predictor`` semantics) as an ``ItemListCollection``
-    keyed by ``user_id`` (``BatchResults.output("predictions")``)."""
+def predict(pipe: Pipeline, pairs, *, batch_size: int = 16384) -> ItemListCollection:
+    """
+    Scores for each user's items (``rating-predictor`` semantics) as an ``ItemListCollection``
+    keyed by ``user_id`` (``BatchResults.output("predictions")``).  ``pairs``: a dict of user ->
+    ``ItemList`` (or item-id array), an ``ItemListCollection`` keyed by ``user_id`` (the
+    reference's ``predict(pipeline, test)``), or a ``DataFrame`` with ``user_id`` and ``item_id``
+    columns (users in order of first appearance, rows in order within a user; the other columns
+    become fields of the lists).
+
+    An item-kNN pipeline (``std:topn-predict`` with its ``BiasScorer`` fallback, or without a
+    fallback) whose vocabularies agree is run as whole batches by user number
+    (:func:`_predict_batched`): the lists are the per-query composition's bit for bit.  Every
+    other pipeline runs query by query.
+    """
+    keys, offsets, item_ids, fields, lists = _ragged_pairs(pairs)
+    parts = _batched_predict_parts(pipe)
+    if parts is not None and fields is not None and not (
+            set(fields) & {"score", "nbr_counts", "is_fallback"}):
+        return _predict_batched(parts, keys, offsets, item_ids, fields, batch_size)
+    if isinstance(pairs, dict):
+        return _predict_loop(pipe, pairs)
+    if lists is None:
+        lists = [ItemList(item_ids=item_ids[offsets[i]:offsets[i + 1]],
+                          **{f: v[offsets[i]:offsets[i + 1]] for f, v in fields.items()})
+                 for i in range(len(keys))]
+    return _predict_loop(pipe, dict(zip(_key_list(keys), lists)))
+
+
+def _key_list(keys) -> list:
+    return [k.item() if isinstance(k, np.generic) else k for k in keys]
+
+
+def _ragged_pairs(pairs):
+    """
+    The query lists of a ``predict`` input as ragged arrays: (user keys, int64 offsets, the
+    concatenated item ids, {field: concatenated values} -- None when the lists do not all carry
+    the same fields --, the ``ItemList`` objects or None for a frame).
+    """
+    if isinstance(pairs, pd.DataFrame):
+        codes, uniq = pd.factorize(pairs["user_id"], sort=False)  # order of first appearance
+        order = np.argsort(codes, kind="stable")
+        counts = np.bincount(codes[codes >= 0], minlength=len(uniq))
+        offsets = np.zeros(len(uniq) + 1, np.int64)
+        np.cumsum(counts, out=offsets[1:])
+        order = order[len(order) - int(offsets[-1]):]  # (rows without a user id dropped)
+        item_ids = pairs["item_id"].to_numpy()[order]
+        fields = {c: pairs[c].to_numpy()[order] for c in pairs.columns
+                  if c not in ("user_id", "item_id")}
+        return np.asarray(uniq), offsets, item_ids, fields, None
+    if isinstance(pairs, ItemListCollection):
+        keys, lists = [], []
+        for k, il in pairs:
+            keys.append(getattr(k, "user_id") if "user_id" in k._fields else k[0])
+            lists.append(il)
+    else:
+        keys = list(pairs)
+        lists = [pairs[u] if isinstance(pairs[u], ItemList) else ItemList(np.asarray(pairs[u]))
+                 for u in keys]
+    offsets = np.zeros(len(lists) + 1, np.int64)
+    np.cumsum([len(il) for il in lists], out=offsets[1:])
+    ids = [il.ids() for il in lists]
+    item_ids = np.concatenate(ids) if ids else np.zeros(0, np.int64)
+    names = {tuple(il._fields) for il in lists}
+    fields = None
+    if len(names) <= 1:
+        fields = {f: np.concatenate([il._fields[f] for il in lists]) for f in
+                  (names.pop() if names else ())}
+    return keys, offsets, item_ids, fields, lists
+
+
+def _batched_predict_parts(pipe: Pipeline):
+    """(scorer, lookup, BiasScorer or None) when ``rating-predictor`` can run by user number:
+    an ``ItemKNNScorer``, a lookup with ``batch``, no merger or a ``FallbackScorer`` over a
+    ``BiasScorer``, and one item (and user) vocabulary throughout; None otherwise."""
+    from .basic import BiasScorer, FallbackScorer
+    from .knn import ItemKNNScorer
+
+    scorer = pipe.node("scorer").component
+    lookup = pipe.node("history-lookup").component
+    if not isinstance(scorer, ItemKNNScorer) or not hasattr(lookup, "batch") or \
+            not scorer.is_trained() or getattr(lookup, "interactions", None) is None:
+        return None
+    ds = lookup.interactions._ds
+    same = lambda a, b: a is b or a == b  # noqa: E731
+    if not same(scorer.items, ds.items):
+        return None
+    rating = ds._attrs.get("rating")
+    if scorer.config.explicit and rating is None:
+        return None  # (the per-query path raises)
+    bias = None
+    merger = pipe.nodes.get("rating-merger")
+    if merger is not None:
+        fb = pipe.nodes.get("fallback-predictor")
+        if not isinstance(merger.component, FallbackScorer) or fb is None or \
+                not isinstance(fb.component, BiasScorer) or not fb.component.is_trained():
+            return None
+        bias = fb.component
+        model = bias.model
+        if model.items is not None and not same(model.items, ds.items):
+            return None
+        if model.users is not None and (not same(model.users, ds.users) or rating is None or
+                                        rating.dtype != np.float32):
+            return None  # (the host sums the history's own ratings: float32 in HBM)
+    return scorer, lookup, bias
+
+
+def _predict_batched(parts, keys, offsets, item_ids, fields, batch_size: int):
+    """
+    ``rating-predictor`` for whole batches by user number: one vectorised vocabulary lookup of
+    every target, and per batch the histories cut out of the HBM-resident training matrix,
+    one ``lk_iknn_score_batch`` call (``ItemKNNScorer.score_history_batch``), the user biases of
+    the ``BiasScorer`` fallback (``lk_bias_user_offsets``), the item means and the fallback merge
+    (``lk_predict_merge``) and one download of scores, counts and flags.  The lists carry the
+    caller's item ids and fields; a query without history has no ``nbr_counts``
+    (item.py:238-245), ``is_fallback`` exists with a fallback only.
+    """
+    import torch
+
+    from . import _device as D
+
+    scorer, lookup, bias = parts
+    B = len(keys)
+    if B == 0:
+        return ItemListCollection(("user_id",))
+    key_arr = keys if isinstance(keys, np.ndarray) else np.asarray(_key_list(keys))
+    n_items = len(scorer.items)
+    nums = scorer.items.numbers(item_ids, missing="negative") if len(item_ids) else \
+        np.zeros(0, np.int32)
+    total = int(offsets[-1])
+    scores = np.empty(total, np.float32)
+    counts = np.empty(total, np.int32)
+    fb = np.empty(total, np.bool_) if bias is not None else None
+    nohist = np.empty(B, np.bool_)
+    d = scorer._device_sims()["device"]
+    means = scorer._device_means()
+    item_biases = bias._device_model()["item_biases"] if bias is not None else None
+    for s0 in range(0, B, batch_size):
+        s1 = min(B, s0 + batch_size)
+        nb = s1 - s0
+        lo, hi = int(offsets[s0]), int(offsets[s1])
+        n = hi - lo
+        hb = lookup.batch(key_arr[s0:s1])
+        nohist[s0:s1] = hb.lengths == 0
+        if n == 0:
+            continue  # (empty target lists only: nothing to score)
+        # one upload: target offsets (int64) and item numbers (int32)
+        packed = np.empty(2 * (nb + 1) + n + (n & 1), np.int32)
+        packed[:2 * (nb + 1)] = (offsets[s0:s1 + 1] - lo).view(np.int32)
+        packed[2 * (nb + 1):2 * (nb + 1) + n] = nums[lo:hi]
+        d_packed = torch.from_numpy(packed).to(d)
+        d_ptr = d_packed[:2 * (nb + 1)].view(torch.int64)
+        d_nums = d_packed[2 * (nb + 1):2 * (nb + 1) + n]
+        s_dev, c_dev = scorer.score_history_batch(hb, d_ptr, d_nums)
+        out = torch.empty(9 * n, dtype=torch.uint8, device=d)  # scores | counts | flags
+        if bias is not None:
+            ub, add = bias.user_offsets_batch(hb)
+            D.predict_merge(d_ptr, d_nums, n_items, s_dev, means, fallback=True,
+                            global_bias=bias.model.global_bias, item_biases=item_biases,
+                            user_bias=ub, user_add=add, out_is_fallback=out[8 * n:])
+        else:
+            D.predict_merge(d_ptr, d_nums, n_items, s_dev, means)
+        out[:4 * n] = s_dev.view(torch.uint8)
+        out[4 * n:8 * n] = c_dev.view(torch.uint8)
+        host = out.cpu().numpy()
+        scores[lo:hi] = host[:4 * n].view(np.float32)
+        counts[lo:hi] = host[4 * n:8 * n].view(np.int32)
+        if fb is not None:
+            fb[lo:hi] = host[8 * n:].view(np.bool_)
+    out_fields = dict(fields)
+    out_fields["nbr_counts"] = counts
+    out_fields["score"] = scores
+    if fb is not None:
+        out_fields["is_fallback"] = fb
+    return ItemListCollection.from_ragged(keys, offsets, item_ids, out_fields, key=("user_id",),
+                                          absent={"nbr_counts": nohist})
+
+
+def _predict_loop(pipe: Pipeline, pairs: dict) -> ItemListCollection:
+    "``predict`` one query at a time (the path of every pipeline without a batched one)."
     scorer = pipe.node("scorer").component
     lookup = pipe.node("history-lookup").component
     users = list(pairs)

@@ -262,6 +262,24 @@ class ItemListCollection:
         ilc._index_stale = True  # the key -> position dict is built by the first ``lookup``
         return ilc
 
+    @classmethod
+    def from_ragged(cls, keys, offsets: np.ndarray, item_ids: np.ndarray,
+                    fields: dict[str, np.ndarray] | None = None, *, key=("user_id",),
+                    absent: dict[str, np.ndarray] | None = None) -> "ItemListCollection":
+        """
+        A collection over ragged result arrays -- list ``i`` is entries
+        ``offsets[i]:offsets[i + 1]`` of ``item_ids`` and of every array in ``fields`` (in the
+        fields' order; ``score`` is float32) -- built lazily like :meth:`from_arrays`: the
+        ``ItemList`` of a key exists once somebody asks for it.  ``absent[name]`` (bool per list)
+        leaves field ``name`` out of the lists where it is set (a query without history has no
+        ``nbr_counts``).  ``to_df`` and ``total_items`` work on the arrays directly.
+        """
+        ilc = cls(key)
+        ilc._lists = _RaggedLists(ilc._key_class, keys, offsets, item_ids, fields or {},
+                                  absent or {})
+        ilc._index_stale = True
+        return ilc
+
     def _ensure_index(self):
         if getattr(self, "_index_stale", False) and self._index is not None:
             self._index_stale = False
@@ -404,6 +422,65 @@ class _LazyLists:
         ends = np.cumsum(counts)
         cols["rank"] = np.arange(1, int(ends[-1]) + 1 if len(ends) else 1) - \
             np.repeat(ends - counts, counts)
+        df = pd.DataFrame(cols)
+        if self.extra:
+            frames = [df]
+            for key, il in self.extra:
+                d2 = il.to_df()
+                for f, v in zip(reversed(key_fields), reversed(key)):
+                    d2.insert(0, f, v)
+                frames.append(d2)
+            df = pd.concat(frames, ignore_index=True)
+        return df
+
+
+class _RaggedLists(_LazyLists):
+    "The ``(key, ItemList)`` sequence of a ragged-array collection (``from_ragged``)."
+
+    def __init__(self, key_class, keys, offsets, item_ids, fields, absent):
+        super().__init__(key_class, keys, None, None, None)
+        self.offsets = np.asarray(offsets, dtype=np.int64)
+        self.item_ids = np.asarray(item_ids)
+        self.fields = dict(fields)
+        self.absent = {k: np.asarray(v, dtype=bool) for k, v in absent.items()}
+        assert len(self.offsets) == len(self.raw_keys) + 1
+        assert all(len(v) == len(self.item_ids) for v in self.fields.values())
+
+    def _make(self, pos: int):
+        hit = self._made.get(pos)
+        if hit is None:
+            lo, hi = int(self.offsets[pos]), int(self.offsets[pos + 1])
+            il = ItemList(item_ids=self.item_ids[lo:hi])
+            for name, val in self.fields.items():
+                gone = self.absent.get(name)
+                if gone is None or not gone[pos]:
+                    il._fields[name] = val[lo:hi]
+            hit = (self.key(pos), il)
+            self._made[pos] = hit
+        return hit
+
+    def total_items(self) -> int:
+        return int(self.offsets[-1] - self.offsets[0]) + sum(len(il) for _k, il in self.extra)
+
+    def to_df(self, key_fields) -> pd.DataFrame:
+        counts = np.diff(self.offsets)
+        lo = int(self.offsets[0])
+        cols = {}
+        for j, f in enumerate(key_fields):
+            col = self.raw_keys if (j == 0 and isinstance(self.raw_keys, np.ndarray)
+                                    and self.raw_keys.ndim == 1) else \
+                np.asarray([self.key(p)[j] for p in range(len(self.raw_keys))])
+            cols[f] = np.repeat(col, counts)
+        sl = slice(lo, int(self.offsets[-1]))
+        cols["item_id"] = self.item_ids[sl]
+        for name, val in self.fields.items():
+            v = val[sl]
+            gone = self.absent.get(name)
+            if gone is not None and gone.any():
+                # what concatenating the lists' frames gives: missing cells are NaN
+                v = v.astype(np.float64)
+                v[np.repeat(gone, counts)] = np.nan
+            cols[name] = v
         df = pd.DataFrame(cols)
         if self.extra:
             frames = [df]

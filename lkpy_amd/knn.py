@@ -159,6 +159,40 @@ class ItemKNNScorer(Component):
     def __call__(self, query, items: ItemList) -> ItemList:
         return self.score_batch([query], [items])[0]
 
+    def _device_means(self):
+        "The explicit model's item means in HBM (f32), uploaded once."
+        st = self._device_sims()
+        bias = st.get("means")
+        if bias is None and self.config.explicit and self.item_means is not None:
+            bias = st["means"] = torch.from_numpy(
+                np.asarray(self.item_means, dtype=np.float32)).to(st["device"])
+        return bias if self.config.explicit else None
+
+    def score_history_batch(self, batch, tgt_ptr, tgt_nums):
+        """
+        ``score_batch`` for training histories by user number (``UserTrainingHistoryLookup.batch``):
+        the histories are cut out of the HBM-resident training matrix with the ratings
+        mean-centred on the way (as in ``_recommend_history_batch``), the targets -- int64 offsets
+        ``tgt_ptr`` [B + 1] and this scorer's item numbers ``tgt_nums`` (-1 = unknown), host
+        arrays or device tensors -- are uploaded once, and one ``lk_iknn_score_batch`` call
+        scores everything.  Returns device (scores f32, counts int32) over the targets: the
+        kernel's output, item means NOT yet added back (``lk_predict_merge`` does that).
+        """
+        st = self._device_sims()
+        d = st["device"]
+        if self.config.explicit and not batch.has_ratings:
+            raise RuntimeError("explicit-feedback scorer must have ratings")
+        if not isinstance(tgt_ptr, torch.Tensor):
+            tgt_ptr = torch.from_numpy(np.ascontiguousarray(tgt_ptr, dtype=np.int64)).to(d)
+        if not isinstance(tgt_nums, torch.Tensor):
+            tgt_nums = torch.from_numpy(np.ascontiguousarray(tgt_nums, dtype=np.int32)).to(d)
+        bias = self._device_means()
+        hist = batch.csr(use_ratings=self.config.explicit, scale=1.0, col_bias=bias,
+                         with_values=self.config.explicit)
+        return D.iknn_score_batch(st["sims"], hist.indptr, hist.indices,
+                                  hist.values if self.config.explicit else None, tgt_ptr,
+                                  tgt_nums, self.config.max_nbrs, self.config.min_nbrs)
+
     def recommend_batch(self, queries, n: int, *, exclude_history: bool = True):
         """
         Top-``n`` lists for many queries at once -- what the ``recommender`` pipeline computes one
