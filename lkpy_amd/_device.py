@@ -135,6 +135,17 @@ def to_host_unpadded(mat: torch.Tensor, k: int) -> np.ndarray:
     return dst.cpu().numpy()
 
 
+def lists_to_host(idx: torch.Tensor, scores: torch.Tensor, rows: torch.Tensor | None = None):
+    """
+    The [B x n] item numbers (int32) and scores (f32) of a batched recommend call as host arrays,
+    in one crossing; ``rows`` (device int64 [B]): output row r is input row ``rows[r]``.
+    """
+    both = torch.cat([idx.view(torch.float32), scores], dim=1)
+    host = to_host(both if rows is None else both[rows])
+    cols = idx.shape[1]
+    return host[:, :cols].view(np.int32), host[:, cols:]
+
+
 @dataclass
 class DeviceCSR:
     "CSR in HBM: the SparseRowArray layout (offsets i32/i64, indices i32, values f32)."

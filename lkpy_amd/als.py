@@ -58,8 +58,7 @@ def _scorer_state(obj) -> dict:
     pend = obj.__dict__.get("_pending_sync")
     if pend is not None:
         pend()
-    st = dict(obj.__dict__)
-    st.pop("_dev", None)
+    st = Component.__getstate__(obj)
     st.pop("_pending_sync", None)
     return st
 
@@ -170,14 +169,12 @@ class ImplicitMFScorer(UsesTrainer, Component):
         _restore_scorer_state(self, state)
 
     def _device_state(self):
-        dev = getattr(self, "_dev", None)
-        if dev is None or dev["src"] is not self.item_embeddings:
+        def upload():
             d = D.device()
-            dev = {"src": self.item_embeddings, "device": d,
-                   "Q": D.to_device_padded(self.item_embeddings, d),
-                   "OtOr": torch.from_numpy(np.ascontiguousarray(self._OtOr)).to(d)}
-            self._dev = dev
-        return dev
+            return {"device": d, "Q": D.to_device_padded(self.item_embeddings, d),
+                    "OtOr": torch.from_numpy(np.ascontiguousarray(self._OtOr)).to(d)}
+
+        return self._device_cache("model", upload, self.item_embeddings, self._OtOr)
 
     def _solver(self, options: TrainingOptions | None = None) -> int:
         name = self.config.solver
@@ -215,51 +212,84 @@ class ImplicitMFScorer(UsesTrainer, Component):
         values = np.concatenate(val).astype(np.float32) if val else np.zeros(0, np.float32)
         return np.asarray(ptr, dtype=np.int64), indices, values
 
+    def _query_csr(self, queries: list[RecQuery]) -> D.DeviceCSR:
+        "``_history_rows`` uploaded: the list front-end's histories as a device CSR."
+        ptr, idx, val = self._history_rows(queries)
+        return D.DeviceCSR.from_arrays(ptr, idx, val, (len(queries), len(self.items)),
+                                       self._device_state()["device"])
+
+    def _fold_in(self, hist: D.DeviceCSR, pending: list | None = None) -> torch.Tensor:
+        "One fold-in per row of ``hist`` (_implicit.py:77-130 per query): one half-epoch launch."
+        st = self._device_state()
+        return D.fold_in(hist, st["Q"], st["OtOr"], self.config.embedding_size, self._solver(),
+                         pending)
+
     def new_user_embedding(self, user_num, user_items: ItemList):
         "One fold-in (_implicit.py:77-99); returns (vector, None)."
-        st = self._device_state()
-        ptr, idx, val = self._history_rows([RecQuery(user_items=user_items)])
-        hist = D.DeviceCSR.from_arrays(ptr, idx, val, (1, len(self.items)), st["device"])
-        u = D.fold_in(hist, st["Q"], st["OtOr"], self.config.embedding_size, self._solver())
+        u = self._fold_in(self._query_csr([RecQuery(user_items=user_items)]))
         return D.to_host_unpadded(u, self.config.embedding_size)[0], None
 
-    def _query_embeddings(self, queries: list[RecQuery]) -> tuple[torch.Tensor, np.ndarray]:
+    def _embeddings(self, hist: D.DeviceCSR, has_hist: np.ndarray, stored: np.ndarray,
+                    pending: list | None = None) -> tuple[torch.Tensor, np.ndarray]:
         """
         Device [B x KP] embedding per query + validity mask, with ``ALSBase.__call__``'s
         precedence (_common.py:139-157): history present and user_embeddings != "prefer" ->
-        fold-in; else the stored row; else invalid.
+        fold-in; else the stored row; else invalid.  ``hist``: the queries' histories (device
+        CSR of confidence values); ``has_hist``, ``stored`` (the user's row of
+        ``user_embeddings``, -1 = none): host arrays over the queries.
         """
-        st = self._device_state()
-        k = self.config.embedding_size
-        B = len(queries)
-        fold = [q.query_items is not None and len(q.query_items) > 0 and
-                self.config.user_embeddings != "prefer" for q in queries]
-        out = torch.zeros((B, D.padded_dim(k)), dtype=torch.float32, device=st["device"])
-        valid = np.zeros(B, dtype=bool)
-        fi = [i for i in range(B) if fold[i]]
-        if fi:
-            ptr, idx, val = self._history_rows([queries[i] for i in fi])
-            hist = D.DeviceCSR.from_arrays(ptr, idx, val, (len(fi), len(self.items)),
-                                           st["device"])
-            u = D.fold_in(hist, st["Q"], st["OtOr"], k, self._solver())
-            out[torch.as_tensor(fi, device=st["device"])] = u
-            valid[fi] = True
-        rest = [i for i in range(B) if not fold[i]]
-        if rest and self.user_embeddings is not None and self.users is not None:
-            nums = [None if queries[i].user_id is None else
-                    self.users.number(queries[i].user_id, missing=None) for i in rest]
-            have = [(i, n) for i, n in zip(rest, nums) if n is not None]
-            if have:
-                rows = self.user_embeddings[[n for _, n in have]]
-                out[torch.as_tensor([i for i, _ in have], device=st["device"])] = \
-                    D.to_device_padded(rows, st["device"])
-                valid[[i for i, _ in have]] = True
-        return out, valid
+        d = self._device_state()["device"]
+        B = len(has_hist)
+        fold = has_hist & (self.config.user_embeddings != "prefer")
+        if B and fold.all():
+            u = self._fold_in(hist, pending)
+        else:
+            u = torch.zeros((B, D.padded_dim(self.config.embedding_size)), dtype=torch.float32,
+                            device=d)
+            if fold.any():
+                rows = np.flatnonzero(fold)
+                u[torch.from_numpy(rows).to(d)] = self._fold_in(D.gather_rows(hist, rows), pending)
+        take = ~fold & (stored >= 0)
+        if take.any():
+            rows = np.ascontiguousarray(self.user_embeddings[stored[take]], dtype=np.float32)
+            u[torch.from_numpy(np.flatnonzero(take)).to(d)] = D.to_device_padded(rows, d)
+        return u, fold | take
+
+    def _query_embeddings(self, queries: list[RecQuery], pending: list | None = None):
+        """
+        :meth:`_embeddings` for a list of queries: histories by :meth:`_history_rows`, stored
+        rows by user id.  Returns (device [B x KP], valid, history CSR).
+        """
+        hist = self._query_csr(queries)
+        has_hist = np.array([q.query_items is not None and len(q.query_items) > 0
+                             for q in queries], dtype=bool)
+        stored = np.full(len(queries), -1, dtype=np.int64)
+        if self.user_embeddings is not None and self.users is not None:
+            for i, q in enumerate(queries):
+                num = None if q.user_id is None else self.users.number(q.user_id, missing=None)
+                stored[i] = -1 if num is None else num
+        return (*self._embeddings(hist, has_hist, stored, pending), hist)
+
+    def _history_batch_embeddings(self, batch, pending: list | None = None):
+        """
+        :meth:`_embeddings` for a :class:`lkpy_amd.basic.HistoryBatch`: the histories' CSR is cut
+        out of the HBM-resident training matrix by one kernel (no per-query Python), the stored
+        rows are found by user number.  Returns (device [B x KP], valid, history CSR).
+        """
+        cfg = self.config
+        stored = np.full(len(batch), -1, dtype=np.int64)
+        if self.user_embeddings is not None and self.users is not None:
+            if batch.users is self.users or batch.users == self.users:
+                stored = batch.user_nums.astype(np.int64)
+            else:
+                stored = self.users.numbers(batch.user_ids, missing="negative").astype(np.int64)
+        hist = batch.csr(use_ratings=cfg.use_ratings, scale=cfg.weight)
+        return (*self._embeddings(hist, batch.lengths > 0, stored, pending), hist)
 
     # -- scoring (src/lenskit/als/_common.py:133-175) -----------------------------------
     def __call__(self, query, items: ItemList) -> ItemList:
         query = RecQuery.create(query)
-        u, valid = self._query_embeddings([query])
+        u, valid, _ = self._query_embeddings([query])
         if not valid[0]:
             return ItemList(items, scores=np.nan)
         st = self._device_state()
@@ -269,44 +299,6 @@ class ImplicitMFScorer(UsesTrainer, Component):
         scores = np.full(len(items), np.nan, dtype=np.float32)
         scores[mask] = all_scores[item_nums[mask]]
         return ItemList(items, scores=scores)
-
-    def _history_batch_embeddings(self, batch, pending: list | None = None):
-        """
-        ``_query_embeddings`` for a :class:`lkpy_amd.basic.HistoryBatch`: the histories' CSR is cut
-        out of the HBM-resident training matrix by one kernel (no per-query Python), the fold-in
-        is ONE half-epoch launch over it (_implicit.py:77-130 per query in the reference), and
-        the precedence of ``ALSBase.__call__`` (_common.py:139-157) is applied with host masks
-        over the batch: history present and user_embeddings != "prefer" -> fold-in; else the
-        stored row of a known user; else invalid.  Returns (device [B x KP], valid, history CSR).
-        """
-        st = self._device_state()
-        cfg = self.config
-        k = cfg.embedding_size
-        B = len(batch)
-        has_hist = batch.lengths > 0
-        stored = np.full(B, -1, dtype=np.int64)
-        if self.user_embeddings is not None and self.users is not None:
-            if batch.users is self.users or batch.users == self.users:
-                stored = batch.user_nums.astype(np.int64)
-            else:
-                stored = self.users.numbers(batch.user_ids, missing="negative").astype(np.int64)
-        fold = has_hist if cfg.user_embeddings != "prefer" else (has_hist & (stored < 0))
-        hist = batch.csr(use_ratings=cfg.use_ratings, scale=cfg.weight)
-        if fold.all():
-            u = D.fold_in(hist, st["Q"], st["OtOr"], k, self._solver(), pending)
-        elif fold.any():
-            sub = batch.subset(fold).csr(use_ratings=cfg.use_ratings, scale=cfg.weight)
-            u = torch.zeros((B, D.padded_dim(k)), dtype=torch.float32, device=st["device"])
-            u[torch.from_numpy(np.flatnonzero(fold)).to(st["device"])] = \
-                D.fold_in(sub, st["Q"], st["OtOr"], k, self._solver(), pending)
-        else:
-            u = torch.zeros((B, D.padded_dim(k)), dtype=torch.float32, device=st["device"])
-        take = ~fold & (stored >= 0)
-        if take.any():
-            rows = np.ascontiguousarray(self.user_embeddings[stored[take]], dtype=np.float32)
-            u[torch.from_numpy(np.flatnonzero(take)).to(st["device"])] = \
-                D.to_device_padded(rows, st["device"])
-        return u, fold | take, hist
 
     def recommend_batch(self, queries, n: int, *, exclude_history: bool = True,
                         device_output: bool = False):
@@ -323,40 +315,27 @@ class ImplicitMFScorer(UsesTrainer, Component):
         if isinstance(queries, HistoryBatch) and not (
                 queries.items is self.items or queries.items == self.items):
             queries = queries.queries()  # (another item vocabulary: the per-query mapping)
+        pending: list = []  # the fold-in's status is read once the scoring is queued behind it
         if isinstance(queries, HistoryBatch):
-            pending: list = []  # the fold-in's status is read once the scoring is queued behind it
             u, valid, hist = self._history_batch_embeddings(queries, pending)
-            st = self._device_state()
-            if exclude_history:
-                idx, sc = D.score_topk(u, st["Q"], self.config.embedding_size, n, hist.indptr,
-                                       hist.indices)
-            else:
-                idx, sc = D.score_topk(u, st["Q"], self.config.embedding_size, n)
-            for plan in pending:
-                plan.check_status()  # RuntimeError("ALS solve error: ...") like the fold-in alone
-            if not valid.all():
-                bad = torch.from_numpy(np.flatnonzero(~valid)).to(st["device"])
-                idx[bad] = -1
-                sc[bad] = float("nan")
-            if device_output:
-                return idx, sc
-            both = torch.cat([idx.view(torch.float32), sc], dim=1)  # one crossing, not two
-            host = D.to_host(both)
-            cols = idx.shape[1]
-            return host[:, :cols].view(np.int32), host[:, cols:]
-        queries = [RecQuery.create(q) for q in queries]
-        u, valid = self._query_embeddings(queries)
+        else:
+            u, valid, hist = self._query_embeddings([RecQuery.create(q) for q in queries],
+                                                    pending)
         st = self._device_state()
-        excl_ptr = excl_idx = None
         if exclude_history:
-            ptr, idx, _ = self._history_rows(queries)
-            excl_ptr = torch.from_numpy(ptr).to(st["device"])
-            excl_idx = torch.from_numpy(idx).to(st["device"])
-        idx, sc = D.score_topk(u, st["Q"], self.config.embedding_size, n, excl_ptr, excl_idx)
-        idx, sc = idx.cpu().numpy(), sc.cpu().numpy()
-        idx[~valid] = -1
-        sc[~valid] = np.nan
-        return idx, sc
+            idx, sc = D.score_topk(u, st["Q"], self.config.embedding_size, n, hist.indptr,
+                                   hist.indices)
+        else:
+            idx, sc = D.score_topk(u, st["Q"], self.config.embedding_size, n)
+        for plan in pending:
+            plan.check_status()  # RuntimeError("ALS solve error: ...") like the fold-in alone
+        if not valid.all():
+            bad = torch.from_numpy(np.flatnonzero(~valid)).to(st["device"])
+            idx[bad] = -1
+            sc[bad] = float("nan")
+        if device_output:
+            return idx, sc
+        return D.lists_to_host(idx, sc)
 
 
 class ImplicitMFTrainer(ModelTrainer):
@@ -488,13 +467,11 @@ class BiasedMFScorer(UsesTrainer, Component):
         _restore_scorer_state(self, state)
 
     def _device_state(self):
-        dev = getattr(self, "_dev", None)
-        if dev is None or dev["src"] is not self.item_embeddings:
+        def upload():
             d = D.device()
-            dev = {"src": self.item_embeddings, "device": d,
-                   "Q": D.to_device_padded(self.item_embeddings, d)}
-            self._dev = dev
-        return dev
+            return {"device": d, "Q": D.to_device_padded(self.item_embeddings, d)}
+
+        return self._device_cache("model", upload, self.item_embeddings)
 
     def new_user_embedding(self, user_num, user_items: ItemList):
         "_explicit.py:56-74: normalise the ratings with the bias model, one explicit row solve."

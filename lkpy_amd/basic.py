@@ -45,15 +45,9 @@ class UserTrainingHistoryLookup(Component):
 
 
     # -- whole batches of queries --------------------------------
-    def __getstate__(self):
-        st = dict(self.__dict__)
-        st.pop("_dev", None)
-        return st
-
     def _device_matrix(self):
-        "The training matrix resident in HBM (uploaded once, never pickled): offsets, items, ratings."
-        st = self.__dict__.get("_dev")
-        if st is None:
+        "The training matrix resident in HBM (uploaded once per training): offsets, items, ratings."
+        def upload():
             from . import _device as D
 
             ds = self.interactions._ds
@@ -67,8 +61,9 @@ class UserTrainingHistoryLookup(Component):
                   "has_ratings": rat is not None}
             if rat is None:
                 st["csr"].values = None
-            self._dev = st
-        return st
+            return st
+
+        return self._device_cache("matrix", upload, self.interactions)
 
     def batch(self, user_ids) -> "HistoryBatch":
         """
@@ -308,25 +303,18 @@ class BiasScorer(Component):
         return ItemList(items, scores=scores)
 
     # -- whole batches of queries (batch.predict) ---------------------------------------------
-    def __getstate__(self):
-        st = dict(self.__dict__)
-        st.pop("_dev", None)
-        return st
-
-    def _device_model(self):
-        "The item biases in HBM (f32; None without an item term), uploaded once, never pickled."
-        st = self.__dict__.get("_dev")
-        if st is None or st["model"] is not self.model:
+    def _device_item_biases(self):
+        "The item biases in HBM (f32; None without an item term), uploaded once per model."
+        def upload():
             import torch
 
             from . import _device as D
 
             ib = self.model.item_biases
-            st = {"model": self.model,
-                  "item_biases": None if ib is None else torch.from_numpy(
-                      np.ascontiguousarray(ib, dtype=np.float32)).to(D.device())}
-            self._dev = st
-        return st
+            return None if ib is None else torch.from_numpy(
+                np.ascontiguousarray(ib, dtype=np.float32)).to(D.device())
+
+        return self._device_cache("item_biases", upload, self.model)
 
     def user_offsets_batch(self, batch: "HistoryBatch"):
         """
@@ -341,7 +329,6 @@ class BiasScorer(Component):
 
         from . import _device as D
 
-        st = self._device_model()
         mat = batch.lookup._device_matrix()
         dev = mat["device"]
         B = len(batch)
@@ -352,7 +339,8 @@ class BiasScorer(Component):
             raise ValueError("user biases from the history need ratings")
         nums = torch.from_numpy(np.ascontiguousarray(batch.user_nums, dtype=np.int32)).to(dev)
         return D.bias_user_offsets(mat["csr"], nums, self.model.global_bias,
-                                   st["item_biases"], _damping(self.model.damping, "user"))
+                                   self._device_item_biases(),
+                                   _damping(self.model.damping, "user"))
 
 
 class FallbackScorer(Component):

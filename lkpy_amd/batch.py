@@ -190,7 +190,7 @@ def _predict_batched(parts, keys, offsets, item_ids, fields, batch_size: int):
     nohist = np.empty(B, np.bool_)
     d = scorer._device_sims()["device"]
     means = scorer._device_means()
-    item_biases = bias._device_model()["item_biases"] if bias is not None else None
+    item_biases = bias._device_item_biases() if bias is not None else None
     for s0 in range(0, B, batch_size):
         s1 = min(B, s0 + batch_size)
         nb = s1 - s0

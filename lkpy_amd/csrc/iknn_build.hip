@@ -15,7 +15,7 @@
 // v_mul followed by an LDS read / v_add / write; FMA contraction is switched off.
 // The accumulation order of every cell is therefore the reference's, independent of
 // scheduling.  (LDS float atomics would also be in order, but ds_add_f32 retires
-// ~1 lane per 3 cycles per CU on gfx950 -- tools/ub/lds_atomic.hip -- 30x slower.)
+// ~1 lane per 3 cycles per CU on gfx950 -- tools/ub/lds_add_ub.hip -- 30x slower.)
 //
 // Data layout.  Each wave keeps a dense f32 accumulator for a window of W columns in
 // its private quarter of the workgroup's LDS (W = 4096 -> 64 KiB per workgroup, two

@@ -60,11 +60,6 @@ class ItemKNNScorer(Component):
     def is_trained(self):
         return hasattr(self, "sim_matrix")
 
-    def __getstate__(self):
-        st = dict(self.__dict__)
-        st.pop("_dev", None)
-        return st
-
     def train(self, data: Dataset, options: TrainingOptions = TrainingOptions()):
         field = "rating" if self.config.explicit else None
         rmat = data.interactions().matrix().scipy(field, layout="coo").astype(np.float32)
@@ -89,131 +84,64 @@ class ItemKNNScorer(Component):
         import pyarrow as pa
 
         assert pa.types.is_large_list(self.sim_matrix.type.storage_type)
-        self._dev = {"sims": out, "device": dev}
+        # the build's output IS the device copy of the new matrix: not uploaded again
+        self._device_cache("sims", lambda: {"sims": out, "device": dev}, self.sim_matrix)
 
     def _device_sims(self):
-        dev = getattr(self, "_dev", None)
-        if dev is None:
+        "The similarity matrix in HBM (int64 offsets), uploaded once per model."
+        def upload():
             d = D.device()
             from .matrix import csr_arrays
 
             so, si, sv, shape = csr_arrays(self.sim_matrix)
-            dev = {"device": d,
-                   "sims": D.DeviceCSR(
-                       torch.from_numpy(np.array(so, dtype=np.int64)).to(d),
-                       torch.from_numpy(np.array(si, dtype=np.int32)).to(d),
-                       torch.from_numpy(np.array(sv, dtype=np.float32)).to(d),
-                       shape, None)}
-            self._dev = dev
-        return dev
+            return {"device": d,
+                    "sims": D.DeviceCSR(
+                        torch.from_numpy(np.array(so, dtype=np.int64)).to(d),
+                        torch.from_numpy(np.array(si, dtype=np.int32)).to(d),
+                        torch.from_numpy(np.array(sv, dtype=np.float32)).to(d),
+                        shape, None)}
 
-    def score_batch(self, queries, item_lists) -> list[ItemList]:
-        "Score many (query, items) pairs in one kernel launch (item.py:231-295 per pair)."
-        st = self._device_sims()
-        d = st["device"]
-        queries = [RecQuery.create(q) for q in queries]
-        r_idx, r_val, r_ptr, t_idx, t_ptr = [], [], [0], [], [0]
-        nohist = []
-        for q, items in zip(queries, item_lists):
-            ratings = q.query_items
-            if ratings is None or len(ratings) == 0:
-                nohist.append(True)
-                r_ptr.append(r_ptr[-1])
-            else:
-                nohist.append(False)
-                ri = ratings.numbers(vocabulary=self.items, missing="negative")
-                if self.config.explicit:
-                    rv = ratings.field("rating")
-                    if rv is None:
-                        raise RuntimeError("explicit-feedback scorer must have ratings")
-                    rv = np.asarray(rv).astype(np.float32, copy=True)
-                    m = ri >= 0
-                    rv[m] -= self.item_means[ri[m]]  # mean-centre (item.py:268-271)
-                    r_val.append(rv)
-                r_idx.append(ri)
-                r_ptr.append(r_ptr[-1] + len(ri))
-            ti = items.numbers(vocabulary=self.items, missing="negative")
-            t_idx.append(ti)
-            t_ptr.append(t_ptr[-1] + len(ti))
-        cat = lambda xs, dt: np.concatenate(xs).astype(dt) if xs else np.zeros(0, dt)  # noqa: E731
-        to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(d)  # noqa: E731
-        rr = to(cat(r_val, np.float32)) if self.config.explicit else None
-        s, c = D.iknn_score_batch(st["sims"], to(np.asarray(r_ptr, np.int64)),
-                                  to(cat(r_idx, np.int32)), rr, to(np.asarray(t_ptr, np.int64)),
-                                  to(cat(t_idx, np.int32)), self.config.max_nbrs,
-                                  self.config.min_nbrs)
-        s, c = s.cpu().numpy(), c.cpu().numpy()
-        out = []
-        for qi, items in enumerate(item_lists):
-            if nohist[qi]:
-                out.append(ItemList(items, scores=np.nan))  # item.py:238-245
-                continue
-            sc = s[t_ptr[qi]:t_ptr[qi + 1]].copy()
-            ti = t_idx[qi]
-            if self.config.explicit:
-                m = ti >= 0
-                sc[m] += self.item_means[ti[m]]  # item.py:282
-            out.append(ItemList(items, scores=sc, nbr_counts=c[t_ptr[qi]:t_ptr[qi + 1]]))
-        return out
-
-    def __call__(self, query, items: ItemList) -> ItemList:
-        return self.score_batch([query], [items])[0]
+        return self._device_cache("sims", upload, self.sim_matrix)
 
     def _device_means(self):
-        "The explicit model's item means in HBM (f32), uploaded once."
-        st = self._device_sims()
-        bias = st.get("means")
-        if bias is None and self.config.explicit and self.item_means is not None:
-            bias = st["means"] = torch.from_numpy(
-                np.asarray(self.item_means, dtype=np.float32)).to(st["device"])
-        return bias if self.config.explicit else None
+        "The explicit model's item means in HBM (f32), uploaded once per model; None if implicit."
+        if not self.config.explicit or self.item_means is None:
+            return None
+        return self._device_cache(
+            "means", lambda: torch.from_numpy(np.asarray(self.item_means, dtype=np.float32)).to(
+                self._device_sims()["device"]), self.item_means)
 
-    def score_history_batch(self, batch, tgt_ptr, tgt_nums):
+    def _row_hits(self, csr: D.DeviceCSR) -> np.ndarray:
         """
-        ``score_batch`` for training histories by user number (``UserTrainingHistoryLookup.batch``):
-        the histories are cut out of the HBM-resident training matrix with the ratings
-        mean-centred on the way (as in ``_recommend_history_batch``), the targets -- int64 offsets
-        ``tgt_ptr`` [B + 1] and this scorer's item numbers ``tgt_nums`` (-1 = unknown), host
-        arrays or device tensors -- are uploaded once, and one ``lk_iknn_score_batch`` call
-        scores everything.  Returns device (scores f32, counts int32) over the targets: the
-        kernel's output, item means NOT yet added back (``lk_predict_merge`` does that).
+        Per row of a device CSR of item numbers (-1 = unknown): the similarity-row lengths of its
+        items, summed -- a query's hit count, which ``lk_iknn_recommend`` sizes its lists and
+        balances its launch by.  Host int64.
         """
-        st = self._device_sims()
-        d = st["device"]
-        if self.config.explicit and not batch.has_ratings:
-            raise RuntimeError("explicit-feedback scorer must have ratings")
-        if not isinstance(tgt_ptr, torch.Tensor):
-            tgt_ptr = torch.from_numpy(np.ascontiguousarray(tgt_ptr, dtype=np.int64)).to(d)
-        if not isinstance(tgt_nums, torch.Tensor):
-            tgt_nums = torch.from_numpy(np.ascontiguousarray(tgt_nums, dtype=np.int32)).to(d)
-        bias = self._device_means()
-        hist = batch.csr(use_ratings=self.config.explicit, scale=1.0, col_bias=bias,
-                         with_values=self.config.explicit)
-        return D.iknn_score_batch(st["sims"], hist.indptr, hist.indices,
-                                  hist.values if self.config.explicit else None, tgt_ptr,
-                                  tgt_nums, self.config.max_nbrs, self.config.min_nbrs)
+        d = csr.indices.device
+        cnt = torch.from_numpy(np.asarray(self.item_counts, dtype=np.int64)).to(d)
+        idx = csr.indices.long()
+        csum = torch.zeros(idx.numel() + 1, dtype=torch.int64, device=d)
+        torch.cumsum(torch.where(idx >= 0, cnt[idx.clamp(min=0)], 0), 0, out=csum[1:])
+        ptr = csr.indptr.long()
+        return (csum[ptr[1:]] - csum[ptr[:-1]]).cpu().numpy()
 
-    def recommend_batch(self, queries, n: int, *, exclude_history: bool = True):
+    def _user_hits(self, lookup) -> np.ndarray:
         """
-        Top-``n`` lists for many queries at once -- what the ``recommender`` pipeline computes one
-        query at a time (src/lenskit/batch/_runner.py:283-308): candidates = every training item
-        minus the query's own (src/lenskit/basic/candidates.py:77-94), this scorer over them
-        (item.py:231-295, means added back: 282), ``TopNRanker`` (basic/topn.py:45-69).  One
-        ``lk_iknn_recommend`` call: scores bit-identical to the reference accumulator's, items
-        with fewer than ``min_nbrs`` neighbours never listed, queries without history get empty
-        lists (item.py:238-245: all-NaN scores).  Returns (item numbers [B x n] with -1 padding,
-        scores [B x n] with NaN padding), like ``ImplicitMFScorer.recommend_batch``.
+        The hit count of every training user of ``lookup``, computed on the device once per
+        training of either component.  The entry is tied to the host matrix the lookup's device
+        matrix is built from, so it does not keep that device matrix alive after a retrain.
         """
-        from .basic import HistoryBatch
+        return self._device_cache("user_hits",
+                                  lambda: self._row_hits(lookup._device_matrix()["csr"]),
+                                  lookup.interactions, self.sim_matrix)
 
-        if isinstance(queries, HistoryBatch) and not (
-                queries.items is self.items or queries.items == self.items):
-            queries = queries.queries()  # (another item vocabulary: the per-query mapping)
-        if isinstance(queries, HistoryBatch):
-            return self._recommend_history_batch(queries, n, exclude_history)
-        st = self._device_sims()
-        d = st["device"]
-        queries = [RecQuery.create(q) for q in queries]
+    # -- the two front-ends: histories as a device CSR in query order -------------------------
+    def _query_csr(self, queries: list[RecQuery]) -> D.DeviceCSR:
+        """
+        The histories of a list of queries: item numbers (-1 = unknown) and, explicit, the
+        float32 ratings minus the float32 item means (item.py:268-271; unknown items are not
+        centred), uploaded in query order.
+        """
         r_idx, r_val, r_ptr = [], [], [0]
         for q in queries:
             ratings = q.query_items
@@ -232,82 +160,124 @@ class ItemKNNScorer(Component):
             r_idx.append(ri)
             r_ptr.append(r_ptr[-1] + len(ri))
         cat = lambda xs, dt: np.concatenate(xs).astype(dt) if xs else np.zeros(0, dt)  # noqa: E731
-        to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(d)  # noqa: E731
-        idx = cat(r_idx, np.int32)
-        ptr = np.asarray(r_ptr, np.int64)
-        # hits per query: the similarity-row lengths of its history items, summed
-        counts = np.asarray(self.item_counts, dtype=np.int64)
-        per = np.where(idx >= 0, counts[np.maximum(idx, 0)], 0)
-        csum = np.concatenate([[0], np.cumsum(per)])
-        hits = csum[ptr[1:]] - csum[ptr[:-1]]
-        # heaviest queries first (the launch is as long as its longest task chain); undone below
-        order = np.argsort(-hits, kind="stable")
-        lens = np.diff(ptr)[order]
-        optr = np.zeros(len(order) + 1, np.int64)
-        np.cumsum(lens, out=optr[1:])
-        take = np.concatenate([np.arange(ptr[q], ptr[q + 1]) for q in order]) if len(idx) else \
-            np.zeros(0, np.int64)
-        bias = st.get("means")
-        if bias is None and self.config.explicit and self.item_means is not None:
-            bias = st["means"] = to(np.asarray(self.item_means, dtype=np.float32))
-        rr = to(cat(r_val, np.float32)[take]) if self.config.explicit else None
-        oi, osc = D.iknn_recommend(st["sims"], to(optr), to(idx[take]), rr,
-                                   bias if self.config.explicit else None, self.config.max_nbrs,
-                                   self.config.min_nbrs, n, hits[order], exclude_history)
-        inv = np.empty_like(order)
-        inv[order] = np.arange(len(order))
-        return oi.cpu().numpy()[inv], osc.cpu().numpy()[inv]
+        hist = D.DeviceCSR.from_arrays(np.asarray(r_ptr, np.int64), cat(r_idx, np.int32),
+                                       cat(r_val, np.float32), (len(queries), len(self.items)),
+                                       self._device_sims()["device"])
+        if not self.config.explicit:
+            hist.values = None
+        return hist
 
-
-    accepts_history_batch = True  # recommend_batch takes a lkpy_amd.basic.HistoryBatch
-
-    def _recommend_history_batch(self, batch, n: int, exclude_history: bool):
+    def _batch_csr(self, batch) -> D.DeviceCSR:
         """
-        ``recommend_batch`` for training histories by user number (``UserTrainingHistoryLookup.
-        batch``): nothing is done per query on the host.  The histories -- in the training rows'
-        order, which is what the reference's lookup hands the scorer (basic/history.py:77-95) --
-        are cut out of the HBM-resident training matrix with the ratings mean-centred on the way
-        (``lk_csr_gather_rows`` with the item means as column bias: item.py:268-271); a query's
-        hit count (the summed similarity-row lengths of its history items, what the launch is
-        balanced by) is a property of the USER, computed once for every training user on the
-        device; the batch goes heaviest query first and the lists come back in the caller's order.
+        The histories of a :class:`lkpy_amd.basic.HistoryBatch`, in the training rows' order
+        (what the reference's lookup hands the scorer, basic/history.py:77-95): cut out of the
+        HBM-resident training matrix with the ratings mean-centred on the way
+        (``lk_csr_gather_rows`` with the item means as column bias: item.py:268-271).
         """
-        st = self._device_sims()
-        d = st["device"]
         if self.config.explicit and not batch.has_ratings:
             raise RuntimeError("explicit-feedback scorer must have ratings")
-        bias = st.get("means")
-        if bias is None and self.config.explicit and self.item_means is not None:
-            bias = st["means"] = torch.from_numpy(
-                np.asarray(self.item_means, dtype=np.float32)).to(d)
-        key = ("user_hits", id(batch.lookup))
-        user_hits = st.get(key)
-        if user_hits is None:
-            # hits of every training user: counts[item] summed over the user's row, on the device
-            mat = batch.lookup._device_matrix()["csr"]
-            cnt = torch.from_numpy(np.asarray(self.item_counts, dtype=np.int64)).to(d)
-            csum = torch.zeros(mat.indices.numel() + 1, dtype=torch.int64, device=d)
-            torch.cumsum(cnt[mat.indices.long()], 0, out=csum[1:])
-            ptr = mat.indptr.long()
-            user_hits = st[key] = (csum[ptr[1:]] - csum[ptr[:-1]]).cpu().numpy()
-        nums = batch.user_nums
-        hits = np.where(nums >= 0, user_hits[np.maximum(nums, 0)], 0).astype(np.int64)
-        order = np.argsort(-hits, kind="stable")  # heaviest queries first; undone below
-        sub = batch.subset(order)
-        hist = sub.csr(use_ratings=self.config.explicit, scale=1.0,
-                       col_bias=bias if self.config.explicit else None,
-                       with_values=self.config.explicit)
-        oi, osc = D.iknn_recommend(st["sims"], hist.indptr, hist.indices,
+        return batch.csr(use_ratings=self.config.explicit, scale=1.0,
+                         col_bias=self._device_means(), with_values=self.config.explicit)
+
+    # -- scoring ------------------------------------------------------------------------------
+    def _score(self, hist: D.DeviceCSR, tgt_ptr, tgt_nums):
+        "One ``lk_iknn_score_batch`` call: device (scores f32, counts int32), item means not added."
+        return D.iknn_score_batch(self._device_sims()["sims"], hist.indptr, hist.indices,
+                                  hist.values if self.config.explicit else None, tgt_ptr,
+                                  tgt_nums, self.config.max_nbrs, self.config.min_nbrs)
+
+    def score_batch(self, queries, item_lists) -> list[ItemList]:
+        "Score many (query, items) pairs in one kernel launch (item.py:231-295 per pair)."
+        hist = self._query_csr([RecQuery.create(q) for q in queries])
+        d = hist.indices.device
+        t_idx = [items.numbers(vocabulary=self.items, missing="negative") for items in item_lists]
+        t_ptr = np.zeros(len(t_idx) + 1, np.int64)
+        np.cumsum([len(ti) for ti in t_idx], out=t_ptr[1:])
+        tgt = np.concatenate(t_idx).astype(np.int32) if t_idx else np.zeros(0, np.int32)
+        s, c = self._score(hist, torch.from_numpy(t_ptr).to(d), torch.from_numpy(tgt).to(d))
+        s, c = s.cpu().numpy(), c.cpu().numpy()
+        out = []
+        for qi, items in enumerate(item_lists):
+            if hist.h_indptr[qi] == hist.h_indptr[qi + 1]:
+                out.append(ItemList(items, scores=np.nan))  # no history: item.py:238-245
+                continue
+            sc = s[t_ptr[qi]:t_ptr[qi + 1]].copy()
+            ti = t_idx[qi]
+            if self.config.explicit:
+                m = ti >= 0
+                sc[m] += self.item_means[ti[m]]  # item.py:282
+            out.append(ItemList(items, scores=sc, nbr_counts=c[t_ptr[qi]:t_ptr[qi + 1]]))
+        return out
+
+    def __call__(self, query, items: ItemList) -> ItemList:
+        return self.score_batch([query], [items])[0]
+
+    def score_history_batch(self, batch, tgt_ptr, tgt_nums):
+        """
+        ``score_batch`` for training histories by user number (``UserTrainingHistoryLookup.batch``):
+        the histories are cut out of the HBM-resident training matrix (:meth:`_batch_csr`), the
+        targets -- int64 offsets ``tgt_ptr`` [B + 1] and this scorer's item numbers ``tgt_nums``
+        (-1 = unknown), host arrays or device tensors -- are uploaded once, and one
+        ``lk_iknn_score_batch`` call scores everything.  Returns device (scores f32, counts
+        int32) over the targets: the kernel's output, item means NOT yet added back
+        (``lk_predict_merge`` does that).
+        """
+        d = self._device_sims()["device"]
+        if not isinstance(tgt_ptr, torch.Tensor):
+            tgt_ptr = torch.from_numpy(np.ascontiguousarray(tgt_ptr, dtype=np.int64)).to(d)
+        if not isinstance(tgt_nums, torch.Tensor):
+            tgt_nums = torch.from_numpy(np.ascontiguousarray(tgt_nums, dtype=np.int32)).to(d)
+        return self._score(self._batch_csr(batch), tgt_ptr, tgt_nums)
+
+    # -- top-n --------------------------------------------------------------------------------
+    accepts_history_batch = True  # recommend_batch takes a lkpy_amd.basic.HistoryBatch
+
+    def recommend_batch(self, queries, n: int, *, exclude_history: bool = True):
+        """
+        Top-``n`` lists for many queries at once -- what the ``recommender`` pipeline computes one
+        query at a time (src/lenskit/batch/_runner.py:283-308): candidates = every training item
+        minus the query's own (src/lenskit/basic/candidates.py:77-94), this scorer over them
+        (item.py:231-295, means added back: 282), ``TopNRanker`` (basic/topn.py:45-69).  One
+        ``lk_iknn_recommend`` call: scores bit-identical to the reference accumulator's, items
+        with fewer than ``min_nbrs`` neighbours never listed, queries without history get empty
+        lists (item.py:238-245: all-NaN scores).  ``queries``: a list of queries, or a
+        :class:`lkpy_amd.basic.HistoryBatch` (training histories by user number: nothing is done
+        per query on the host, and a query's hit count is a property of the USER, computed once
+        for every training user on the device).  Returns (item numbers [B x n] with -1 padding,
+        scores [B x n] with NaN padding), like ``ImplicitMFScorer.recommend_batch``.
+        """
+        from .basic import HistoryBatch
+
+        if isinstance(queries, HistoryBatch) and not (
+                queries.items is self.items or queries.items == self.items):
+            queries = queries.queries()  # (another item vocabulary: the per-query mapping)
+        if isinstance(queries, HistoryBatch):
+            batch = queries
+            nums = batch.user_nums
+            hits = np.where(nums >= 0, self._user_hits(batch.lookup)[np.maximum(nums, 0)], 0)
+            return self._recommend(lambda order: self._batch_csr(batch.subset(order)),
+                                   hits.astype(np.int64), n, exclude_history)
+        hist = self._query_csr([RecQuery.create(q) for q in queries])
+        return self._recommend(
+            lambda order: D.gather_rows(hist, order, with_values=self.config.explicit),
+            self._row_hits(hist), n, exclude_history)
+
+    def _recommend(self, cut, hits: np.ndarray, n: int, exclude_history: bool):
+        """
+        The tail of both ``recommend_batch`` front-ends: ``cut(order)`` gives the histories as a
+        device CSR with the heaviest query first (the launch is as long as its longest task
+        chain), one ``lk_iknn_recommend`` call scores them, and the lists are put back in the
+        caller's order on the device and downloaded at once.
+        """
+        order = np.argsort(-hits, kind="stable")
+        hist = cut(order)
+        oi, osc = D.iknn_recommend(self._device_sims()["sims"], hist.indptr, hist.indices,
                                    hist.values if self.config.explicit else None,
-                                   bias if self.config.explicit else None, self.config.max_nbrs,
+                                   self._device_means(), self.config.max_nbrs,
                                    self.config.min_nbrs, n, hits[order], exclude_history)
-        inv_h = np.empty_like(order)
-        inv_h[order] = np.arange(len(order))  # (the inverse permutation: O(n), no second sort)
-        inv = torch.from_numpy(inv_h).to(d)
-        both = torch.cat([oi.view(torch.float32), osc], dim=1)[inv]
-        host = D.to_host(both)
-        cols = oi.shape[1]
-        return host[:, :cols].view(np.int32), host[:, cols:]
+        inv = np.empty_like(order)
+        inv[order] = np.arange(len(order))  # (the inverse permutation: O(n), no second sort)
+        return D.lists_to_host(oi, osc, torch.from_numpy(inv).to(oi.device))
 
 
 # ---------------------------------------------------------------------------------------
@@ -354,11 +324,6 @@ class UserKNNScorer(Component):
     def is_trained(self):
         return hasattr(self, "user_ratings")
 
-    def __getstate__(self):
-        st = dict(self.__dict__)
-        st.pop("_dev", None)
-        return st
-
     def train(self, data: Dataset, options: TrainingOptions = TrainingOptions()):
         "user.py:122-168: centre by user mean (explicit), normalise rows, keep both matrices"
         import scipy.sparse.linalg as spla
@@ -382,18 +347,16 @@ class UserKNNScorer(Component):
         self.users = data.users
         self.user_means = means
         self.items = data.items
-        self.__dict__.pop("_dev", None)
 
     def _device_state(self):
-        st = getattr(self, "_dev", None)
-        if st is None:
+        def upload():
             from .matrix import csr_arrays
 
             d = D.device()
             uv = self.user_vectors
             uv.sort_indices()
             ro, ri, rv, shape = csr_arrays(self.user_ratings)
-            st = {
+            return {
                 "device": d,
                 "vectors": D.DeviceCSR.from_arrays(uv.indptr, uv.indices, uv.data, uv.shape, d),
                 "ratings": D.DeviceCSR(
@@ -402,8 +365,8 @@ class UserKNNScorer(Component):
                     None if rv is None else torch.from_numpy(np.array(rv, np.float32)).to(d),
                     shape, None),
             }
-            self._dev = st
-        return st
+
+        return self._device_cache("model", upload, self.user_vectors, self.user_ratings)
 
     def _user_data(self, query: RecQuery):
         "``_get_user_data`` (user.py:264-307): (user number | None, dense item vector, mean)"
@@ -513,11 +476,6 @@ class EASEScorer(Component):
     def is_trained(self):
         return hasattr(self, "weights")
 
-    def __getstate__(self):
-        st = dict(self.__dict__)
-        st.pop("_dev", None)
-        return st
-
     def train(self, data: Dataset, options: TrainingOptions = TrainingOptions()):
         solver = options.env_var("LK_EASE_SOLVER", None)
         if solver and solver not in ("torch", "scipy"):
@@ -550,16 +508,12 @@ class EASEScorer(Component):
             mat = inv.cpu().numpy()
         self.items = data.items
         self.weights = mat
-        self.__dict__.pop("_dev", None)
         assert self.weights.shape == (n_items, n_items)
 
     def _device_weights(self):
-        w = getattr(self, "_dev", None)
-        if w is None:
-            w = torch.from_numpy(np.ascontiguousarray(self.weights, dtype=np.float32)).to(
-                D.device())
-            self._dev = w
-        return w
+        return self._device_cache(
+            "weights", lambda: torch.from_numpy(
+                np.ascontiguousarray(self.weights, dtype=np.float32)).to(D.device()), self.weights)
 
     def score_batch(self, queries, item_lists) -> list[ItemList]:
         "Scores for a batch of (query, items) pairs; one device call for all of them."

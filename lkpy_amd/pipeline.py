@@ -66,6 +66,26 @@ class Component:
     def __repr__(self):
         return f"<{self.__class__.__name__} {self.dump_config()}>"
 
+    def _device_cache(self, key: str, build, *sources):
+        """
+        The device state kept under ``key``: ``build()``'s result, stored with the host objects it
+        was built from (``sources``) and built again once any of them is no longer the same
+        object -- after a retrain, say.  Never pickled (``__getstate__``).
+        """
+        cache = self.__dict__.setdefault("_dev", {})
+        entry = cache.get(key)
+        if entry is None or len(entry[0]) != len(sources) or \
+                any(a is not b for a, b in zip(entry[0], sources)):
+            cache.pop(key, None)
+            entry = None  # (the stale entry's device memory is released before the build)
+            entry = cache[key] = (sources, build())
+        return entry[1]
+
+    def __getstate__(self):
+        st = dict(self.__dict__)
+        st.pop("_dev", None)
+        return st
+
 
 def import_path_string(path: str):
     "``module.Class`` or ``module:Class`` -> object (``_types.py:284-309``)."

@@ -1,5 +1,5 @@
 // Microbenchmark: LDS float-atomic and slice-load rates at one wave per SIMD (the
-// occupancy of iknn_build_kernel).  hipcc --offload-arch=gfx950 -O3 -o /tmp/ub lds_atomic.hip
+// occupancy of iknn_build_kernel).  hipcc --offload-arch=gfx950 -O3 -o /tmp/ub lds_add_ub.hip
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
