@@ -115,7 +115,10 @@ int lk_gramian(const float *d_m, int64_t n, int32_t k, int32_t ld, float reg, fl
  *
  * A plan (row schedule: longest-first order, split of very long rows into
  * chunks, workspace layout) is built ONCE per matrix from the HOST copy of
- * indptr and reused for every epoch.
+ * indptr and reused for every epoch (csrc/als_plan.hip).  It also fixes which
+ * kernel takes which rows: the ALS environment knobs of INTEGRATION.md are read
+ * when the plan is created, not at every half-epoch.  It belongs to the device
+ * current at creation; lk_als_plan_destroy may be called with any device current.
  * ---------------------------------------------------------------------- */
 typedef struct lk_als_plan lk_als_plan;
 
@@ -188,7 +191,7 @@ int lk_als_plan_set_ctl(lk_als_plan *plan, lk_task_ctl *ctl);
 int64_t lk_als_plan_short_rows(const lk_als_plan *plan);
 /* rows the 16 x 16 ... 64 x 64 Woodbury systems take: <= 64 entries at padded k = 256 (rows of
  * 65 .. 128 entries additionally take a 128 x 128 system there unless LK_ALS_WB128=0); at padded
- * k = 128 <= 64 / 32 / 16 entries with LK_ALS_WB64_K128 = 64 (default) / 32 / 0 */
+ * k = 128 <= 64 / 32 / 16 entries with LK_ALS_WB64_K128 = 64 (default) / 32 / 0 at plan creation */
 int64_t lk_als_plan_woodbury_rows(const lk_als_plan *plan);
 int lk_als_plan_set_z(lk_als_plan *plan, const float *d_z);
 /* The same path with NOTHING computed on the caller's side: hand the plan a device buffer of

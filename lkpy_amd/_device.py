@@ -267,6 +267,21 @@ def als_order_mode(x) -> str:
     return x
 
 
+def use_woodbury(kp: int, solver: int, woodbury_rows: int, has_negative) -> bool:
+    """
+    Do the Woodbury kernels take the short rows of a half-epoch (csrc/als_wb.hip,
+    als_wb64_kernel)?  Padded k = 128 / 256, the exact solver, at least ``LK_ALS_WB_MIN_ROWS``
+    (default 4096; 0 disables) Woodbury rows -- enough to pay for Z = other @ OtOr^-1 -- and no
+    negative confidence value: the kernels take sqrt(v) of every increment, so with negative
+    values (use_ratings=True and negative ratings) they would flag rows the dense sposv path
+    still solves.  ``has_negative`` is called only when the rest holds (it costs a device scan).
+    The library's own host entry (lk_als_implicit_half_epoch_host_ctl) applies the same rule.
+    """
+    wb_min = int(os.environ.get("LK_ALS_WB_MIN_ROWS", "4096"))
+    return (64 < kp <= 256 and solver == _native.SOLVER_CHOLESKY and wb_min > 0
+            and woodbury_rows >= wb_min and not has_negative())
+
+
 class ALSPlan:
     "Row schedule + workspace of one CSR orientation (lk_als_plan)."
 
@@ -308,22 +323,14 @@ class ALSPlan:
         self.frob = torch.zeros(1, dtype=torch.float32, device=dev)
         self.solver = int(lib.lk_als_plan_solver(self._h))
         # rows with <= 64 entries at padded k > 64: Woodbury paths (csrc/als_wb.hip, als_wb64_kernel)
-        # when there are enough of them to pay for Z = other @ OtOr^-1 (LK_ALS_WB_MIN_ROWS; 0
-        # disables)
         self.short_rows = int(lib.lk_als_plan_short_rows(self._h))        # <= 16 entries
         # rows the Woodbury kernels take: <= 64 entries at padded k = 256 (<= 128 with the
         # 128 x 128 variant, counted by the caller); at k = 128 <= 16, or <= 32 / 64 with
         # LK_ALS_WB64_K128 (the library applies the same rule)
         self.woodbury_rows = int(lib.lk_als_plan_woodbury_rows(self._h))
-        wb_min = int(os.environ.get("LK_ALS_WB_MIN_ROWS", "4096"))
-        self.use_wb = (64 < self.kp <= 256 and self.solver == _native.SOLVER_CHOLESKY
-                       and wb_min > 0 and self.woodbury_rows >= wb_min)
         self._negative_values = None  # not scanned yet (one reduction + one host sync)
-        if self.use_wb and self.negative_values:
-            # the Woodbury kernels take sqrt(v) of every confidence increment: with negative
-            # values (use_ratings=True and negative ratings) they would flag rows the dense
-            # sposv path still solves -- such matrices keep the dense kernels for every row
-            self.use_wb = False
+        self.use_wb = use_woodbury(self.kp, self.solver, self.woodbury_rows,
+                                   lambda: self.negative_values)
         self._z = None
         self._z_leader = None  # another slice's plan whose Z this one uses (share_z_from)
         self._z_shared_set = False
@@ -567,11 +574,8 @@ class ALSPlanGroup:
                                    full_h_indptr=getattr(p0.csr, "full_h_indptr", None))
         self.short_rows = sum(p.short_rows for p in plans)
         self.woodbury_rows = sum(p.woodbury_rows for p in plans)
-        wb_min = int(os.environ.get("LK_ALS_WB_MIN_ROWS", "4096"))
-        # the Woodbury decision belongs to the half-epoch, not to a slice of it
-        use_wb = (64 < self.kp <= 256 and self.solver == _native.SOLVER_CHOLESKY and wb_min > 0
-                  and self.woodbury_rows >= wb_min)
-        if use_wb:
+
+        def has_negative() -> bool:
             # the slices are views into ONE values array (offsets are not rebased): scan each
             # distinct array once, whether or not a slice had reason to look on its own
             seen = {}
@@ -582,7 +586,10 @@ class ALSPlanGroup:
                     seen[key] = p.negative_values
                 else:
                     p._negative_values = seen[key]
-            use_wb = not any(seen.values())
+            return any(seen.values())
+
+        # the Woodbury decision belongs to the half-epoch, not to a slice of it
+        use_wb = use_woodbury(self.kp, self.solver, self.woodbury_rows, has_negative)
         for p in plans:
             p.use_wb = use_wb
         for p in plans[1:]:

@@ -602,13 +602,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
     store_chunk_slab<NT>(acc, yacc, slab, wave, lane);
 }
 
-// LK_BLK_CHUNK_DMA=0: the register-ring chunk kernel at k = 256 too (A/B timing)
-static bool chunk_dma_enabled()
-{
-    const char *e = getenv("LK_BLK_CHUNK_DMA");
-    return !(e && e[0] == '0');
-}
-
 // ---- one step of the blocked factorisation ---------------------------------------------------
 // `rot` (wave-uniform, 0..3): which wave of the workgroup plays "panel wave 0" for this row.  The
 // panel rows of a step are dealt to the waves in order (vtid = panel row), so at k = 128 only two
@@ -1301,39 +1294,6 @@ __global__ void als_blk_prep_otor_kernel(const float *__restrict__ otor, int ld_
     notor_p[idx] = v;
 }
 
-// LK_ALS_WB4=0: rows with <= 4 entries take the wave-per-row kernel too (A/B timing, tests)
-static bool als_wb8_enabled()
-{
-    const char *e = getenv("LK_ALS_WB8");
-    return !(e && e[0] == '0');
-}
-static bool als_wb4_enabled()
-{
-    const char *e = getenv("LK_ALS_WB4");
-    return !(e && e[0] == '0');
-}
-
-// LK_ALS_WB128=0: rows with 65 .. 128 entries stay on the dense kernel (A/B timing, tests)
-static bool als_wb128_enabled()
-{
-    const char *e = getenv("LK_ALS_WB128");
-    return !(e && e[0] == '0');
-}
-
-// LK_ALS_SIDE_STREAM=0: OtOr^-1 on the launch stream (A/B timing)
-static bool side_stream_enabled()
-{
-    const char *e = getenv("LK_ALS_SIDE_STREAM");
-    return !(e && e[0] == '0');
-}
-
-// LK_ALS_WB64=0: rows with 17 .. 64 entries stay on the dense kernel (A/B timing, tests)
-static bool als_wb64_enabled()
-{
-    const char *e = getenv("LK_ALS_WB64");
-    return !(e && e[0] == '0');
-}
-
 template <int NT, bool IS64, bool EXPL>
 static int launch_blk(const lk_als_plan *p, const void *indptr, const int32_t *indices,
                       const float *values, int64_t n_rows, int64_t n_cols, int k, float *this_,
@@ -1359,20 +1319,11 @@ static int launch_blk(const lk_als_plan *p, const void *indptr, const int32_t *i
     }
     hipLaunchKernelGGL(als_blk_prep_otor_kernel<NT>, dim3((C::KP * C::KP + 255) / 256), dim3(256),
                        0, st, otor, ld_otor, k, notor_p);
-    // first task of the Woodbury kernels: rows <= 16 entries always; 17 .. 64 at padded k = 256
-    // (17 .. 32 / 64 at k = 128 with LK_ALS_WB64_K128 = 32 / 64; LK_ALS_WB64=0: none)
-    int64_t n_wb64_first = p->t_short;
-    if (als_wb64_enabled()) {
-        if (NT == 16) {
-            n_wb64_first = p->t_mid;
-        } else {
-            const int lim = wb64_k128_limit();
-            n_wb64_first = lim >= 64 ? p->t_mid : (lim >= 32 ? p->t_32 : p->t_short);
-        }
-    }
+    // the task ranges of the Woodbury kernels are the plan's (als_plan.h): rows <= 16 entries
+    // always, 17 .. 64 (and 65 .. 128) at padded k = 256, 17 .. 32 / 64 at k = 128
     const bool prefix = p->dense_limit >= 0;  // CG hybrid: the chunked rows only, no Woodbury
     const bool own_z = !EXPL && p->d_zbuf != nullptr && !p->ctl &&
-                       (n_wb64_first < n_rows || p->z_for_others) && n_cols > 0 && !prefix;
+                       (p->t_wb64 < n_rows || p->z_for_others) && n_cols > 0 && !prefix;
     // OtOr^-1 to float64 accuracy (spd_inverse.hip; status[1] = its flag, tested by the Woodbury
     // kernels and by the fallback launch below): one workgroup for most of its time, so it goes
     // to the plan's side stream, under the chunk kernel, and the Z GEMM waits for it
@@ -1380,7 +1331,7 @@ static int launch_blk(const lk_als_plan *p, const void *indptr, const int32_t *i
     if (own_z) {
         float *ginv = reinterpret_cast<float *>(ws + p->off_ginv);
         hipStream_t sv = st;
-        if (side_stream_enabled() && p->n_chunks > 0) {
+        if (p->side_streams && p->n_chunks > 0) {
             if (!p->side) {
                 p->side = lk::side_stream_acquire();
                 LK_REQUIRE(p->side != nullptr, "als: no side stream");
@@ -1418,9 +1369,7 @@ static int launch_blk(const lk_als_plan *p, const void *indptr, const int32_t *i
         }
     }
     if (p->n_chunks > 0) {
-        bool dma = false;
-        if constexpr (NT == 16) dma = chunk_dma_enabled();
-        if (dma) {
+        if (p->chunk_dma) {
             if constexpr (NT == 16) {  // gathered rows staged through LDS (72 KiB, dynamic)
                 static PerDeviceOnce attr_once;
                 bool &attr_set = attr_once.flag();
@@ -1446,12 +1395,9 @@ static int launch_blk(const lk_als_plan *p, const void *indptr, const int32_t *i
         // run under the Woodbury kernels; the dense launch joins that stream anyway
         hipStream_t sg = st;
         if (p->hybrid && n_yhyb > 0 && p->n_groups > 0 && p->side_rhs) {
-            const char *s = getenv("LK_ALS_SIDE_STREAM");
-            if (!(s && s[0] == '0')) {
-                int rc = plan_rhs_wait_main(p, st);
-                if (rc != LK_OK) return rc;
-                sg = p->side_rhs;
-            }
+            int rc = plan_rhs_wait_main(p, st);
+            if (rc != LK_OK) return rc;
+            sg = p->side_rhs;
         }
         int rc = launch_slab_group_reduce(p, slabs, (size_t)C::SLAB, sg);
         if (rc != LK_OK) return rc;
@@ -1473,39 +1419,31 @@ static int launch_blk(const lk_als_plan *p, const void *indptr, const int32_t *i
         LK_HIP_CHECK(hipMemcpyAsync(status + 1, p->d_zflag_src, sizeof(int),
                                     hipMemcpyDeviceToDevice, st));
     const bool shared_z = !EXPL && p->d_zflag_src != nullptr && !own_z;
-    const bool use_wb = !EXPL && z != nullptr && !p->ctl && n_wb64_first < n_rows && !prefix;
-    // (17 .. 64 entries: only at padded k = 256 -- at k = 128 the 64 x 64 system costs as much as
-    // the dense solve of this file, measured on the ML-25M shape)
-    // (65 .. 128 entries at padded k = 256: the same identity with a 128 x 128 system,
-    // als_wb128_kernel; LK_ALS_WB128=0 keeps those rows on the dense kernel)
-    const bool wb128 = NT == 16 && als_wb64_enabled() && als_wb128_enabled() && use_wb &&
-                       p->t_128 < p->t_mid;
-    const int64_t n_dense =
-        prefix ? (p->dense_limit < n_rows ? p->dense_limit : n_rows)
-               : (use_wb ? (wb128 ? p->t_128 : n_wb64_first) : n_rows);
+    const bool use_wb = !EXPL && z != nullptr && !p->ctl && p->t_wb64 < n_rows && !prefix;
+    const int64_t n_dense = prefix ? (p->dense_limit < n_rows ? p->dense_limit : n_rows)
+                                   : (use_wb ? p->t_wb128 : n_rows);
     if (use_wb) {
-        // <= 4 entries (and empty rows): four rows per wave; 5 .. 16: a wave per row
-        // (5 .. 8 entries: two rows per wave, LK_ALS_WB8=0: a wave per row)
-        const int64_t t4 = als_wb4_enabled() ? p->t_4 : n_rows;
-        const int64_t t8 = als_wb8_enabled() ? p->t_8 : t4;
-        int rc = als_wb_launch(p, indptr, IS64 ? 1 : 0, indices, values, p->t_short, t8, this_,
-                               other, z, row_delta, status, st);
+        // <= 4 entries (and empty rows): four rows per wave; 5 .. 8: two rows per wave;
+        // 9 .. 16: a wave per row
+        int rc = als_wb_launch(p, indptr, IS64 ? 1 : 0, indices, values, p->t_short, p->t_wb8,
+                               this_, other, z, row_delta, status, st);
         if (rc != LK_OK) return rc;
-        rc = als_wb4_launch(p, indptr, IS64 ? 1 : 0, indices, values, t8, t4, this_, other, z,
-                            row_delta, status, st, 8);
+        rc = als_wb4_launch(p, indptr, IS64 ? 1 : 0, indices, values, p->t_wb8, p->t_wb4, this_,
+                            other, z, row_delta, status, st, 8);
         if (rc != LK_OK) return rc;
-        rc = als_wb4_launch(p, indptr, IS64 ? 1 : 0, indices, values, t4, n_rows, this_, other,
-                            z, row_delta, status, st, 4);
+        rc = als_wb4_launch(p, indptr, IS64 ? 1 : 0, indices, values, p->t_wb4, n_rows, this_,
+                            other, z, row_delta, status, st, 4);
         if (rc != LK_OK) return rc;
         // rows with 17 .. 64 entries: the same identity with a 64 x 64 system
-        rc = als_wb64_launch(p, indptr, IS64 ? 1 : 0, indices, values, n_wb64_first, p->t_short,
+        rc = als_wb64_launch(p, indptr, IS64 ? 1 : 0, indices, values, p->t_wb64, p->t_short,
                              this_, other, z, row_delta, status, st);
         if (rc != LK_OK) return rc;
-        if (wb128) {
-            const int64_t nr = p->t_mid - p->t_128;
+        // rows with 65 .. 128 entries (padded k = 256): a 128 x 128 system, als_wb128_kernel
+        if (p->t_wb128 < p->t_wb64) {
+            const int64_t nr = p->t_wb64 - p->t_wb128;
             hipLaunchKernelGGL((als_wb128_kernel<IS64>), dim3((unsigned)nr), dim3(256), 0, st,
                                static_cast<const IT *>(indptr), indices, values,
-                               p->d_order + p->t_128, nr, other, z, this_, row_delta, status);
+                               p->d_order + p->t_wb128, nr, other, z, this_, row_delta, status);
         }
         if (own_z || shared_z)  // no-op unless spd_inverse raised its flag
             hipLaunchKernelGGL((als_blk_fallback_kernel<NT, IS64>), dim3(1024), dim3(256), 0, st,

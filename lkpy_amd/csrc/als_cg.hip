@@ -512,32 +512,23 @@ static int launch_cg(const lk_als_plan *p, const void *indptr, const int32_t *in
     return launch_delta_reduce(row_delta, n_rows, partial, out_frob, st);
 }
 
-// LK_ALS_CG_HYBRID (test hook / A-B knob): 0 = CG for every row; 1 = the chunked rows (more than
-// LK_ALS_LONG_ROW entries) go to the exact kernels; default 2 = every row longer than the CG
-// kernel keeps in registers does.
-static int cg_hybrid_mode()
-{
-    const char *e = getenv("LK_ALS_CG_HYBRID");
-    return (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 2;
-}
-
 int als_cg_half_epoch(const lk_als_plan *p, const void *indptr, int is64, const int32_t *indices,
                       const float *values, int64_t n_rows, int k, float *this_, int ld_this,
                       const float *other, int ld_other, const float *otor, int ld_otor, char *ws,
                       float *out_frob, hipStream_t st)
 {
     // Matrix-free CG pays for itself where a row's gathered factor rows stay in registers over
-    // the iterations: 256 / 128 / 64 entries at padded k = 64 / 128 / 256 (t_cg: 85 % of the
+    // the iterations: 256 / 128 / 64 entries at padded k = 64 / 128 / 256 (85 % of the
     // ML-25M user rows, 96 % of its item rows, 40 % of the entries at k = 64).  Longer rows would
     // gather their tail again in EVERY iteration (measured at k = 64: 62 ms per epoch with CG on
     // every row -- one workgroup iterating over the 81 491-entry item is 2.5 ms per iteration of
     // serial gather latency; 29.6 ms with only the chunked rows solved exactly),
     // while the exact kernels form such a row's normal matrix once, on the matrix cores.  So the
-    // first t_cg tasks of the longest-first order go to the exact kernels, the rest to CG.
-    // (Not with a task-control block: its progress accounting is per launch.)
+    // first cg_exact tasks of the longest-first order (the plan's, LK_ALS_CG_HYBRID) go to the
+    // exact kernels, the rest to CG.  (Not with a task-control block: its progress accounting is
+    // per launch.)
     int64_t t_begin = 0;
-    const int mode = p->ctl ? 0 : cg_hybrid_mode();
-    const int64_t t_exact = mode == 2 ? p->t_cg : (mode == 1 ? p->n_long : 0);
+    const int64_t t_exact = p->ctl ? 0 : p->cg_exact;
     if (t_exact > 0) {
         p->dense_limit = t_exact;
         const int rc =
@@ -545,7 +536,7 @@ int als_cg_half_epoch(const lk_als_plan *p, const void *indptr, int is64, const 
                                             other, otor, ld_otor, ws, out_frob, st, false, 0.f)
                        : als_chol_half_epoch(p, indptr, is64, indices, values, n_rows, k, this_,
                                              ld_this, other, ld_other, otor, ld_otor, ws, out_frob,
-                                             st);
+                                             st, false, 0.f);
         p->dense_limit = -1;
         if (rc != LK_OK) return rc;
         t_begin = t_exact;

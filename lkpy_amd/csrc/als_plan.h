@@ -1,9 +1,8 @@
-// als_plan.h -- the ALS plan object shared by the Cholesky and CG half-epoch kernels.
+// als_plan.h -- the ALS plan object shared by the Cholesky and CG half-epoch kernels.  Built,
+// queried and dispatched by als_plan.hip; the kernel files launch from its fields.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#include <stdlib.h>
 
 #define LK_DELTA_BLOCKS 256
 
@@ -12,11 +11,6 @@
 #ifndef LK_ALS_WB64_K128_DEFAULT
 #define LK_ALS_WB64_K128_DEFAULT 64
 #endif
-static inline int wb64_k128_limit()
-{
-    const char *e = getenv("LK_ALS_WB64_K128");
-    return e ? atoi(e) : LK_ALS_WB64_K128_DEFAULT;
-}
 
 #ifndef LK_ALS_CHUNK
 #define LK_ALS_CHUNK 1024  // CSR entries per chunk of a long row
@@ -44,15 +38,23 @@ struct lk_als_plan {
     // padded k > 64 the implicit model solves them through the Woodbury kernel (als_wb.hip)
     // when the caller supplied Z = other * OtOr^-1 for this half-epoch (lk_als_plan_set_z)
     int64_t t_short = 0;
-    int64_t t_mid = 0;  // rows with 17 .. 64 entries are [t_mid, t_short): als_wb64_kernel
-    int64_t t_4 = 0;    // rows with <= 4 entries are [t_4, n_rows): als_wb4_kernel, four per wave
-    int64_t t_8 = 0;    // rows with 5 .. 8 entries are [t_8, t_4): als_wb4_kernel<.., 8>, two per wave
-    int64_t t_32 = 0;   // rows with 17 .. 32 entries are [t_32, t_short): the 32 x 32 system of als_wb64_kernel (KP = 128)
-    int64_t t_128 = 0;  // rows with 65 .. 128 entries are [t_128, t_mid): als_wb128_kernel (KP = 256)
-    // rows [t_cg, n_rows) have at most 16384 / KP entries (256 / 128 / 64 at padded k = 64 /
-    // 128 / 256): what the CG kernel keeps in registers over its iterations (als_cg.hip)
-    int64_t t_cg = 0;
+    // The task ranges of the Woodbury kernels (padded k = 128 / 256), fixed at creation from the
+    // row lengths and the LK_ALS_WB* switches -- a range that is switched off is empty and its
+    // rows go to the next one up (the dense kernel last):
+    //   [t_wb128, t_wb64)  65 .. 128 entries (KP = 256): als_wb128_kernel
+    //   [t_wb64, t_short)  17 .. 64 entries (KP = 128: up to LK_ALS_WB64_K128): als_wb64_kernel
+    //   [t_short, t_wb8)   9 .. 16 entries: als_wb_kernel, a wave per row
+    //   [t_wb8, t_wb4)     5 .. 8 entries: als_wb4_kernel<.., 8>, two per wave
+    //   [t_wb4, n_rows)    <= 4 entries: als_wb4_kernel, four per wave
+    int64_t t_wb128 = 0, t_wb64 = 0, t_wb8 = 0, t_wb4 = 0;
+    // lk_als_plan_woodbury_rows: as LK_ALS_WB64_K128 says (the other switches do not count)
+    int64_t wb_rows = 0;
+    // CG plans: the first cg_exact tasks go to the exact kernels (LK_ALS_CG_HYBRID, als_cg.hip)
+    int64_t cg_exact = 0;
     int64_t t_cg1 = 0;  // rows [t_cg1, n_rows): at most 4096 / KP entries -- one wave's registers
+    bool side_streams = true;  // LK_ALS_SIDE_STREAM: a half-epoch may use the side streams below
+    bool chunk_dma = false;    // padded k = 256: the LDS-staged chunk kernel (LK_BLK_CHUNK_DMA)
+    int device = -1;           // the device the plan's buffers and streams belong to
     mutable const float *d_z = nullptr;
     // ... or a caller-owned [n_cols x KP] buffer the LIBRARY fills with Z at every implicit
     // half-epoch (lk_als_plan_set_z_workspace): OtOr^-1 by spd_inverse.hip, Z by the scoring GEMM
@@ -133,11 +135,12 @@ struct lk_als_plan {
 };
 
 namespace lk {
-// exact half-epoch for padded k <= 64: one wave per row (als_chol.hip; implicit model)
+// exact half-epoch for padded k <= 64: one wave per row (als_chol.hip)
+size_t als_chol_slab_floats(int NT);
 int als_chol_half_epoch(const lk_als_plan *p, const void *indptr, int is64, const int32_t *indices,
                         const float *values, int64_t n_rows, int k, float *this_, int ld_this,
                         const float *other, int ld_other, const float *otor, int ld_otor, char *ws,
-                        float *out_frob, hipStream_t st);
+                        float *out_frob, hipStream_t st, bool expl, float reg);
 // exact half-epoch for padded k = 128 / 256: one workgroup per row (als_blk.hip)
 size_t als_blk_slab_floats(int NT);
 int als_blk_half_epoch(const lk_als_plan *p, const void *indptr, int is64, const int32_t *indices,
@@ -151,6 +154,11 @@ int als_big_half_epoch(const lk_als_plan *p, const void *indptr, int is64, const
                        const float *values, int64_t n_rows, int k, float *this_,
                        const float *other, const float *otor, int ld_otor, char *ws,
                        float *out_frob, hipStream_t st, bool expl, float reg);
+// the CG option, padded k = 64 / 128 / 256; its long rows go to the exact kernels (als_cg.hip)
+int als_cg_half_epoch(const lk_als_plan *p, const void *indptr, int is64, const int32_t *indices,
+                      const float *values, int64_t n_rows, int k, float *this_, int ld_this,
+                      const float *other, int ld_other, const float *otor, int ld_otor, char *ws,
+                      float *out_frob, hipStream_t st);
 size_t gramian_big_workspace_bytes(int KP);
 int gramian_big(const float *m, int64_t n, int k, int KP, float reg, float *out, int ld_out,
                 float *ws, hipStream_t st);
@@ -183,7 +191,8 @@ int launch_rhs_reference(const lk_als_plan *p, const void *indptr, int is64,
                          int64_t n_tasks, const float *other, bool expl, float *y_out,
                          hipStream_t st);
 // the plan's rhs side stream (created on first use), forked behind what `st` holds now
-// (LK_ALS_SIDE_STREAM=0: `st` itself); plan_join_rhs makes `st` wait for what it holds then
+// (side_streams off: `st` itself); plan_join_rhs makes `st` wait for what it holds then
+// (als_plan.hip)
 int plan_fork_rhs(const lk_als_plan *p, hipStream_t st, hipStream_t *side);
 int plan_join_rhs(const lk_als_plan *p, hipStream_t st);
 // the rhs side stream waits for what `st` holds now (a second fork point inside the half-epoch)

@@ -235,45 +235,6 @@ __global__ __launch_bounds__((RC_NP + 1) * 64) void als_rhs_chain_kernel(
     } while (s0 < nst);
 }
 
-static bool rhs_side_enabled()
-{
-    const char *e = getenv("LK_ALS_SIDE_STREAM");
-    return !(e && e[0] == '0');
-}
-
-int plan_fork_rhs(const lk_als_plan *p, hipStream_t st, hipStream_t *side)
-{
-    *side = st;
-    if (!rhs_side_enabled()) return LK_OK;
-    if (!p->side_rhs) {
-        p->side_rhs = lk::side_stream_acquire();
-        LK_REQUIRE(p->side_rhs != nullptr, "als: no side stream");
-        LK_HIP_CHECK(hipEventCreateWithFlags(&p->ev_fork_rhs, hipEventDisableTiming));
-        LK_HIP_CHECK(hipEventCreateWithFlags(&p->ev_join_rhs, hipEventDisableTiming));
-        LK_HIP_CHECK(hipEventCreateWithFlags(&p->ev_mid_rhs, hipEventDisableTiming));
-    }
-    LK_HIP_CHECK(hipEventRecord(p->ev_fork_rhs, st));
-    LK_HIP_CHECK(hipStreamWaitEvent(p->side_rhs, p->ev_fork_rhs, 0));
-    *side = p->side_rhs;
-    return LK_OK;
-}
-
-int plan_rhs_wait_main(const lk_als_plan *p, hipStream_t st)
-{
-    if (!rhs_side_enabled() || !p->side_rhs) return LK_OK;
-    LK_HIP_CHECK(hipEventRecord(p->ev_mid_rhs, st));
-    LK_HIP_CHECK(hipStreamWaitEvent(p->side_rhs, p->ev_mid_rhs, 0));
-    return LK_OK;
-}
-
-int plan_join_rhs(const lk_als_plan *p, hipStream_t st)
-{
-    if (!rhs_side_enabled() || !p->side_rhs) return LK_OK;
-    LK_HIP_CHECK(hipEventRecord(p->ev_join_rhs, p->side_rhs));
-    LK_HIP_CHECK(hipStreamWaitEvent(st, p->ev_join_rhs, 0));
-    return LK_OK;
-}
-
 // tasks [0, n_tasks) of `order` (order == nullptr: rows 0 .. n_tasks); y_out[t] <- row order[t]
 int launch_rhs_reference(const lk_als_plan *p, const void *indptr, int is64,
                          const int32_t *indices, const float *values, const int32_t *order,
@@ -297,13 +258,3 @@ int launch_rhs_reference(const lk_als_plan *p, const void *indptr, int is64,
 }
 
 }  // namespace lk
-
-extern "C" int lk_als_plan_set_rhs_workspace(lk_als_plan *p, float *d_y)
-{
-    LK_REQUIRE(p != nullptr, "lk_als_plan_set_rhs_workspace: null plan");
-    LK_REQUIRE(d_y == nullptr || p->solver == LK_SOLVER_CHOLESKY,
-               "lk_als_plan_set_rhs_workspace: the reference-order right-hand side belongs to the "
-               "exact solver (the CG option has no reference to reproduce)");
-    p->d_yref = d_y;
-    return LK_OK;
-}

@@ -72,3 +72,45 @@ def test_explicit_bit_identical(gpu, rng, monkeypatch):
         got[mode] = D.to_host_unpadded(d_this, k)
     assert np.isfinite(got["1"]).all()
     assert np.array_equal(got["1"], got["0"])
+
+
+def test_plan_keeps_its_kernel_choice(gpu, rng, monkeypatch):
+    """The plan settles at creation which kernel takes which rows (csrc/als_plan.hip): the chunk
+    kernel its 1024-entry work units were cut for, the 64 x 64 Woodbury range, the side streams.
+    Switches changed after it exists leave its half-epoch bit-identical."""
+    from lkpy_amd import _device as D
+    from lkpy_amd import _native
+
+    k, n_cols = 256, 30000
+    lens = np.concatenate([[n for n in LENS if n > 2048], rng.integers(0, 65, 3000)])
+    indptr = np.zeros(len(lens) + 1, np.int64)
+    np.cumsum(lens, out=indptr[1:])
+    indices = np.concatenate(
+        [np.sort(rng.choice(n_cols, n, replace=False)) for n in lens]).astype(np.int32)
+    values = rng.integers(1, 6, indptr[-1]).astype(np.float32)
+    mat = sps.csr_array((values, indices, indptr), shape=(len(lens), n_cols))
+    other = (rng.standard_normal((n_cols, k)) * 0.05).astype(np.float32)
+    csr = D.DeviceCSR.from_arrays(mat.indptr.astype(np.int32), mat.indices, mat.data, mat.shape, gpu)
+    d_other = D.to_device_padded(other, gpu)
+    d_otor = D.Gramian(k, gpu)(d_other, 0.1)
+    switches = ("LK_BLK_CHUNK_DMA", "LK_ALS_WB64", "LK_ALS_SIDE_STREAM")
+    for name in switches:
+        monkeypatch.delenv(name, raising=False)
+    monkeypatch.setenv("LK_ALS_WB_MIN_ROWS", "1")
+
+    def run(switch_off_after_creation):
+        plan = D.ALSPlan(csr, k, _native.SOLVER_CHOLESKY)
+        assert plan.use_wb and plan.order_mode == "auto" and plan.long_rows() == (lens > 2048).sum()
+        if switch_off_after_creation:
+            for name in switches:
+                monkeypatch.setenv(name, "0")
+        d_this = D.to_device_padded(np.zeros((mat.shape[0], k), np.float32), gpu)
+        plan.half_epoch(d_this, d_other, d_otor)
+        plan.check_status()
+        for name in switches:
+            monkeypatch.delenv(name, raising=False)
+        return D.to_host_unpadded(d_this, k)
+
+    want = run(False)
+    assert np.isfinite(want).all()
+    assert np.array_equal(run(True), want)

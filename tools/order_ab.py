@@ -52,8 +52,8 @@ def main():
     Q0 = lko.als_initial_params(rng, ui.shape[1], k)
     P0 = lko.als_initial_params(rng, ui.shape[0], k)
 
-    # a variant: mode[:ENV=VALUE[:ENV=VALUE ...]] (environment knobs the library reads per launch
-    # or per plan, e.g. auto:LK_ALS_SIDE_STREAM=0)
+    # a variant: mode[:ENV=VALUE[:ENV=VALUE ...]] (environment knobs the library reads when a plan
+    # is created -- set before the engine below builds its plans -- e.g. auto:LK_ALS_SIDE_STREAM=0)
     variants = []
     for m in args.modes.split(","):
         mode, *envs = m.split(":")
