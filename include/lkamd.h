@@ -591,6 +591,56 @@ int lk_ease_score_batch(const int64_t *d_hist_ptr, const int32_t *d_hist_items,
                         int64_t n_queries, const float *d_weights, int64_t n_items, int64_t ld_w,
                         float *d_out, int64_t ld_out, void *stream);
 
+/* ------------------------------------------------------------------------
+ * SLIM / fsSLIM (`SLIMScorer`, src/lenskit/knn/slim.py:53-152; csrc/slim.hip).
+ * lk_slim_train_*: replaces `_accel.slim.train_slim(ui_matrix, iu_matrix, l1_reg, l2_reg,
+ *   max_iters, max_nbrs)` (src/accel/slim/mod.rs:58-301): one elastic-net regression per target
+ *   item by cyclic coordinate descent with soft thresholding, on the STRUCTURE of the users x
+ *   items matrix `ui` and its transpose `iu` (offsets i32 / i64, both the same; no row may name a
+ *   column twice).  Learns the rows of the TRANSPOSED weight matrix for the target items
+ *   d_columns[0 .. n_cols) (NULL: every item, n_cols = n_items) -- rows in the order of the list,
+ *   columns ascending, int64 offsets.  The result is the reference's bit for bit: the active list
+ *   in first-encounter order, the fsSLIM cut (max_nbrs > 0: the max_nbrs largest cosines, float64
+ *   key, stable) and its sorted order as the descent order, every coordinate's update a
+ *   sequential float32 sum over the item's users in stored order, the stop at max |diff| <= 1e-3
+ *   or after max_iters rounds, weights >= 1e-12 kept.  d_item_sqrt [n_items] = sqrt((double)
+ *   user count of the item), made by the caller (NumPy's sqrt is correctly rounded).
+ *   Two-phase like lk_iknn_build_*: _count trains the columns into a staging area of the
+ *   workspace (lk_slim_train_workspace_bytes: n_cols x min(max_nbrs, n_items) pairs plus one
+ *   slot per resident wave; cut long column lists into several calls), fills d_out_indptr
+ *   [n_cols + 1] and returns the total through *h_total_nnz (blocking); _fill compacts the staging
+ *   area into d_out_indices / d_out_values (same n_users, n_items, n_cols, max_nbrs, workspace).
+ *   `ctl` (may be NULL): cancel / progress in columns; a cancelled _count returns LK_E_CANCELLED.
+ *   h_stats (may be NULL) [3]: descent rounds, coordinate updates and residual entries summed by
+ *   those updates, over all columns of the call.
+ * lk_slim_score_batch: `x @ self.weights` (slim.py:139-144) for a batch of queries: out[q][c] =
+ *   sum over the history items of query q, in history order, of weights[item][c] (the stored
+ *   `weights` CSR, int64 offsets; a repeated history item counts twice, items outside
+ *   [0, n_items) are skipped), every other cell 0.  mark_history prepares the panel for
+ *   lk_argtopn: bit 0 turns the query's own items into NaN, bit 1 the whole row of a query whose
+ *   history is empty.
+ * lk_take_scores: out[r][k] = scores[r][idx[r][k]] (NaN where idx is negative): the scores of
+ *   the lists lk_argtopn selected.
+ * ---------------------------------------------------------------------- */
+size_t lk_slim_train_workspace_bytes(int64_t n_users, int64_t n_items, int64_t n_cols,
+                                     int64_t max_nbrs);
+int lk_slim_train_count(const void *d_ui_indptr, const int32_t *d_ui_indices,
+                        const void *d_iu_indptr, const int32_t *d_iu_indices, int indptr_is_64,
+                        int64_t n_users, int64_t n_items, const double *d_item_sqrt, float l1_reg,
+                        float l2_reg, int32_t max_iters, int64_t max_nbrs,
+                        const int32_t *d_columns, int64_t n_cols, lk_task_ctl *ctl, void *d_ws,
+                        int64_t *d_out_indptr, int64_t *h_total_nnz, int64_t *h_stats,
+                        void *stream);
+int lk_slim_train_fill(int64_t n_users, int64_t n_items, int64_t n_cols, int64_t max_nbrs,
+                       const void *d_ws, const int64_t *d_out_indptr, int32_t *d_out_indices,
+                       float *d_out_values, void *stream);
+int lk_slim_score_batch(const int64_t *d_hist_ptr, const int32_t *d_hist_items, int64_t n_queries,
+                        const int64_t *d_w_indptr, const int32_t *d_w_indices,
+                        const float *d_w_values, int64_t n_items, float *d_out, int64_t ld_out,
+                        int mark_history, void *stream);
+int lk_take_scores(const float *d_scores, int64_t n_rows, int64_t row_len, const int32_t *d_idx,
+                   int64_t n, float *d_out, void *stream);
+
 /* Batched fold-in (new-user embeddings) -- `ImplicitMFScorer.new_user_embedding` /
  * `_train_new_row` (src/lenskit/als/_implicit.py:77-130) -- is the SAME algebra as one ALS
  * row with OtOr = Q^T Q + user_reg I: build a plan over the histories' CSR offsets and call

@@ -4,4 +4,4 @@ Function seam: drop-in stand-ins for the functions of the reference's native mod
 (SURVEY.md section 8b).  Host buffers in, host buffers out; the arithmetic runs in the HIP
 kernels behind ``lkpy_amd/_lkamd.so`` -- there is no CPU fallback.
 """
-from . import als, data, knn  # noqa: F401
+from . import als, data, knn, slim  # noqa: F401

@@ -987,6 +987,152 @@ def ease_score_batch(hist_ptr: torch.Tensor, hist_items: torch.Tensor,
     return out
 
 
+SLIM_STAGE_BYTES = 2 << 30  # staging area of one lk_slim_train_count call (column batches)
+
+
+def slim_train(ui: DeviceCSR, iu: DeviceCSR, l1: float, l2: float, max_iters: int,
+               max_nbrs: int | None, columns=None, ctl: "TaskCtl | None" = None,
+               stats: dict | None = None, on_batch=None) -> DeviceCSR:
+    """
+    SLIM / fsSLIM training (lk_slim_train_count / _fill; ``train_slim``,
+    src/accel/slim/mod.rs:58-301): ``ui`` users x items and ``iu`` items x users, structure only
+    (values are ignored).  Returns the rows of the TRANSPOSED weight matrix for the target items
+    ``columns`` (host integers; None = every item) as a device CSR with int64 offsets, rows in
+    the order of the list (item order for None), columns ascending -- the reference's rows bit
+    for bit.  Long column
+    lists go through in batches whose staging area stays under ``SLIM_STAGE_BYTES``;
+    ``on_batch(columns done)`` is called after each.  ``stats``: receives the summed
+    ``rounds``, ``coord_updates`` and ``resid_entries`` of the descent.
+    """
+    lib = _native.require_gpu()
+    n_users, n_items = ui.shape
+    assert iu.shape == (n_items, n_users)
+    assert ui.h_indptr.dtype == iu.h_indptr.dtype
+    if int(max_iters) < 1:
+        raise ValueError("max_iters must be positive")
+    dev = ui.indices.device
+    is64 = 1 if ui.h_indptr.dtype == np.int64 else 0
+    mn = 0 if max_nbrs is None else int(max_nbrs)
+    if max_nbrs is not None and mn < 1:
+        raise ValueError("max_nbrs must be positive")
+    if columns is None:
+        cols = None
+        n_cols = n_items
+    else:
+        cols = np.ascontiguousarray(columns, dtype=np.int32)
+        if cols.ndim != 1 or (len(cols) and (cols.min() < 0 or cols.max() >= n_items)):
+            raise ValueError("slim_train: column out of range")
+        n_cols = len(cols)
+    if n_cols == 0:
+        return DeviceCSR(torch.zeros(1, dtype=torch.int64, device=dev),
+                         torch.empty(0, dtype=torch.int32, device=dev),
+                         torch.empty(0, dtype=torch.float32, device=dev), (0, n_items), None)
+    # sqrt(n_j) as the reference forms it, (n as f64).sqrt(): NumPy's sqrt is correctly rounded
+    sq = torch.from_numpy(np.sqrt(np.diff(iu.h_indptr).astype(np.float64))).to(dev)
+    cap = min(mn, n_items) if mn else n_items
+    step = max(1, SLIM_STAGE_BYTES // (8 * max(cap, 1)))
+    order = None
+    if cols is None and n_items > 1:
+        # every column: the most-rated targets first -- their columns are the long ones, and the
+        # waves draw columns in list order -- and the rows put back in item order at the end
+        order = np.argsort(-np.diff(iu.h_indptr), kind="stable").astype(np.int32)
+        cols = order
+    tot = {"rounds": 0, "coord_updates": 0, "resid_entries": 0}
+    parts = []
+    for lo in range(0, max(n_cols, 1), step):
+        hi = min(n_cols, lo + step)
+        nb = hi - lo
+        d_cols = None if cols is None else torch.from_numpy(cols[lo:hi]).to(dev)
+        ws = torch.empty(lib.lk_slim_train_workspace_bytes(n_users, n_items, nb, mn),
+                         dtype=torch.uint8, device=dev)
+        out_ptr = torch.empty(nb + 1, dtype=torch.int64, device=dev)
+        total = ctypes.c_int64(0)
+        st = (ctypes.c_int64 * 3)()
+        check(
+            lib.lk_slim_train_count(
+                _ptr(ui.indptr), _ptr(ui.indices), _ptr(iu.indptr), _ptr(iu.indices), is64,
+                n_users, n_items, _ptr(sq), float(np.float32(l1)), float(np.float32(l2)),
+                int(max_iters), mn, _ptr(d_cols), nb, None if ctl is None else ctl._h, _ptr(ws),
+                _ptr(out_ptr), ctypes.byref(total), st, _stream()
+            ),
+            "lk_slim_train_count",
+        )  # fmt: skip
+        nnz = int(total.value)
+        out_idx = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)[:nnz]
+        out_val = torch.empty(max(nnz, 1), dtype=torch.float32, device=dev)[:nnz]
+        if nnz:
+            check(
+                lib.lk_slim_train_fill(n_users, n_items, nb, mn, _ptr(ws), _ptr(out_ptr),
+                                       _ptr(out_idx), _ptr(out_val), _stream()),
+                "lk_slim_train_fill",
+            )
+        torch.cuda.current_stream().synchronize()
+        del ws
+        for k, v in zip(tot, st):
+            tot[k] += int(v)
+        parts.append((out_ptr, out_idx, out_val))
+        if on_batch is not None:
+            on_batch(hi)
+    if stats is not None:
+        stats.update(tot)
+    if len(parts) == 1:
+        ptr, idx, val = parts[0]
+    else:  # (plumbing: the batches' rows one after the other)
+        base, ptrs = 0, [parts[0][0][:1]]
+        for p, _i, _v in parts:
+            ptrs.append(p[1:] + base)
+            base += int(p[-1])
+        ptr = torch.cat(ptrs)
+        idx = torch.cat([p[1] for p in parts])
+        val = torch.cat([p[2] for p in parts])
+    out = DeviceCSR(ptr, idx, val, (n_cols, n_items), None)
+    if order is not None:
+        out.h_indptr = ptr.cpu().numpy()
+        inv = np.empty_like(order)
+        inv[order] = np.arange(n_items, dtype=np.int32)
+        out = gather_rows(out, inv)
+        out.h_indptr = None
+    return out
+
+
+def slim_score_batch(hist_ptr: torch.Tensor, hist_items: torch.Tensor, weights: DeviceCSR,
+                     rows: tuple[int, int] | None = None, strike_history: bool = False,
+                     nan_empty: bool = False) -> torch.Tensor:
+    """
+    ``x @ weights`` per query (lk_slim_score_batch; src/lenskit/knn/slim.py:139-144): the history
+    items' rows of the stored ``weights`` CSR (int64 offsets) added in history order into a dense
+    [B x n_items] f32 panel; unreached items are 0.  ``rows = (lo, hi)``: those queries only.
+    The panel as ``argtopn`` wants it: ``strike_history`` makes the query's own items NaN,
+    ``nan_empty`` the whole row of a query with an empty history.
+    """
+    lib = _native.require_gpu()
+    n = int(weights.shape[1])
+    lo, hi = (0, int(hist_ptr.shape[0]) - 1) if rows is None else (int(rows[0]), int(rows[1]))
+    assert 0 <= lo <= hi < int(hist_ptr.shape[0])
+    assert hist_ptr.dtype == torch.int64 and hist_items.dtype == torch.int32
+    assert weights.indptr.dtype == torch.int64
+    out = torch.empty((hi - lo, n), dtype=torch.float32, device=weights.indices.device)
+    check(
+        lib.lk_slim_score_batch(_ptr(hist_ptr[lo:]), _ptr(hist_items), hi - lo,
+                                _ptr(weights.indptr), _ptr(weights.indices), _ptr(weights.values),
+                                n, _ptr(out), n, (1 if strike_history else 0) |
+                                (2 if nan_empty else 0), _stream()),
+        "lk_slim_score_batch",
+    )
+    return out
+
+
+def take_scores(scores: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    "The scores of the lists ``argtopn`` selected: [B x n] f32, NaN under -1 (lk_take_scores)."
+    lib = _native.require_gpu()
+    assert scores.dtype == torch.float32 and scores.is_contiguous() and scores.dim() == 2
+    assert idx.dtype == torch.int32 and idx.is_contiguous() and idx.shape[0] == scores.shape[0]
+    out = torch.empty(tuple(idx.shape), dtype=torch.float32, device=scores.device)
+    check(lib.lk_take_scores(_ptr(scores), scores.shape[0], scores.shape[1], _ptr(idx),
+                             idx.shape[1], _ptr(out), _stream()), "lk_take_scores")
+    return out
+
+
 def score_dense(users: torch.Tensor, items: torch.Tensor, k: int) -> torch.Tensor:
     "All (user, item) scores, [B x I] f32 (lk_score_dense)."
     lib = _native.require_gpu()

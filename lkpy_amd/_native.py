@@ -151,6 +151,17 @@ def _declare(lib):
         "lk_ease_score_batch": (
             c_int, [vp, vp, c_int64, vp, c_int64, c_int64, vp, c_int64, vp]
         ),
+        "lk_slim_train_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
+        "lk_slim_train_count": (
+            c_int,
+            [vp, vp, vp, vp, c_int, c_int64, c_int64, vp, c_float, c_float, c_int32, c_int64, vp,
+             c_int64, vp, vp, vp, POINTER(c_int64), POINTER(c_int64), vp],
+        ),
+        "lk_slim_train_fill": (c_int, [c_int64, c_int64, c_int64, c_int64, vp, vp, vp, vp, vp]),
+        "lk_slim_score_batch": (
+            c_int, [vp, vp, c_int64, vp, vp, vp, c_int64, vp, c_int64, c_int, vp]
+        ),
+        "lk_take_scores": (c_int, [vp, c_int64, c_int64, vp, c_int64, vp, vp]),
         "lk_score_topk_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
         "lk_score_topk": (
             c_int,

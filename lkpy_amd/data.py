@@ -562,6 +562,15 @@ class _Matrix:
             return sps.coo_array((values, (ds._rows, ds._cols)), shape=shape)
         return sps.csr_array((values, ds._cols, ds._indptr), shape=shape)
 
+    def csr_structure(self, *, format: str = "arrow"):
+        """``_relationships.py:549-562``, the ``format="arrow"`` form: the matrix without values
+        as a structure-only ``SparseRowArray``."""
+        ds = self._ds
+        if format != "arrow":
+            raise ValueError(f"unsupported CSR structure format {format}")
+        return SparseRowArray.from_arrays(ds._indptr, ds._cols,
+                                          shape=(ds.user_count, ds.item_count))
+
     def row_items(self, user_id) -> ItemList | None:
         ds = self._ds
         u = ds.users.number(user_id, missing=None)

@@ -1,7 +1,8 @@
 """
 Component seam for neighbourhood models -- item-based k-NN and user-based
-k-NN (mirror of ``lenskit.knn.UserKNNScorer``, src/lenskit/knn/user.py:25-316) and EASE (end of
-the file, mirror of ``lenskit.knn.EASEScorer``, src/lenskit/knn/ease.py).
+k-NN (mirror of ``lenskit.knn.UserKNNScorer``, src/lenskit/knn/user.py:25-316), EASE (mirror of
+``lenskit.knn.EASEScorer``, src/lenskit/knn/ease.py) and SLIM / fsSLIM (end of the file, mirror of
+``lenskit.knn.SLIMScorer``, src/lenskit/knn/slim.py).
 
 Item-based k-NN: mirror of ``lenskit.knn.ItemKNNScorer`` /
 ``ItemKNNConfig`` (src/lenskit/knn/item.py:41-295).  Matrix preparation is the reference's
@@ -550,3 +551,160 @@ class EASEScorer(Component):
 
     def __call__(self, query, items: ItemList) -> ItemList:
         return self.score_batch([query], [items])[0]
+
+
+# ---------------------------------------------------------------------------------------
+# SLIM / fsSLIM
+# ---------------------------------------------------------------------------------------
+
+
+class SLIMConfig(BaseModel, extra="forbid"):
+    "``SLIMConfig`` (src/lenskit/knn/slim.py:29-50)."
+
+    l1_reg: PositiveFloat = 1.0
+    "L1 regularization strength."
+    l2_reg: PositiveFloat = 1.0
+    "L2 regularization strength."
+    max_iters: PositiveInt = 100
+    "Maximum coordinate-descent rounds per column."
+    max_nbrs: PositiveInt | None = None
+    "Maximum neighbours (features) per item; a positive integer enables fsSLIM (cosine selection)."
+
+
+class SLIMScorer(Component):
+    """
+    Sparse linear methods (``SLIMScorer``, src/lenskit/knn/slim.py:53-152): one elastic-net
+    regression per item, learned by coordinate descent with soft thresholding.  Training runs on
+    the device, a wave per column, and learns the reference's sparse matrix bit for bit
+    (``lk_slim_train_count`` / ``_fill``, csrc/slim.hip); scoring adds the history items' weight
+    rows in history order (``lk_slim_score_batch``), whole batches of queries at a time, and
+    ``recommend_batch`` selects the lists from bounded panels with ``lk_argtopn``.  The learned
+    state stays on the host: ``weights`` (SciPy CSR, feature rows) and ``items``.
+    """
+
+    config: SLIMConfig
+
+    weights: sps.csr_array
+    "The TRANSPOSED weight matrix: ``weights[i, j]`` is the weight of item i in predicting item j."
+    items: Vocabulary
+
+    PANEL_BYTES = 1 << 30  # score panel of one recommend / score step
+
+    def is_trained(self) -> bool:
+        return hasattr(self, "weights")
+
+    def train(self, data: Dataset, options: TrainingOptions = TrainingOptions()):
+        "slim.py:93-119, line for line."
+        import pyarrow as pa
+
+        from ._accel import slim as _slim_accel
+        from .parallel import run_accel_task
+
+        ui_matrix = data.interactions().matrix().csr_structure(format="arrow")
+        iu_matrix = ui_matrix.transpose()
+        weights = run_accel_task(
+            _slim_accel.train_slim(
+                ui_matrix,
+                iu_matrix,
+                self.config.l1_reg,
+                self.config.l2_reg,
+                self.config.max_iters,
+                self.config.max_nbrs,
+            )
+        )
+        weights = pa.chunked_array(weights).combine_chunks()
+        weights = SparseRowArray.from_array(weights)
+        self.weights = weights.to_scipy().T.tocsr()
+        self.items = data.items
+
+    def _device_weights(self) -> D.DeviceCSR:
+        def upload():
+            w = self.weights
+            d = D.device()
+            return D.DeviceCSR(torch.from_numpy(np.array(w.indptr, dtype=np.int64)).to(d),
+                               torch.from_numpy(np.array(w.indices, dtype=np.int32)).to(d),
+                               torch.from_numpy(np.array(w.data, dtype=np.float32)).to(d),
+                               (int(w.shape[0]), int(w.shape[1])), None)
+
+        return self._device_cache("weights", upload, self.weights)
+
+    def _panel_rows(self) -> int:
+        return max(1, self.PANEL_BYTES // (4 * max(len(self.items), 1)))
+
+    def _query_csr(self, queries: list[RecQuery]) -> D.DeviceCSR:
+        "The histories of a list of queries in query order: item numbers, -1 = unknown."
+        r_idx, r_ptr = [], [0]
+        for q in queries:
+            hist = q.query_items
+            if hist is not None and len(hist) > 0:
+                r_idx.append(hist.numbers(vocabulary=self.items, missing="negative"))
+            r_ptr.append(r_ptr[-1] + (0 if hist is None else len(hist)))
+        idx = np.concatenate(r_idx).astype(np.int32) if r_idx else np.zeros(0, np.int32)
+        d = self._device_weights().indices.device
+        ptr = np.asarray(r_ptr, np.int64)
+        return D.DeviceCSR(torch.from_numpy(ptr).to(d), torch.from_numpy(idx).to(d), None,
+                           (len(queries), len(self.items)), ptr)
+
+    def score_batch(self, queries, item_lists) -> list[ItemList]:
+        "Scores for a batch of (query, items) pairs (slim.py:121-152 per pair)."
+        w = self._device_weights()
+        hist = self._query_csr([RecQuery.create(q) for q in queries])
+        out = []
+        step = self._panel_rows()
+        for lo in range(0, len(item_lists), step):
+            hi = min(len(item_lists), lo + step)
+            panel = D.to_host(D.slim_score_batch(hist.indptr, hist.indices, w, rows=(lo, hi)))
+            for i in range(lo, hi):
+                items = item_lists[i]
+                if hist.h_indptr[i] == hist.h_indptr[i + 1]:
+                    out.append(ItemList(items, scores=np.nan))  # no / empty history: 125-130
+                    continue
+                t_inos = items.numbers(vocabulary=self.items, missing="negative")
+                sc = np.full(len(items), np.nan, dtype=np.float32)
+                t_ok = t_inos >= 0
+                sc[t_ok] = panel[i - lo][t_inos[t_ok]]
+                out.append(ItemList(items, scores=sc))
+        return out
+
+    def __call__(self, query, items: ItemList) -> ItemList:
+        return self.score_batch([query], [items])[0]
+
+    # -- top-n --------------------------------------------------------------------------------
+    accepts_history_batch = True  # recommend_batch takes a lkpy_amd.basic.HistoryBatch
+
+    def recommend_batch(self, queries, n: int, *, exclude_history: bool = True):
+        """
+        Top-``n`` lists for many queries at once -- what the ``recommender`` pipeline computes one
+        query at a time: candidates = every training item minus the query's own
+        (src/lenskit/basic/candidates.py:77-94), this scorer over them, ``TopNRanker``
+        (basic/topn.py:45-69).  Items no history item points at score 0.0 and are listed when
+        fewer than ``n`` score above it; a query without history gets an empty list.
+        ``queries``: a list of queries, or a :class:`lkpy_amd.basic.HistoryBatch` (training
+        histories by user number, cut out of the HBM-resident training matrix).  The batch goes
+        through in panels of at most ``PANEL_BYTES``.  Returns (item numbers [B x n] with -1
+        padding, scores [B x n] with NaN padding), like ``ItemKNNScorer.recommend_batch``.
+        """
+        from .basic import HistoryBatch
+
+        if isinstance(queries, HistoryBatch) and not (
+                queries.items is self.items or queries.items == self.items):
+            queries = queries.queries()  # (another item vocabulary: the per-query mapping)
+        w = self._device_weights()
+        if isinstance(queries, HistoryBatch):
+            hist = queries.csr(with_values=False)
+        else:
+            hist = self._query_csr([RecQuery.create(q) for q in queries])
+        B = hist.shape[0]
+        n = int(n)
+        cols = len(self.items) if n < 0 else n
+        oi = torch.full((B, cols), -1, dtype=torch.int32, device=w.indices.device)
+        osc = torch.full((B, cols), float("nan"), dtype=torch.float32, device=w.indices.device)
+        step = self._panel_rows()
+        for lo in range(0, B, step):
+            hi = min(B, lo + step)
+            panel = D.slim_score_batch(hist.indptr, hist.indices, w, rows=(lo, hi),
+                                       strike_history=exclude_history, nan_empty=True)
+            idx = D.argtopn(panel, n)
+            oi[lo:hi, :idx.shape[1]] = idx
+            osc[lo:hi, :idx.shape[1]] = D.take_scores(panel, idx)
+        return D.lists_to_host(oi, osc)
