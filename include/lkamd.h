@@ -721,6 +721,61 @@ int lk_synth_zipf_rows(const int64_t *d_indptr, int64_t n_rows, int64_t n_items,
                        const int32_t *d_long_rows, int64_t n_long_rows, int32_t *d_out_indices,
                        void *stream);
 
+/* ------------------------------------------------------------------------
+ * Run evaluation (csrc/metrics.hip; lkpy_amd/metrics.py composes the metric values on the host
+ * from these statistics with the reference's own expressions).  Replaces the per-list loop of
+ * `MeasurementCollector.add_collection_measurements` (src/lenskit/metrics/_collect.py:156-186)
+ * and the `measure_list` bodies it calls.  Item NUMBERS throughout; a truth CSR has one row per
+ * list (int64 offsets, items ascending, no duplicates) -- rows cut out of the per-test-set
+ * matrix with lk_csr_gather_rows.  All calls are asynchronous on `stream`; every float64 output
+ * is a sum taken in rank (list) order and depends on its own list and truth row only.
+ *
+ * lk_rank_stats: d_lists [n_lists x ld] in rank order, the first `len` columns are read; entries
+ *   < 0 are dropped BEFORE ranks are assigned (rank = 1 + kept entries before it).  `cutoffs`
+ *   (host, 1..8 values, 0 = whole list), d_weights [n_tables x w_ld] float64 with
+ *   d_weights[t * w_ld + rank - 1] = w_t(rank), w_ld >= len, 0..4 tables, and
+ *   n_cutoffs * (1 + 2 n_tables) <= 64.  Outputs (field-major):
+ *     d_out_counts int32 [(2 + 2 n_cutoffs) x n_lists]: row 0 n_recs (kept entries), row 1 the
+ *       truth row's length, rows 2 + 2c / 3 + 2c: n_hits (`recs.isin(test).sum()`, a repeated
+ *       item counts each time) and first_hit (1-based rank, 0 = none) inside cutoff c
+ *       (ranking/_pr.py:44,67, _hit.py:42, _recip.py:45-50);
+ *     d_out_sums float64 [n_cutoffs * (1 + 2 n_tables) x n_lists]: per cutoff c, row
+ *       c * (1 + 2 n_tables) = ap_sum, sum over hit ranks of (hits up to here) / rank
+ *       (_map.py:37-41); + 1 + 2t = w_hits, sum of w_t(rank) over hit ranks (`_binary_dcg`,
+ *       _dcg.py:248-255; `rank_biased_precision`, _rbp.py:17-37); + 2 + 2t = g_hits, sum of
+ *       max(gain, 0) * w_t(rank), the float32 gain widened first, a NaN gain skipped
+ *       (`_graded_dcg`, _dcg.py:224-245; 0 when d_truth_gains is NULL).
+ * lk_ideal_gain: graded NDCG's denominator (_dcg.py:118-133).  Per truth row the gains with NaN
+ *   dropped and negatives clipped to 0, sorted descending; for combination k the first
+ *   cutoffs[k] of them (0: all) times w_tables[k](1 ..) added in that order:
+ *   d_out_ideal [n_combos x n_rows]; d_out_count [n_rows] = non-NaN gains.  Rows longer than
+ *   4096 entries must be listed in d_long_rows and are sorted in d_ws
+ *   (lk_ideal_gain_workspace_bytes(n_long_rows, longest_row)); products beyond w_ld are not
+ *   formed.
+ * lk_predict_errors: RMSE / MAE (predict.py:73-111, 131-137, 164-169).  Ragged prediction lists
+ *   of DISTINCT items (int64 offsets, item numbers, float32 scores) against the truth CSR with float32 ratings, or -- with
+ *   d_truth_ptr NULL -- against d_pred_ratings carried by the lists.  e = score - rating, e * e
+ *   and |e| in float32, accumulated in float64 in list order.  d_out_sums [2 x n_lists]: sse,
+ *   sae; d_out_counts [3 x n_lists]: n (finite errors), n_missing_score (rated, not scored or
+ *   scored NaN), n_missing_truth (scored, no rating) -- predict.py:102-109.
+ * ---------------------------------------------------------------------- */
+int lk_rank_stats(const int32_t *d_lists, int64_t n_lists, int64_t ld, int64_t len,
+                  const int64_t *d_truth_ptr, const int32_t *d_truth_items,
+                  const float *d_truth_gains, const int32_t *cutoffs, int32_t n_cutoffs,
+                  const double *d_weights, int32_t n_tables, int64_t w_ld, int32_t *d_out_counts,
+                  double *d_out_sums, void *stream);
+size_t lk_ideal_gain_workspace_bytes(int64_t n_long_rows, int64_t longest_row);
+int lk_ideal_gain(const int64_t *d_truth_ptr, const float *d_gains, int64_t n_rows,
+                  const int32_t *d_long_rows, int64_t n_long_rows, int64_t longest_row,
+                  void *d_ws, const int32_t *cutoffs, const int32_t *tables, int32_t n_combos,
+                  const double *d_weights, int32_t n_tables, int64_t w_ld, double *d_out_ideal,
+                  int32_t *d_out_count, void *stream);
+int lk_predict_errors(int64_t n_lists, const int64_t *d_pred_ptr, const int32_t *d_pred_items,
+                      const float *d_pred_scores, const float *d_pred_ratings,
+                      const int64_t *d_truth_ptr, const int32_t *d_truth_items,
+                      const float *d_truth_ratings, double *d_out_sums, int32_t *d_out_counts,
+                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1318,3 +1318,112 @@ def iknn_prepare(ratings, explicit: bool = True, dev=None):
     ui = DeviceCSR(dcsr.indptr, dcsr.indices, v_users, (n_users, n_items), dcsr.h_indptr)
     iu = DeviceCSR(t.indptr, t.indices, v_items, (n_items, n_users), t_ptr)
     return ui, iu, means, all_zero
+
+
+RANK_STATS_MAX_CUTOFFS = 8  # of one lk_rank_stats launch (csrc/metrics.hip)
+RANK_STATS_MAX_TABLES = 4
+IDEAL_GAIN_LDS_ROW = 4096  # longest truth row lk_ideal_gain sorts in LDS
+
+
+def _i32_array(vals):
+    arr = (ctypes.c_int32 * max(len(vals), 1))()
+    for i, v in enumerate(vals):
+        arr[i] = int(v)
+    return arr
+
+
+def rank_stats(lists: torch.Tensor, truth: DeviceCSR, cutoffs, weights: torch.Tensor | None,
+               gains: bool = False, length: int | None = None):
+    """
+    The sufficient statistics of the ranking metrics for a batch of lists (lk_rank_stats):
+    ``lists`` device int32 [B x ld] item numbers in rank order (negative entries dropped before
+    ranking), ``truth`` the per-list truth CSR (int64 offsets, rows ascending; ``values`` = gains
+    when ``gains``), ``cutoffs`` host integers (0 = whole list), ``weights`` device float64
+    [tables x w_ld] or None.  Returns device (counts int32 [(2 + 2 C) x B], sums float64
+    [C (1 + 2 T) x B]) laid out as include/lkamd.h says.
+    """
+    lib = _native.require_gpu()
+    assert lists.dtype == torch.int32 and lists.dim() == 2 and lists.is_contiguous()
+    B, ld = int(lists.shape[0]), int(lists.shape[1])
+    ln = ld if length is None else int(length)
+    assert truth.indptr.dtype == torch.int64 and int(truth.indptr.shape[0]) == B + 1
+    C = len(cutoffs)
+    T = 0 if weights is None else int(weights.shape[0])
+    if weights is not None:
+        assert weights.dtype == torch.float64 and weights.is_contiguous()
+    dev = lists.device
+    counts = torch.empty((2 + 2 * C, B), dtype=torch.int32, device=dev)
+    sums = torch.empty((C * (1 + 2 * T), B), dtype=torch.float64, device=dev)
+    check(
+        lib.lk_rank_stats(_ptr(lists), B, ld, ln, _ptr(truth.indptr),
+                          _ptr(truth.indices), _ptr(truth.values) if gains else None,
+                          _i32_array(cutoffs), C, _ptr(weights), T,
+                          0 if weights is None else int(weights.shape[1]), _ptr(counts),
+                          _ptr(sums), _stream()),
+        "lk_rank_stats",
+    )
+    return counts, sums
+
+
+def ideal_gain(truth: DeviceCSR, combos, weights: torch.Tensor):
+    """
+    Graded NDCG's denominators (lk_ideal_gain): per row of ``truth`` (values = gains; needs the
+    host copy of the offsets) and per ``combos`` entry (cutoff, table) the descending clipped
+    gains dotted with the table.  Returns device (ideal float64 [combos x rows], count of
+    non-NaN gains int32 [rows]).
+    """
+    lib = _native.require_gpu()
+    R = int(truth.indptr.shape[0]) - 1
+    dev = truth.indptr.device
+    lens = np.diff(truth.h_indptr)
+    long_rows = np.flatnonzero(lens > IDEAL_GAIN_LDS_ROW).astype(np.int32)
+    longest = int(lens.max()) if R else 0
+    d_long = torch.from_numpy(long_rows).to(dev) if len(long_rows) else None
+    wb = lib.lk_ideal_gain_workspace_bytes(len(long_rows), longest)
+    ws = torch.empty(wb, dtype=torch.uint8, device=dev) if wb else None
+    ideal = torch.zeros((len(combos), R), dtype=torch.float64, device=dev)
+    count = torch.zeros(R, dtype=torch.int32, device=dev)
+    assert weights.dtype == torch.float64 and weights.is_contiguous()
+    check(
+        lib.lk_ideal_gain(_ptr(truth.indptr), _ptr(truth.values), R, _ptr(d_long),
+                          len(long_rows), longest, _ptr(ws), _i32_array([c for c, _t in combos]),
+                          _i32_array([t for _c, t in combos]), len(combos), _ptr(weights),
+                          int(weights.shape[0]), int(weights.shape[1]), _ptr(ideal), _ptr(count),
+                          _stream()),
+        "lk_ideal_gain",
+    )
+    return ideal, count
+
+
+def predict_errors(pred_ptr: torch.Tensor, pred_items: torch.Tensor | None,
+                   pred_scores: torch.Tensor, truth: DeviceCSR | None,
+                   pred_ratings: torch.Tensor | None = None):
+    """
+    Squared / absolute prediction errors per list (lk_predict_errors): ragged lists (int64
+    offsets, int32 item numbers, f32 scores) against the per-list ``truth`` CSR (values =
+    ratings), or against ``pred_ratings`` when ``truth`` is None.  Returns device (sums float64
+    [2 x B]: sse, sae; counts int32 [3 x B]: n, n_missing_score, n_missing_truth).
+    """
+    lib = _native.require_gpu()
+    B = int(pred_ptr.shape[0]) - 1
+    dev = pred_ptr.device
+    assert pred_ptr.dtype == torch.int64 and pred_scores.dtype == torch.float32
+    sums = torch.zeros((2, B), dtype=torch.float64, device=dev)
+    counts = torch.zeros((3, B), dtype=torch.int32, device=dev)
+    if truth is not None:
+        assert truth.indptr.dtype == torch.int64 and int(truth.indptr.shape[0]) == B + 1
+        assert pred_items is not None and pred_items.dtype == torch.int32
+    else:
+        assert pred_ratings is not None and pred_ratings.dtype == torch.float32
+    if int(pred_scores.shape[0]) == 0:  # (no entry is read; the call wants non-null arrays)
+        pred_items = torch.zeros(1, dtype=torch.int32, device=dev)
+        pred_ratings = torch.zeros(1, dtype=torch.float32, device=dev)
+    check(
+        lib.lk_predict_errors(B, _ptr(pred_ptr), _ptr(pred_items), _ptr(pred_scores),
+                              _ptr(pred_ratings), _ptr(truth.indptr) if truth else None,
+                              _ptr(truth.indices) if truth else None,
+                              _ptr(truth.values) if truth else None, _ptr(sums), _ptr(counts),
+                              _stream()),
+        "lk_predict_errors",
+    )
+    return sums, counts

@@ -182,6 +182,16 @@ def _declare(lib):
         "lk_csr_gather_rows": (
             c_int, [vp, c_int, vp, vp, c_int64, vp, vp, vp, c_float, vp, vp, vp]
         ),
+        "lk_rank_stats": (
+            c_int, [vp, c_int64, c_int64, c_int64, vp, vp, vp, vp, c_int32, vp, c_int32, c_int64,
+                    vp, vp, vp]
+        ),
+        "lk_ideal_gain_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+        "lk_ideal_gain": (
+            c_int, [vp, vp, c_int64, vp, c_int64, c_int64, vp, vp, vp, c_int32, vp, c_int32,
+                    c_int64, vp, vp, vp]
+        ),
+        "lk_predict_errors": (c_int, [c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "lk_als_implicit_half_epoch_host": (
             c_int,
             [vp, c_int, vp, vp, c_int64, c_int64, c_int32, vp, vp, vp, c_int32, vp],

@@ -170,6 +170,21 @@ class ItemList:
         out._fields = {k: v[sel] for k, v in self._fields.items()}
         return out
 
+    def __getitem__(self, sel) -> "ItemList":
+        "A slice, index array or mask of the list (``_items.py``, ``__getitem__``); order is kept."
+        if isinstance(sel, (int, np.integer)):
+            sel = [int(sel)]
+        return self._take(sel if isinstance(sel, slice) else np.asarray(sel),
+                          ordered=self.ordered)
+
+    def isin(self, other: "ItemList") -> np.ndarray:
+        "Per item: is it (by id) in ``other``?  (``ItemList.isin``)"
+        return np.isin(self.ids(), other.ids())
+
+    def ranks(self) -> np.ndarray | None:
+        "1-based ranks of an ordered list, None for an unordered one (``ItemList.ranks``)."
+        return np.arange(1, len(self) + 1, dtype=np.int32) if self.ordered else None
+
     def remove(self, *, ids=None, numbers=None) -> "ItemList":
         "Drop the given items (``_items.py:1083-1128``)."
         if numbers is not None:
@@ -306,6 +321,11 @@ class ItemListCollection:
         self._ensure_index()
         pos = self._index.get(key)
         return None if pos is None else self._lists[pos][1]
+
+    def lookup_projected(self, key: tuple) -> ItemList | None:
+        """The list whose key is ``key`` projected onto this collection's key fields
+        (``_collection/_base.py``, ``lookup_projected``): ``key`` is a named tuple that has them."""
+        return self.lookup(tuple(getattr(key, f) for f in self.key_fields))
 
     def items(self):
         return iter(self._lists)
