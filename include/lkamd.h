@@ -776,6 +776,87 @@ int lk_predict_errors(int64_t n_lists, const int64_t *d_pred_ptr, const int32_t 
                       const float *d_truth_ratings, double *d_out_sums, int32_t *d_out_counts,
                       void *stream);
 
+/* ------------------------------------------------------------------------
+ * FlexMF implicit (csrc/flexmf.hip): the minibatch trainer of `lenskit.flexmf.FlexMFImplicitScorer`
+ * -- score = b_u + b_i + p_u . q_i, logistic / pairwise (BPR) / WARP loss, AdamW or SparseAdam.
+ * All tables are float32, row-major and UNPADDED ([rows x k], biases [rows]); a NULL bias table
+ * is an absent one (counts as 0).  Every call is asynchronous on `stream`; nothing is atomic
+ * on floats and every sum has a fixed order, so a step is a function of its inputs alone.
+ * ---------------------------------------------------------------------- */
+#define LK_FLEXMF_LOGISTIC 0
+#define LK_FLEXMF_PAIRWISE 1
+#define LK_FLEXMF_WARP 2
+#define LK_FLEXMF_ADAMW 0
+#define LK_FLEXMF_SPARSE_ADAM 1
+#define LK_FLEXMF_MAX_K 256
+
+/* table order everywhere: 0 u_embed, 1 i_embed, 2 u_bias, 3 i_bias (`FlexMFModel`,
+ * src/lenskit/flexmf/_model.py:73-81) with the optimiser's two moment tables of each */
+typedef struct lk_flexmf_tables {
+    float *param[4];
+    float *exp_avg[4];
+    float *exp_avg_sq[4];
+    int64_t n_users, n_items;
+    int32_t k;
+} lk_flexmf_tables;
+
+typedef struct lk_flexmf_hyper {
+    int32_t loss;      /* LK_FLEXMF_LOGISTIC | PAIRWISE | WARP */
+    int32_t optimizer; /* LK_FLEXMF_ADAMW | LK_FLEXMF_SPARSE_ADAM */
+    int32_t l2;        /* 1: the explicit L2 term of reg_method = "L2" */
+    int32_t n_neg;     /* negatives per positive */
+    /* doubles, as Torch's optimisers hold them: each is rounded to float32 where Torch rounds */
+    double pos_weight; /* logistic loss only */
+    double reg;        /* weight decay (AdamW) or the L2 strength */
+    double lr, beta1, beta2, eps;
+    double bias_corr1, bias_corr2; /* 1 - beta^t of the step about to be taken, from the host */
+} lk_flexmf_hyper;
+
+/* Negative sampling -- `sample_negatives` (src/accel/data/sampling.rs:17-63) behind
+ * `MatrixRelationshipSet.sample_negatives` (src/lenskit/data/_relationships.py:725-793).
+ * d_out [n_rows x n]: for (row r, replicate j) a column drawn uniformly from [0, n_cols)
+ * (popular: the column of a uniformly drawn entry of d_indices), redrawn while it is an entry of
+ * CSR row d_rows[r] (binary search; columns ascending inside a row), at most max_attempts
+ * times, after which the last draw stands; verify = 0: the first draw stands.  The draw is
+ * Philox4x32-10(key, (counter, r, j, attempt)): the reference's PCG64 stream is not reproduced,
+ * the contract is distributional. */
+int lk_flexmf_sample_negatives(const int64_t *d_indptr, const int32_t *d_indices, int64_t nnz,
+                               int64_t n_cols, const int32_t *d_rows, int64_t n_rows, int32_t n,
+                               int popular, int verify, int32_t max_attempts, uint64_t key,
+                               uint64_t counter, int32_t *d_out, void *stream);
+
+/* One batch's (user, item) pairs: out[i] = all[perm[i]] for both arrays -- `make_batch`
+ * (src/lenskit/flexmf/_training.py:350-358) on the device-resident epoch permutation. */
+int lk_flexmf_gather_batch(const int32_t *d_perm, int64_t n, const int32_t *d_all_users,
+                           const int32_t *d_all_items, int32_t *d_users, int32_t *d_items,
+                           void *stream);
+
+/* The WARP / "misranked" negative search -- `FlexMFWARPTrainer.scored_negatives`
+ * (src/lenskit/flexmf/_implicit.py:293-396) -- as a function of a candidate table
+ * d_cand [batch x tries]: per sample, try t = 1.. takes candidate t - 1; a candidate scoring
+ * strictly above the best so far replaces it (count = t); the search stops once best >= the
+ * positive's score.  Candidates are scored only up to the stopping try.  Outputs: d_neg [batch],
+ * d_count [batch] int32, d_weight [batch] float64 = the harmonic-number approximation at
+ * rank = (n_items - 1) / (count + 1), in double. */
+int lk_flexmf_warp_search(const lk_flexmf_tables *tables, const int32_t *d_users,
+                          const int32_t *d_pos, const int32_t *d_cand, int64_t batch,
+                          int32_t tries, int32_t *d_neg, int32_t *d_count, double *d_weight,
+                          void *stream);
+
+/* One training step -- `FlexMFImplicitTrainer.train_batch` + `opt.step()`
+ * (src/lenskit/flexmf/_implicit.py:253-274,399-415, _model.py:145-198, _training.py:238-252):
+ * forward, loss, gradients, per-row gradient sums (stable radix sort by destination row, then
+ * one wave per touched row adding in sample order) and the optimiser update, as
+ * torch.optim.AdamW / torch.optim.SparseAdam perform it.  d_neg [batch x n_neg];
+ * d_weights [batch] float64 (WARP only).  d_slot: int32 [n_users + n_items], all -1 on entry and
+ * on return (AdamW only; NULL otherwise).  *d_loss receives the batch loss, *d_loss_sum (may be
+ * NULL) has it added. */
+size_t lk_flexmf_step_workspace_bytes(int64_t batch, int32_t n_neg, int32_t k);
+int lk_flexmf_step(const lk_flexmf_tables *tables, const lk_flexmf_hyper *hyper,
+                   const int32_t *d_users, const int32_t *d_pos, const int32_t *d_neg,
+                   const double *d_weights, int64_t batch, void *d_ws, int32_t *d_slot,
+                   float *d_loss, float *d_loss_sum, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

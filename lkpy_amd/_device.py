@@ -1427,3 +1427,193 @@ def predict_errors(pred_ptr: torch.Tensor, pred_items: torch.Tensor | None,
         "lk_predict_errors",
     )
     return sums, counts
+
+
+# ---------------------------------------------------------------------------------------
+# FlexMF implicit (csrc/flexmf.hip)
+# ---------------------------------------------------------------------------------------
+
+_FLEXMF_TABLES = ("u_embed", "i_embed", "u_bias", "i_bias")
+
+
+def _i32_dev(a, dev) -> torch.Tensor:
+    if isinstance(a, torch.Tensor):
+        return a.to(device=dev, dtype=torch.int32).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+
+
+def flexmf_sample_negatives(indptr: torch.Tensor, indices: torch.Tensor, n_cols: int, rows,
+                            n: int, weighting: str, key: int, counter: int = 0, *,
+                            verify: bool = True, max_attempts: int = 10) -> torch.Tensor:
+    """
+    Negative columns for ``rows`` (lk_flexmf_sample_negatives): int32 device [len(rows) x n].
+    ``indptr`` (int64) / ``indices`` (int32, ascending inside a row): the training matrix on the
+    device; ``weighting``: ``uniform`` | ``popular`` | ``popularity``; the draw is a function of
+    (key, counter, row position, replicate, attempt) alone.
+    """
+    lib = _native.require_gpu()
+    if weighting not in ("uniform", "popular", "popularity"):
+        raise ValueError(f"unsupported weighting {weighting}")
+    assert indptr.dtype == torch.int64 and indices.dtype == torch.int32
+    dev = indptr.device
+    rows = _i32_dev(rows, dev)
+    out = torch.empty((rows.numel(), int(n)), dtype=torch.int32, device=dev)
+    check(lib.lk_flexmf_sample_negatives(
+        _ptr(indptr), _ptr(indices), indices.numel(), int(n_cols), _ptr(rows), rows.numel(),
+        int(n), int(weighting != "uniform"), int(bool(verify)), int(max_attempts),
+        int(key) & (2**64 - 1), int(counter) & (2**64 - 1), _ptr(out), _stream()),
+        "lk_flexmf_sample_negatives")
+    return out
+
+
+class FlexMFState:
+    """
+    The FlexMF model and its optimiser state in HBM: the four tables of ``FlexMFModel``
+    (src/lenskit/flexmf/_model.py:73-81; an absent bias table is ``None``), Adam's two moment
+    tables of each, the global step count and the step's scratch.  ``step`` is one
+    ``train_batch`` + ``opt.step()`` (lk_flexmf_step) on explicit (users, positives, negatives
+    [, weights]); ``warp_search`` is the misranked-negative search on an explicit candidate table.
+    """
+
+    def __init__(self, u_embed, i_embed, u_bias=None, i_bias=None, *, loss: str = "logistic",
+                 reg_method: str | None = "AdamW", regularization: float = 0.01,
+                 learning_rate: float = 0.01, negative_count: int = 1,
+                 positive_weight: float = 1.0, dev=None):
+        self.dev = dev = device(dev)
+        host = [u_embed, i_embed, u_bias, i_bias]
+        self.n_users, self.k = np.shape(u_embed)
+        self.n_items = np.shape(i_embed)[0]
+        if not 1 <= self.k <= _native.FLEXMF_MAX_K:
+            raise ValueError(f"unsupported embedding size {self.k} "
+                             f"(supported: 1..{_native.FLEXMF_MAX_K})")
+        if np.shape(i_embed)[1] != self.k:
+            raise ValueError("user and item embeddings differ in width")
+        self.param, self.exp_avg, self.exp_avg_sq = [], [], []
+        for i, a in enumerate(host):
+            if a is None:
+                t = None
+            else:
+                a = np.ascontiguousarray(a, dtype=np.float32)
+                rows = self.n_users if i in (0, 2) else self.n_items
+                if i >= 2:
+                    a = a.reshape(-1)
+                if a.shape[0] != rows:
+                    raise ValueError(f"{_FLEXMF_TABLES[i]} has {a.shape[0]} rows, not {rows}")
+                t = torch.from_numpy(a).to(dev)
+            self.param.append(t)
+            self.exp_avg.append(None if t is None else torch.zeros_like(t))
+            self.exp_avg_sq.append(None if t is None else torch.zeros_like(t))
+        if loss not in _native.FLEXMF_LOSSES:
+            raise ValueError(f"unknown loss {loss}")
+        if reg_method not in ("AdamW", "L2", None):
+            raise ValueError(f"unknown regularization method {reg_method}")
+        self.loss, self.reg_method = loss, reg_method
+        self.regularization, self.learning_rate = float(regularization), float(learning_rate)
+        self.negative_count, self.positive_weight = int(negative_count), float(positive_weight)
+        self.beta1, self.beta2, self.eps = 0.9, 0.999, 1e-8  # the defaults of both optimisers
+        self.steps = 0
+        self._ws = None
+        self._ws_batch = 0
+        # AdamW: row -> slot of its summed gradient, all -1 between steps
+        self._slot = torch.full((self.n_users + self.n_items,), -1, dtype=torch.int32,
+                                device=dev) if reg_method == "AdamW" else None
+        self._tables = _native.FlexMFTables()
+        for i in range(4):
+            self._tables.param[i] = _ptr(self.param[i]).value
+            self._tables.exp_avg[i] = _ptr(self.exp_avg[i]).value
+            self._tables.exp_avg_sq[i] = _ptr(self.exp_avg_sq[i]).value
+        self._tables.n_users, self._tables.n_items = self.n_users, self.n_items
+        self._tables.k = self.k
+
+    def _check_indices(self, users, pos, neg):
+        for name, t, bound in (("users", users, self.n_users), ("positives", pos, self.n_items),
+                               ("negatives", neg, self.n_items)):
+            if t.numel() and (int(t.min()) < 0 or int(t.max()) >= bound):
+                raise ValueError(f"{name} outside [0, {bound})")
+
+    def step(self, users, positives, negatives, weights=None, *, loss_sum=None,
+             check_indices: bool = True) -> torch.Tensor:
+        "One training step; returns the batch loss (device, 1 element), nothing synchronised."
+        lib = _native.require_gpu()
+        dev = self.dev
+        users, positives = _i32_dev(users, dev).reshape(-1), _i32_dev(positives, dev).reshape(-1)
+        negatives = _i32_dev(negatives, dev).reshape(-1)
+        B, n = users.numel(), self.negative_count
+        if positives.numel() != B or negatives.numel() != B * n or B < 1:
+            raise ValueError("batch arrays disagree in length")
+        if self.loss == "warp":
+            if weights is None or n != 1:
+                raise ValueError("WARP loss takes one negative per sample and the weights")
+            weights = torch.as_tensor(weights).to(device=dev, dtype=torch.float64).contiguous()
+            if weights.numel() != B:
+                raise ValueError("weights disagree with the batch in length")
+        else:
+            weights = None
+        if check_indices:  # (the trainer's own arrays come from the dataset and the sampler)
+            self._check_indices(users, positives, negatives)
+        if self._ws is None or self._ws_batch < B:
+            self._ws = torch.empty(lib.lk_flexmf_step_workspace_bytes(B, n, self.k),
+                                   dtype=torch.uint8, device=dev)
+            self._ws_batch = B
+        self.steps += 1
+        h = _native.FlexMFHyper(
+            _native.FLEXMF_LOSSES[self.loss],
+            _native.FLEXMF_ADAMW if self.reg_method == "AdamW" else _native.FLEXMF_SPARSE_ADAM,
+            int(self.reg_method == "L2"), n, self.positive_weight, self.regularization,
+            self.learning_rate, self.beta1, self.beta2, self.eps,
+            1.0 - self.beta1 ** self.steps, 1.0 - self.beta2 ** self.steps)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        check(lib.lk_flexmf_step(ctypes.byref(self._tables), ctypes.byref(h), _ptr(users),
+                                 _ptr(positives), _ptr(negatives), _ptr(weights), B,
+                                 _ptr(self._ws), _ptr(self._slot), _ptr(loss), _ptr(loss_sum),
+                                 _stream()), "lk_flexmf_step")
+        return loss
+
+    def warp_search(self, users, positives, candidates, *, check_indices: bool = True):
+        """
+        The misranked-negative search over ``candidates`` [B x tries] (lk_flexmf_warp_search):
+        (negatives int32 [B], counts int32 [B], weights float64 [B]) on the device.
+        """
+        lib = _native.require_gpu()
+        dev = self.dev
+        users, positives = _i32_dev(users, dev).reshape(-1), _i32_dev(positives, dev).reshape(-1)
+        candidates = _i32_dev(candidates, dev)
+        B = users.numel()
+        if candidates.dim() != 2 or candidates.shape[0] != B or positives.numel() != B:
+            raise ValueError("candidate table disagrees with the batch")
+        if check_indices:
+            self._check_indices(users, positives, candidates)
+        neg = torch.empty(B, dtype=torch.int32, device=dev)
+        count = torch.empty(B, dtype=torch.int32, device=dev)
+        weight = torch.empty(B, dtype=torch.float64, device=dev)
+        check(lib.lk_flexmf_warp_search(ctypes.byref(self._tables), _ptr(users), _ptr(positives),
+                                        _ptr(candidates), B, candidates.shape[1], _ptr(neg),
+                                        _ptr(count), _ptr(weight), _stream()),
+              "lk_flexmf_warp_search")
+        return neg, count, weight
+
+    def host_tables(self) -> dict:
+        "The four parameter tables as host arrays under Torch's ``state_dict`` names."
+        return {f"{name}.weight": None if t is None else
+                (t.cpu().numpy() if i < 2 else t.cpu().numpy().reshape(-1, 1))
+                for i, (name, t) in enumerate(zip(_FLEXMF_TABLES, self.param))}
+
+    def load_tables(self, state) -> None:
+        for name, t in zip(_FLEXMF_TABLES, self.param):
+            val = state.get(f"{name}.weight")
+            if t is not None and val is not None:
+                val = torch.as_tensor(np.asarray(val, dtype=np.float32)).reshape(t.shape)
+                t.copy_(val.to(self.dev))
+
+
+def flexmf_gather_batch(perm: torch.Tensor, all_users: torch.Tensor, all_items: torch.Tensor):
+    "(users, items) of one batch: ``all[perm]`` of both arrays (lk_flexmf_gather_batch)."
+    lib = _native.require_gpu()
+    assert perm.dtype == torch.int32 and perm.is_contiguous()
+    n = perm.numel()
+    users = torch.empty(n, dtype=torch.int32, device=perm.device)
+    items = torch.empty(n, dtype=torch.int32, device=perm.device)
+    check(lib.lk_flexmf_gather_batch(_ptr(perm), n, _ptr(all_users), _ptr(all_items),
+                                     _ptr(users), _ptr(items), _stream()),
+          "lk_flexmf_gather_batch")
+    return users, items

@@ -32,6 +32,27 @@ SOLVER_CG = 1
 SOLVER_AUTO = 2
 
 
+FLEXMF_LOSSES = {"logistic": 0, "pairwise": 1, "warp": 2}
+FLEXMF_ADAMW = 0
+FLEXMF_SPARSE_ADAM = 1
+FLEXMF_MAX_K = 256
+
+
+class FlexMFTables(ctypes.Structure):
+    "``lk_flexmf_tables``: u_embed, i_embed, u_bias, i_bias and their two moment tables."
+    _fields_ = [("param", c_void_p * 4), ("exp_avg", c_void_p * 4), ("exp_avg_sq", c_void_p * 4),
+                ("n_users", c_int64), ("n_items", c_int64), ("k", c_int32)]
+
+
+class FlexMFHyper(ctypes.Structure):
+    "``lk_flexmf_hyper``"
+    _fields_ = [("loss", c_int32), ("optimizer", c_int32), ("l2", c_int32), ("n_neg", c_int32),
+                ("pos_weight", ctypes.c_double), ("reg", ctypes.c_double),
+                ("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
+                ("eps", ctypes.c_double), ("bias_corr1", ctypes.c_double),
+                ("bias_corr2", ctypes.c_double)]
+
+
 class BackendUnavailable(RuntimeError):
     "The HIP extension or the GPU is missing; there is deliberately no CPU fallback."
 
@@ -192,6 +213,19 @@ def _declare(lib):
                     c_int64, vp, vp, vp]
         ),
         "lk_predict_errors": (c_int, [c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "lk_flexmf_sample_negatives": (
+            c_int, [vp, vp, c_int64, c_int64, vp, c_int64, c_int32, c_int, c_int, c_int32,
+                    ctypes.c_uint64, ctypes.c_uint64, vp, vp]
+        ),
+        "lk_flexmf_gather_batch": (c_int, [vp, c_int64, vp, vp, vp, vp, vp]),
+        "lk_flexmf_warp_search": (
+            c_int, [POINTER(FlexMFTables), vp, vp, vp, c_int64, c_int32, vp, vp, vp, vp]
+        ),
+        "lk_flexmf_step_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
+        "lk_flexmf_step": (
+            c_int, [POINTER(FlexMFTables), POINTER(FlexMFHyper), vp, vp, vp, vp, c_int64, vp, vp,
+                    vp, vp, vp]
+        ),
         "lk_als_implicit_half_epoch_host": (
             c_int,
             [vp, c_int, vp, vp, c_int64, c_int64, c_int32, vp, vp, vp, c_int32, vp],

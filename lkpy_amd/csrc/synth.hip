@@ -16,36 +16,11 @@
 // Short rows (<= 32): one thread per row, insertion sort in registers/scratch; longer rows (up
 // to LK_SYNTH_MAX_ROW = 4096): one wave per row, bitonic sort + prefix-max scan in LDS.
 #include "common.h"
+#include "philox.h"
 
 #define LK_SYNTH_MAX_ROW 4096
 
 namespace lk {
-
-struct Philox {
-    uint32_t k0, k1;
-    __device__ __forceinline__ void round(uint32_t (&c)[4], uint32_t ka, uint32_t kb) const
-    {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ ka;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ kb;
-        c[1] = (uint32_t)p1;
-        c[3] = (uint32_t)p0;
-        c[0] = n0;
-        c[2] = n2;
-    }
-    // Philox4x32-10: 128-bit counter -> 4 x 32 random bits
-    __device__ __forceinline__ void operator()(uint32_t (&c)[4]) const
-    {
-        uint32_t a = k0, b = k1;
-#pragma unroll
-        for (int r = 0; r < 10; ++r) {
-            round(c, a, b);
-            a += 0x9E3779B9u;
-            b += 0xBB67AE85u;
-        }
-    }
-};
 
 // rank in [0, n_items) with P(rank = r) ~ 1 / (r + 1)
 __device__ __forceinline__ int zipf_rank(uint64_t seed, int64_t row, uint32_t j, int64_t n_items,

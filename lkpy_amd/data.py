@@ -591,6 +591,46 @@ class _Matrix:
         return SparseRowArray.from_arrays(ds._indptr, ds._cols,
                                           shape=(ds.user_count, ds.item_count))
 
+    def _device_csr(self, dev=None):
+        "(offsets int64, columns int32) of the matrix on the device, uploaded once per matrix object"
+        import torch
+
+        from . import _device as D
+
+        dev = D.device(dev)
+        hit = self.__dict__.get("_dev_csr")
+        if hit is None or hit[0].device != dev:
+            ds = self._ds
+            hit = (torch.from_numpy(ds._indptr.astype(np.int64)).to(dev),
+                   torch.from_numpy(ds._cols).to(dev))
+            self.__dict__["_dev_csr"] = hit
+        return hit
+
+    def sample_negatives(self, rows, *, weighting: str = "uniform", n: int | None = None,
+                         verify: bool = True, max_attempts: int = 10, rng=None) -> np.ndarray:
+        """
+        ``MatrixRelationshipSet.sample_negatives`` (``_relationships.py:725-793``): for every
+        entry of ``rows`` a column (``n`` columns) the row has no interaction with, drawn
+        ``uniform`` or by ``popular`` (``popularity``) weighting, redrawn at most ``max_attempts``
+        times while it is one of the row's own; int32 of shape ``(len,)`` for ``n=None`` and
+        ``(len, n)`` otherwise.  Drawn on the device (lk_flexmf_sample_negatives) from a
+        counter-based stream keyed by ``rng``'s next raw value: the distribution is the
+        reference's, its bit stream is not.
+        """
+        from . import _device as D
+
+        rng = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
+        rows = np.require(rows, dtype=np.int32)
+        if rows.ndim != 1:
+            raise ValueError("rows must be one-dimensional")
+        if len(rows) and (rows.min() < 0 or rows.max() >= self._ds.user_count):
+            raise ValueError("row numbers outside the matrix")
+        indptr, cols = self._device_csr()
+        out = D.flexmf_sample_negatives(indptr, cols, self._ds.item_count, rows, n or 1, weighting,
+                                        int(rng.bit_generator.random_raw()), 0, verify=verify,
+                                        max_attempts=max_attempts).cpu().numpy()
+        return out.reshape(-1) if n is None else out.reshape(-1, n)
+
     def row_items(self, user_id) -> ItemList | None:
         ds = self._ds
         u = ds.users.number(user_id, missing=None)

@@ -1,0 +1,371 @@
+"""
+FlexMF implicit: mirror of ``lenskit.flexmf.FlexMFImplicitScorer`` / ``FlexMFImplicitConfig`` /
+``FlexMFImplicitTrainer`` / ``FlexMFWARPTrainer`` (src/lenskit/flexmf/_base.py:34-164,
+_implicit.py:32-415, _model.py, _training.py:39-358) -- matrix factorisation with biases,
+``score = b_u + b_i + p_u . q_i``, trained by minibatch Adam on logistic, pairwise (BPR) or WARP
+loss with sampled negatives.
+
+The reference runs a batch as a few dozen small Torch launches with two host round trips (the
+negative sampler is a host function, the WARP search copies its mask to the host in the loop).
+Here a whole epoch is queued on the device: the permutation is uploaded once, negatives are drawn
+by a counter-based generator in a kernel, forward / loss gradient / per-row gradient sums /
+optimiser update are the kernels of ``csrc/flexmf.hip``, the loss is accumulated on the device and
+read once per epoch.  The parameter initialisation is the reference's own (a CPU
+``torch.Generator`` seeded the same way), so the same seed starts from the same bits.
+
+Not here: the explicit-feedback FlexMF and LightGCN (``convolution_layers > 0`` validates, and
+``create_trainer`` raises ``NotImplementedError``).
+"""
+
+from __future__ import annotations
+
+from typing import Literal
+
+import numpy as np
+import torch
+from pydantic import BaseModel, NonNegativeInt, PositiveFloat, PositiveInt, model_validator
+
+from . import _device as D
+from . import _native
+from .als import _DeviceBacked, _scorer_state
+from .data import Dataset, ItemList, RecQuery, Vocabulary
+from .pipeline import Component
+from .training import ModelTrainer, TrainingOptions, UsesTrainer
+
+WARP_MAX_TRIES = 200  # MAX_TRIES, _implicit.py:26
+
+# What a preset stands for: the values it supplies for keys the caller leaves out.  "logistic"
+# is not in the reference's table (_implicit.py:32-46), but its pipelines/flexmf-logistic.toml
+# names it; it supplies nothing, because logistic loss is what the defaults already are.
+_BIAS_FREE = {"user_bias": False, "item_bias": False}
+PRESETS = {
+    "logistic": {},
+    "bpr": {"loss": "pairwise", **_BIAS_FREE},
+    "warp": {"loss": "warp", "negative_strategy": "misranked", **_BIAS_FREE},
+    "lightgcn": {"loss": "pairwise", "convolution_layers": 3, **_BIAS_FREE},
+}
+
+
+class FlexMFImplicitConfig(BaseModel):
+    """
+    The fields and defaults of the reference's configuration (_base.py:34-95,
+    _implicit.py:49-138), which pipeline files and callers address by name.
+    """
+
+    embedding_size: PositiveInt = 64
+    embedding_size_exp: PositiveInt | None = None
+    batch_size: int = 8 * 1024
+    learning_rate: float = 0.01
+    epochs: int = 10
+    regularization: float = 0.01
+    reg_method: Literal["AdamW", "L2"] | None = "AdamW"
+
+    preset: Literal["bpr", "warp", "lightgcn", "logistic"] | None = None
+    loss: Literal["logistic", "pairwise", "warp"] = "logistic"
+    negative_strategy: Literal["uniform", "popular", "misranked"] | None = None
+    negative_count: PositiveInt = 1
+    positive_weight: PositiveFloat = 1.0
+    user_bias: bool | None = None
+    item_bias: bool = True
+    convolution_layers: NonNegativeInt = 0
+
+    def selected_negative_strategy(self) -> str:
+        "the strategy in force: the configured one, else what the loss implies"
+        implied = "misranked" if self.loss == "warp" else "uniform"
+        return self.negative_strategy or implied
+
+    def selected_user_bias(self) -> bool:
+        "a user bias left unspecified is learned under logistic loss only (_implicit.py:223-228)"
+        return self.loss == "logistic" if self.user_bias is None else bool(self.user_bias)
+
+    @model_validator(mode="before")
+    @classmethod
+    def _fill_from_preset(cls, values):
+        if not isinstance(values, dict) or not values.get("preset"):
+            return values
+        name = values["preset"]
+        supplied = PRESETS.get(name)
+        if supplied is None:
+            raise ValueError(f"preset {name!r} is not one of {sorted(PRESETS)}")
+        filled = dict(values)
+        for key, default in supplied.items():
+            filled.setdefault(key, default)  # a key the caller gave is kept
+        return filled
+
+    @model_validator(mode="after")
+    def _check_negative_sampling(self):
+        strategy = self.selected_negative_strategy()
+        if self.loss == "warp" and strategy != "misranked":
+            raise ValueError(f"loss 'warp' weights each sample by the search for a misranked "
+                             f"negative; negative_strategy={strategy!r} cannot provide that")
+        if strategy == "misranked" and self.negative_count != 1:
+            raise ValueError(f"the misranked search yields one negative per positive; "
+                             f"negative_count={self.negative_count} is not available with it")
+        return self
+
+    def model_post_init(self, _ctx):
+        if self.embedding_size_exp is not None:
+            object.__setattr__(self, "embedding_size", 2 ** int(self.embedding_size_exp))
+        if self.embedding_size > _native.FLEXMF_MAX_K:
+            # fail at configuration time: the training kernels keep a row in at most four
+            # registers per lane (scoring, with its two bias columns, takes far wider operands)
+            raise ValueError(f"embedding_size {self.embedding_size} exceeds the device kernels' "
+                             f"limit of {_native.FLEXMF_MAX_K}")
+        if self.batch_size < 1:
+            raise ValueError("batch_size must be positive")
+
+
+class FlexMFImplicitScorer(UsesTrainer, Component):
+    """
+    Implicit-feedback FlexMF.  Learned state (host arrays, refreshed lazily from the device while
+    a trainer is live): ``user_embeddings`` [users x k], ``item_embeddings`` [items x k],
+    ``user_bias`` [users] | None, ``item_bias`` [items] | None, ``users``, ``items``.
+    """
+
+    config: FlexMFImplicitConfig
+    accepts_history_batch = True  # recommend_batch takes a lkpy_amd.basic.HistoryBatch
+
+    users: Vocabulary
+    items: Vocabulary
+    user_embeddings = _DeviceBacked()
+    item_embeddings = _DeviceBacked()
+    user_bias = _DeviceBacked()
+    item_bias = _DeviceBacked()
+
+    def create_trainer(self, data, options):
+        if self.config.convolution_layers > 0:
+            raise NotImplementedError(
+                "LightGCN (convolution_layers > 0) has no device trainer in lkpy_amd")
+        if self.config.selected_negative_strategy() == "misranked":
+            return FlexMFWARPTrainer(self, data, options)
+        return FlexMFImplicitTrainer(self, data, options)
+
+    def __getstate__(self):
+        return _scorer_state(self)
+
+    def __setstate__(self, state):
+        state = dict(state)
+        state.pop("_dev", None)
+        state.pop("_pending_sync", None)
+        self.__dict__.update(state)
+
+    # -- device state: the biases folded in as two extra columns -----------------------
+    def _device_state(self):
+        def upload():
+            d = D.device()
+            P, Q = self.user_embeddings, self.item_embeddings
+            one_u, one_i = np.ones((len(P), 1), np.float32), np.ones((len(Q), 1), np.float32)
+            bu = np.zeros_like(one_u) if self.user_bias is None else \
+                np.asarray(self.user_bias, np.float32).reshape(-1, 1)
+            bi = np.zeros_like(one_i) if self.item_bias is None else \
+                np.asarray(self.item_bias, np.float32).reshape(-1, 1)
+            # [p_u, 1, b_u] . [q_i, b_i, 1] = p_u . q_i + b_i + b_u
+            return {"device": d, "U": D.to_device_padded(np.hstack([P, one_u, bu]), d),
+                    "Q": D.to_device_padded(np.hstack([Q, bi, one_i]), d)}
+
+        return self._device_cache("model", upload, self.user_embeddings, self.item_embeddings,
+                                  self.user_bias, self.item_bias)
+
+    @property
+    def _score_k(self) -> int:
+        return self.config.embedding_size + 2
+
+    def _user_rows(self, nums: np.ndarray):
+        "device [B x KP] operand rows of the users ``nums`` (-1: unknown -> a zero row) + validity"
+        st = self._device_state()
+        nums = np.asarray(nums, dtype=np.int64)
+        valid = nums >= 0
+        idx = torch.from_numpy(np.where(valid, nums, 0)).to(st["device"])
+        return st["U"][idx].contiguous(), valid
+
+    # -- scoring (_base.py:116-164) -------------------------------------------------------
+    def __call__(self, query, items: ItemList) -> ItemList:
+        query = RecQuery.create(query)
+        u_row = None if query.user_id is None else self.users.number(query.user_id, missing=None)
+        if u_row is None:  # no fold-in from a history: an unknown user cannot be scored
+            return ItemList(items, scores=np.nan)
+        st = self._device_state()
+        u, _ = self._user_rows(np.array([u_row]))
+        all_scores = D.score_dense(u, st["Q"], self._score_k)[0].cpu().numpy()
+        item_nums = items.numbers(vocabulary=self.items, missing="negative")
+        mask = item_nums >= 0
+        scores = np.full(len(items), np.nan, dtype=np.float32)
+        scores[mask] = all_scores[item_nums[mask]]
+        return ItemList(items, scores=scores)
+
+    def recommend_batch(self, queries, n: int, *, exclude_history: bool = True,
+                        device_output: bool = False):
+        """
+        Dense scoring + top-N for many queries at once on ``lk_score_topk``, from the operands
+        ``__call__`` scores with.  ``queries``: a list of queries or a
+        :class:`lkpy_amd.basic.HistoryBatch`.  Returns (item numbers [B x n] with -1 padding,
+        scores [B x n] with NaN padding); an unknown user's row is all padding.
+        """
+        from .basic import HistoryBatch
+
+        if isinstance(queries, HistoryBatch) and not (
+                queries.items is self.items or queries.items == self.items):
+            queries = queries.queries()
+        st = self._device_state()
+        hist = None
+        if isinstance(queries, HistoryBatch):
+            if queries.users is self.users or queries.users == self.users:
+                nums = queries.user_nums.astype(np.int64)
+            else:
+                nums = self.users.numbers(queries.user_ids, missing="negative").astype(np.int64)
+            if exclude_history:
+                hist = queries.csr(with_values=False)
+        else:
+            qs = [RecQuery.create(q) for q in queries]
+            nums = np.full(len(qs), -1, dtype=np.int64)
+            idx, ptr = [], [0]
+            for i, q in enumerate(qs):
+                num = None if q.user_id is None else self.users.number(q.user_id, missing=None)
+                nums[i] = -1 if num is None else num
+                h = q.query_items
+                cnt = 0
+                if exclude_history and h is not None and len(h) > 0:
+                    ri = h.numbers(vocabulary=self.items, missing="negative")
+                    idx.append(np.sort(ri[ri >= 0]))
+                    cnt = len(idx[-1])
+                ptr.append(ptr[-1] + cnt)
+            if exclude_history:
+                indices = np.concatenate(idx).astype(np.int32) if idx else np.zeros(0, np.int32)
+                hist = D.DeviceCSR.from_arrays(np.asarray(ptr, np.int64), indices, None,
+                                               (len(qs), len(self.items)), st["device"])
+        u, valid = self._user_rows(nums)
+        if hist is not None:
+            idx, sc = D.score_topk(u, st["Q"], self._score_k, n, hist.indptr, hist.indices)
+        else:
+            idx, sc = D.score_topk(u, st["Q"], self._score_k, n)
+        if not valid.all():
+            bad = torch.from_numpy(np.flatnonzero(~valid)).to(st["device"])
+            idx[bad] = -1
+            sc[bad] = float("nan")
+        if device_output:
+            return idx, sc
+        return D.lists_to_host(idx, sc)
+
+
+def initial_tables(n_users: int, n_items: int, k: int, gen: torch.Generator, *, user_bias: bool,
+                   item_bias: bool, user_counts=None, item_counts=None) -> dict:
+    """
+    ``FlexMFModel.__init__`` + ``zero_users`` / ``zero_items`` (_model.py:73-120,
+    _training.py:108-112) on the host: ``normal_(std=0.1)`` from the CPU generator into u_bias,
+    i_bias, u_embed, i_embed in that order (present tables only), then the rows of users and
+    items without a training interaction zeroed.  Keys are Torch's ``state_dict`` names.
+    """
+    shapes = [("u_bias.weight", (n_users, 1), user_bias), ("i_bias.weight", (n_items, 1), item_bias),
+              ("u_embed.weight", (n_users, k), True), ("i_embed.weight", (n_items, k), True)]
+    out = {}
+    for name, shape, present in shapes:
+        out[name] = torch.empty(shape, dtype=torch.float32).normal_(0.0, 0.1, generator=gen) \
+            .numpy() if present else None
+    for names, counts in ((("u_bias.weight", "u_embed.weight"), user_counts),
+                          (("i_bias.weight", "i_embed.weight"), item_counts)):
+        if counts is not None:
+            for name in names:
+                if out[name] is not None:
+                    out[name][np.asarray(counts) == 0] = 0.0
+    return out
+
+
+class FlexMFImplicitTrainer(ModelTrainer):
+    "``FlexMFTrainerBase`` + ``FlexMFImplicitTrainer`` (_training.py:39-258, _implicit.py:164-290)."
+
+    def __init__(self, scorer: FlexMFImplicitScorer, data: Dataset, options: TrainingOptions):
+        self.scorer = scorer
+        self.config = cfg = scorer.config
+        # the NumPy generator first, then Torch's (_training.py:102-103): with a Generator as the
+        # seed the Torch seed is that generator's next draw
+        self.rng = options.random_generator()
+        self.torch_rng = options.random_generator(type="torch")
+        dev_name = options.configured_device()
+        self.dev = dev = D.device(None if dev_name in ("cuda", "cpu") else dev_name)
+
+        scorer.users, scorer.items = data.users, data.items
+        self.matrix = data.interactions().matrix()
+        ds = self.matrix._ds
+        self.n_users, self.n_items = data.user_count, data.item_count
+        self.n_samples = ds.interaction_count  # repeated pairs stay separate samples
+        tabs = initial_tables(
+            self.n_users, self.n_items, cfg.embedding_size, self.torch_rng,
+            user_bias=cfg.selected_user_bias(), item_bias=cfg.item_bias,
+            user_counts=np.diff(ds._indptr), item_counts=np.bincount(ds._cols,
+                                                                     minlength=self.n_items))
+        self.state = D.FlexMFState(
+            tabs["u_embed.weight"], tabs["i_embed.weight"], tabs["u_bias.weight"],
+            tabs["i_bias.weight"], loss=cfg.loss, reg_method=cfg.reg_method,
+            regularization=cfg.regularization, learning_rate=cfg.learning_rate,
+            negative_count=cfg.negative_count, positive_weight=cfg.positive_weight, dev=dev)
+        self.d_users = torch.from_numpy(ds._rows).to(dev)
+        self.d_items = torch.from_numpy(ds._cols).to(dev)
+        self.d_indptr, self.d_cols = self.matrix._device_csr(dev)
+        # the key of the negative sampler's counter-based stream
+        self.sample_key = int(self.rng.bit_generator.random_raw())
+        self.epochs_trained = 0
+        self._set_host(tabs)
+
+    def _set_host(self, tabs: dict):
+        s = self.scorer
+        s.__dict__.pop("_pending_sync", None)
+        s.user_embeddings, s.item_embeddings = tabs["u_embed.weight"], tabs["i_embed.weight"]
+        ub, ib = tabs["u_bias.weight"], tabs["i_bias.weight"]
+        s.user_bias = None if ub is None else ub.reshape(-1)
+        s.item_bias = None if ib is None else ib.reshape(-1)
+
+    def negatives(self, users: torch.Tensor, positives: torch.Tensor, counter: int):
+        "``scored_negatives`` (_implicit.py:276-290): (negatives [B x n], no weights)."
+        cfg = self.config
+        neg = D.flexmf_sample_negatives(self.d_indptr, self.d_cols, self.n_items, users,
+                                        cfg.negative_count, cfg.selected_negative_strategy(),
+                                        self.sample_key, counter)
+        return neg, None
+
+    def train_epoch(self) -> dict[str, float]:
+        bs = self.config.batch_size
+        perm = np.require(self.rng.permutation(self.n_samples), dtype=np.int32)
+        d_perm = torch.from_numpy(perm).to(self.dev)  # one upload per epoch
+        loss_sum = torch.zeros(1, dtype=torch.float32, device=self.dev)
+        batches = 0
+        for start in range(0, self.n_samples, bs):
+            users, items = D.flexmf_gather_batch(d_perm[start:start + bs], self.d_users,
+                                                 self.d_items)
+            neg, weights = self.negatives(users, items, (self.epochs_trained << 32) | batches)
+            self.state.step(users, items, neg, weights, loss_sum=loss_sum, check_indices=False)
+            batches += 1
+        self.epochs_trained += 1
+        # the tables stay in HBM; the host copies are refreshed on first read (_DeviceBacked)
+        self.scorer.__dict__["_pending_sync"] = self._sync
+        avg = float(loss_sum.item()) / max(batches, 1)  # the epoch's one synchronisation
+        return {"loss": avg}
+
+    def _sync(self):
+        self._set_host(self.state.host_tables())
+
+    def finalize(self):
+        self._sync()
+
+    def get_parameters(self):
+        return {k: v for k, v in self.state.host_tables().items() if v is not None}
+
+    def load_parameters(self, state) -> None:
+        self.state.load_tables(state)
+        self.scorer.__dict__["_pending_sync"] = self._sync
+
+
+class FlexMFWARPTrainer(FlexMFImplicitTrainer):
+    """
+    ``FlexMFWARPTrainer`` (_implicit.py:293-396).  The reference draws candidates ten at a time
+    for the rows still searching; candidates are independent draws, so the table of all
+    ``WARP_MAX_TRIES`` per sample drawn up front has the same distribution, and the search is a
+    deterministic function of it that scores only up to the stopping try.
+    """
+
+    def negatives(self, users, positives, counter):
+        cand = D.flexmf_sample_negatives(self.d_indptr, self.d_cols, self.n_items, users,
+                                         WARP_MAX_TRIES, "uniform", self.sample_key, counter)
+        neg, _count, weights = self.state.warp_search(users, positives, cand,
+                                                      check_indices=False)
+        # the losses that ignore the weights but ask for misranked negatives take them here too
+        return neg, (weights if self.config.loss == "warp" else None)

@@ -25,8 +25,30 @@ class TrainingOptions:
     rng: object = None
     environment: dict[str, str] = field(default_factory=dict)
 
-    def random_generator(self) -> np.random.Generator:
-        "``random_generator(seed)`` -> ``np.random.default_rng`` (src/lenskit/random.py:181-185)."
+    def random_generator(self, *, type: str = "numpy"):
+        """``random_generator(seed)`` -> ``np.random.default_rng`` (src/lenskit/random.py:181-185);
+        ``type="torch"``: a CPU ``torch.Generator`` seeded as src/lenskit/random.py:187-205 seeds
+        it -- an int directly, a ``SeedSequence`` (or a sequence of ints) by
+        ``generate_state(1)[0]``, a NumPy ``Generator`` by one int32-range draw, a
+        ``BitGenerator`` by ``random_raw()``; no seed: the generator as Torch constructs it."""
+        if type == "torch":
+            import torch
+
+            gen, seed = torch.Generator(), self.rng
+            if isinstance(seed, (int, np.integer)) and not isinstance(seed, bool):
+                gen.manual_seed(int(seed))
+            elif isinstance(seed, np.random.SeedSequence):
+                gen.manual_seed(int(seed.generate_state(1)[0]))
+            elif isinstance(seed, (list, tuple)):
+                gen.manual_seed(int(np.random.SeedSequence(seed).generate_state(1)[0]))
+            elif isinstance(seed, np.random.Generator):
+                i32 = np.iinfo(np.int32)
+                gen.manual_seed(int(seed.integers(i32.min, i32.max)))
+            elif isinstance(seed, np.random.BitGenerator):
+                gen.manual_seed(int(seed.random_raw()))
+            return gen
+        if type != "numpy":
+            raise ValueError(f"invalid RNG type {type}")
         if isinstance(self.rng, np.random.Generator):
             return self.rng
         return np.random.default_rng(self.rng)
