@@ -857,6 +857,53 @@ int lk_flexmf_step(const lk_flexmf_tables *tables, const lk_flexmf_hyper *hyper,
                    const double *d_weights, int64_t batch, void *d_ws, int32_t *d_slot,
                    float *d_loss, float *d_loss_sum, void *stream);
 
+/* ------------------------------------------------------------------------
+ * FlexMF explicit (csrc/flexmf.hip): the trainer of `lenskit.flexmf.FlexMFExplicitScorer`
+ * (src/lenskit/flexmf/_explicit.py:25-125) -- the same tables and optimisers, a rating per
+ * sample, squared error, no negatives.
+ * ---------------------------------------------------------------------- */
+#define LK_FLEXMF_MSE 3 /* lk_flexmf_hyper.loss of lk_flexmf_step_explicit */
+
+/* out[i] = all[perm[i]] of a float32 array: the ratings' companion of lk_flexmf_gather_batch
+ * (`make_batch` with `fields`, src/lenskit/flexmf/_training.py:350-358). */
+int lk_flexmf_gather_values(const int32_t *d_perm, int64_t n, const float *d_all, float *d_out,
+                            void *stream);
+
+/* One training step -- `FlexMFExplicitTrainer.train_batch` + `opt.step()`
+ * (src/lenskit/flexmf/_explicit.py:108-125, _model.py:145-198, _training.py:238-252).
+ * hyper->loss = LK_FLEXMF_MSE, hyper->n_neg = 0, pos_weight is ignored.  With
+ * pred = b_u + b_i + p_u . q_i and B = batch: the loss is mean (pred - r)^2 and *d_loss receives
+ * it WITHOUT the L2 term (the reference returns `loss`, not `loss_all`); each sample's score
+ * gradient is 2 (pred - r) / B.  hyper->l2 = 1 (reg_method "L2", the explicit default) adds
+ * reg * mean(b_u^2 + b_i^2 + |p_u| + |q_i|) -- norms, not squared norms -- to the objective: per
+ * occurrence in the batch reg x / (B |x|) to an embedding row x (0 where |x| = 0, as Torch
+ * gives) and 2 reg b / B to a bias, the same on the user and the item side (the implicit step
+ * halves the item side).  Optimiser, staging, the float64 per-row sums in sample order, d_slot
+ * and d_loss_sum: as lk_flexmf_step.  d_ratings: float32 [batch].  A batch may hold a user, or
+ * a (user, item) pair, any number of times.  The workspace has its own size function because
+ * lk_flexmf_step_workspace_bytes rejects n_neg = 0. */
+size_t lk_flexmf_step_explicit_workspace_bytes(int64_t batch, int32_t k);
+int lk_flexmf_step_explicit(const lk_flexmf_tables *tables, const lk_flexmf_hyper *hyper,
+                            const int32_t *d_users, const int32_t *d_items,
+                            const float *d_ratings, int64_t batch, void *d_ws, int32_t *d_slot,
+                            float *d_loss, float *d_loss_sum, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Ragged pair scoring for factor models (csrc/mf_pairs.hip): d_out[t] = the inner product over
+ * k columns of row d_user_rows[q] of d_users with row d_tgt_items[t] of d_items, for every t in
+ * [d_tgt_ptr[q], d_tgt_ptr[q + 1]) -- `FlexMFScorerBase.__call__`
+ * (src/lenskit/flexmf/_base.py:116-164) for n_queries queries in one launch, without a row of
+ * scores per user.  The operands are the padded matrices of lk_score_dense (leading dimensions
+ * multiples of 4 floats covering k rounded up to 4, bases 16-byte aligned).  d_tgt_ptr: int64
+ * [n_queries + 1], ascending from 0 to total.  A user row or a target outside its table (-1:
+ * unknown) gives NaN.  The summation order depends on k alone, so a score has the same bits
+ * whatever else the batch holds; no atomics.
+ * ---------------------------------------------------------------------- */
+int lk_mf_score_pairs(const float *d_users, int32_t ld_users, int64_t n_users,
+                      const float *d_items, int32_t ld_items, int64_t n_items, int32_t k,
+                      const int32_t *d_user_rows, int64_t n_queries, const int64_t *d_tgt_ptr,
+                      const int32_t *d_tgt_items, int64_t total, float *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1430,7 +1430,7 @@ def predict_errors(pred_ptr: torch.Tensor, pred_items: torch.Tensor | None,
 
 
 # ---------------------------------------------------------------------------------------
-# FlexMF implicit (csrc/flexmf.hip)
+# FlexMF implicit and explicit (csrc/flexmf.hip), ragged pair scoring (csrc/mf_pairs.hip)
 # ---------------------------------------------------------------------------------------
 
 _FLEXMF_TABLES = ("u_embed", "i_embed", "u_bias", "i_bias")
@@ -1473,6 +1473,8 @@ class FlexMFState:
     tables of each, the global step count and the step's scratch.  ``step`` is one
     ``train_batch`` + ``opt.step()`` (lk_flexmf_step) on explicit (users, positives, negatives
     [, weights]); ``warp_search`` is the misranked-negative search on an explicit candidate table.
+    With ``loss="mse"`` it is the FlexMF explicit model, stepped by ``step_explicit`` (users,
+    items, ratings: lk_flexmf_step_explicit).
     """
 
     def __init__(self, u_embed, i_embed, u_bias=None, i_bias=None, *, loss: str = "logistic",
@@ -1503,7 +1505,7 @@ class FlexMFState:
             self.param.append(t)
             self.exp_avg.append(None if t is None else torch.zeros_like(t))
             self.exp_avg_sq.append(None if t is None else torch.zeros_like(t))
-        if loss not in _native.FLEXMF_LOSSES:
+        if loss != "mse" and loss not in _native.FLEXMF_LOSSES:
             raise ValueError(f"unknown loss {loss}")
         if reg_method not in ("AdamW", "L2", None):
             raise ValueError(f"unknown regularization method {reg_method}")
@@ -1536,6 +1538,8 @@ class FlexMFState:
         "One training step; returns the batch loss (device, 1 element), nothing synchronised."
         lib = _native.require_gpu()
         dev = self.dev
+        if self.loss == "mse":
+            raise ValueError("a squared-error model is stepped by step_explicit")
         users, positives = _i32_dev(users, dev).reshape(-1), _i32_dev(positives, dev).reshape(-1)
         negatives = _i32_dev(negatives, dev).reshape(-1)
         B, n = users.numel(), self.negative_count
@@ -1567,6 +1571,40 @@ class FlexMFState:
                                  _ptr(positives), _ptr(negatives), _ptr(weights), B,
                                  _ptr(self._ws), _ptr(self._slot), _ptr(loss), _ptr(loss_sum),
                                  _stream()), "lk_flexmf_step")
+        return loss
+
+    def step_explicit(self, users, items, ratings, *, loss_sum=None,
+                      check_indices: bool = True) -> torch.Tensor:
+        """One squared-error step on (users, items, ratings); returns the batch's mean squared
+        error -- without the L2 term -- (device, 1 element), nothing synchronised."""
+        lib = _native.require_gpu()
+        dev = self.dev
+        if self.loss != "mse":
+            raise ValueError(f"step_explicit needs loss 'mse', not {self.loss!r}")
+        users, items = _i32_dev(users, dev).reshape(-1), _i32_dev(items, dev).reshape(-1)
+        ratings = torch.as_tensor(ratings).to(device=dev, dtype=torch.float32).reshape(-1)
+        ratings = ratings.contiguous()
+        B = users.numel()
+        if items.numel() != B or ratings.numel() != B or B < 1:
+            raise ValueError("batch arrays disagree in length")
+        if check_indices:
+            self._check_indices(users, items, items)
+        if self._ws is None or self._ws_batch < B:
+            self._ws = torch.empty(lib.lk_flexmf_step_explicit_workspace_bytes(B, self.k),
+                                   dtype=torch.uint8, device=dev)
+            self._ws_batch = B
+        self.steps += 1
+        h = _native.FlexMFHyper(
+            _native.FLEXMF_MSE,
+            _native.FLEXMF_ADAMW if self.reg_method == "AdamW" else _native.FLEXMF_SPARSE_ADAM,
+            int(self.reg_method == "L2"), 0, 1.0, self.regularization, self.learning_rate,
+            self.beta1, self.beta2, self.eps, 1.0 - self.beta1 ** self.steps,
+            1.0 - self.beta2 ** self.steps)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        check(lib.lk_flexmf_step_explicit(ctypes.byref(self._tables), ctypes.byref(h),
+                                          _ptr(users), _ptr(items), _ptr(ratings), B,
+                                          _ptr(self._ws), _ptr(self._slot), _ptr(loss),
+                                          _ptr(loss_sum), _stream()), "lk_flexmf_step_explicit")
         return loss
 
     def warp_search(self, users, positives, candidates, *, check_indices: bool = True):
@@ -1617,3 +1655,36 @@ def flexmf_gather_batch(perm: torch.Tensor, all_users: torch.Tensor, all_items: 
                                      _ptr(users), _ptr(items), _stream()),
           "lk_flexmf_gather_batch")
     return users, items
+
+
+def flexmf_gather_values(perm: torch.Tensor, all_values: torch.Tensor) -> torch.Tensor:
+    "``all_values[perm]`` of a float32 array, the ratings of one batch (lk_flexmf_gather_values)."
+    lib = _native.require_gpu()
+    assert perm.dtype == torch.int32 and perm.is_contiguous()
+    assert all_values.dtype == torch.float32 and all_values.is_contiguous()
+    out = torch.empty(perm.numel(), dtype=torch.float32, device=perm.device)
+    check(lib.lk_flexmf_gather_values(_ptr(perm), perm.numel(), _ptr(all_values), _ptr(out),
+                                      _stream()), "lk_flexmf_gather_values")
+    return out
+
+
+def mf_score_pairs(users: torch.Tensor, items: torch.Tensor, k: int, user_rows: torch.Tensor,
+                   tgt_ptr: torch.Tensor, tgt_items: torch.Tensor) -> torch.Tensor:
+    """
+    Ragged pair scores (lk_mf_score_pairs): ``users`` [U x KP] / ``items`` [I x KP] padded device
+    operands of inner width ``k``; query q is row ``user_rows[q]`` (int32) against the items
+    ``tgt_items[tgt_ptr[q]:tgt_ptr[q + 1]]`` (int64 offsets from 0, int32 items).  Returns f32
+    [len(tgt_items)] on the device, NaN where the user row or the item is -1.
+    """
+    lib = _native.require_gpu()
+    assert users.dtype == torch.float32 and users.is_contiguous() and users.dim() == 2
+    assert items.dtype == torch.float32 and items.is_contiguous() and items.dim() == 2
+    assert user_rows.dtype == torch.int32 and tgt_items.dtype == torch.int32
+    assert tgt_ptr.dtype == torch.int64 and tgt_ptr.numel() == user_rows.numel() + 1
+    assert user_rows.is_contiguous() and tgt_ptr.is_contiguous() and tgt_items.is_contiguous()
+    out = torch.empty(tgt_items.numel(), dtype=torch.float32, device=users.device)
+    check(lib.lk_mf_score_pairs(_ptr(users), users.shape[1], users.shape[0], _ptr(items),
+                                items.shape[1], items.shape[0], int(k), _ptr(user_rows),
+                                user_rows.numel(), _ptr(tgt_ptr), _ptr(tgt_items),
+                                tgt_items.numel(), _ptr(out), _stream()), "lk_mf_score_pairs")
+    return out

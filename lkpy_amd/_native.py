@@ -33,6 +33,7 @@ SOLVER_AUTO = 2
 
 
 FLEXMF_LOSSES = {"logistic": 0, "pairwise": 1, "warp": 2}
+FLEXMF_MSE = 3  # lk_flexmf_step_explicit's loss
 FLEXMF_ADAMW = 0
 FLEXMF_SPARSE_ADAM = 1
 FLEXMF_MAX_K = 256
@@ -225,6 +226,16 @@ def _declare(lib):
         "lk_flexmf_step": (
             c_int, [POINTER(FlexMFTables), POINTER(FlexMFHyper), vp, vp, vp, vp, c_int64, vp, vp,
                     vp, vp, vp]
+        ),
+        "lk_flexmf_gather_values": (c_int, [vp, c_int64, vp, vp, vp]),
+        "lk_flexmf_step_explicit_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+        "lk_flexmf_step_explicit": (
+            c_int, [POINTER(FlexMFTables), POINTER(FlexMFHyper), vp, vp, vp, c_int64, vp, vp, vp,
+                    vp, vp]
+        ),
+        "lk_mf_score_pairs": (
+            c_int, [vp, c_int32, c_int64, vp, c_int32, c_int64, c_int32, vp, c_int64, vp, vp,
+                    c_int64, vp, vp]
         ),
         "lk_als_implicit_half_epoch_host": (
             c_int,

@@ -27,6 +27,13 @@
 // The forward kernel therefore copies every row it gathers into scratch (batch x (2 + n_neg) rows:
 // 6 MB at batch 8192, k 64, one negative) BEFORE anything is written; the row-sum kernels read the
 // other side from that copy only, and a row's own old value is read by the one wave that owns it.
+//
+// FlexMF explicit (lk_flexmf_step_explicit) is the same step without negatives: a rating per
+// sample, squared error, and an L2 term whose weights are the same on both sides.  It has a
+// forward kernel and a row-sum kernel of its own (flexmf_forward_mse_kernel,
+// flexmf_rowsum_mse_kernel) and shares the sorts, the optimiser updates, the AdamW pass, the loss
+// kernel and the scratch layout (with no negatives: E = B) with the implicit step, whose kernels
+// are as they were.
 #include <math.h>
 
 #include "common.h"
@@ -121,6 +128,14 @@ __global__ __launch_bounds__(256) void flexmf_gather_kernel(
     const int32_t s = perm[i];
     users[i] = all_users[s];
     items[i] = all_items[s];
+}
+
+__global__ __launch_bounds__(256) void flexmf_gather_values_kernel(
+    const int32_t *__restrict__ perm, int64_t n, const float *__restrict__ all,
+    float *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = all[perm[i]];
 }
 
 // ---- WARP search ---------------------------------------------------------------------------
@@ -450,6 +465,130 @@ __global__ __launch_bounds__(64 * WPB) void flexmf_adamw_kernel(lk_flexmf_tables
     }
 }
 
+// ---- FlexMF explicit: squared error on (user, item, rating) -----------------------------------
+// pred = (b_u + b_i) + p_u . q_i;  loss = mean (pred - r)^2;  dL/dpred = 2 (pred - r) / B.
+// reg_method "L2" adds reg * mean(b_u^2 + b_i^2 + |p_u| + |q_i|): per occurrence reg x / (B |x|)
+// to an embedding row (0 at x = 0) and 2 reg b / B to a bias, the same on both sides.
+template <int KR>
+__global__ __launch_bounds__(64 * WPB) void flexmf_forward_mse_kernel(
+    lk_flexmf_tables T, Scalars H, const int32_t *__restrict__ users,
+    const int32_t *__restrict__ items, const float *__restrict__ ratings, int64_t B, Scratch W)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int k = T.k;
+    const int32_t u = users[b], i = items[b];
+    const float *P = T.param[0], *Q = T.param[1], *ub = T.param[2], *ib = T.param[3];
+    const float fB = (float)B;
+    float dot = 0.0f, pn = 0.0f, qn = 0.0f;
+#pragma unroll
+    for (int r = 0; r < KR; ++r) {
+        const int f = lane + 64 * r;
+        const bool ok = f < k;
+        const float p = ok ? P[(int64_t)u * k + f] : 0.0f;
+        const float q = ok ? Q[(int64_t)i * k + f] : 0.0f;
+        dot += p * q;
+        pn += p * p;
+        qn += q * q;
+        if (ok) {
+            W.Ps[b * k + f] = p;
+            W.Qs[b * k + f] = q;
+        }
+    }
+    const float pred = ((ub ? ub[u] : 0.0f) + (ib ? ib[i] : 0.0f)) + wave_sum(dot);
+    float c_user = 0.0f, c_item = 0.0f;
+    if (H.l2) {
+        const float pnorm = sqrtf(wave_sum(pn)), qnorm = sqrtf(wave_sum(qn));
+        c_user = pnorm > 0.0f ? H.reg / (fB * pnorm) : 0.0f;
+        c_item = qnorm > 0.0f ? H.reg / (fB * qnorm) : 0.0f;
+    }
+    if (lane == 0) {
+        const float diff = pred - ratings[b];
+        const float g = 2.0f * diff / fB;
+        W.g_item[b] = g;
+        W.gsum_user[b] = g;
+        W.c_item[b] = c_item;
+        W.c_user[b] = c_user;
+        W.ikey[0][b] = (uint32_t)i;
+        W.ival[0][b] = (uint32_t)b;
+        W.ukey[0][b] = (uint32_t)u;
+        W.uval[0][b] = (uint32_t)b;
+        W.lossv[b] = diff * diff / fB;  // the squared error alone: the L2 term is not reported
+    }
+}
+
+// one wave per touched row, either side: its samples in sample order, in float64
+template <int KR, bool ITEM, bool FUSED>
+__global__ __launch_bounds__(64 * WPB) void flexmf_rowsum_mse_kernel(
+    lk_flexmf_tables T, Scalars H, const uint32_t *__restrict__ skey,
+    const uint32_t *__restrict__ sval, int64_t B, Scratch W, int64_t g_off,
+    int32_t *__restrict__ slot)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t e0 = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
+    if (e0 >= B) return;
+    const uint32_t row = skey[e0];
+    if (e0 > 0 && skey[e0 - 1] == row) return;  // not the head of its row's run
+    const int k = T.k;
+    const float *staged = ITEM ? W.Ps : W.Qs;  // the other side, as it was before the step
+    const float *cvec = ITEM ? W.c_item : W.c_user;
+    const double cb1 = H.l2 ? (double)(2.0f * H.reg / (float)B) : 0.0;
+    double acc[KR];
+#pragma unroll
+    for (int r = 0; r < KR; ++r) acc[r] = 0.0;
+    double gb = 0.0, cself = 0.0, cbias = 0.0;
+    for (int64_t i = e0; i < B && skey[i] == row; ++i) {
+        const int64_t s = sval[i];
+        const double coef = (double)W.g_item[s];
+        const float *other = staged + s * k;
+#pragma unroll
+        for (int r = 0; r < KR; ++r) {
+            const int f = lane + 64 * r;
+            if (f < k) acc[r] += coef * (double)other[f];
+        }
+        gb += coef;
+        cself += (double)cvec[s];
+        cbias += cb1;
+    }
+    const int ti = ITEM ? 1 : 0, tb = ITEM ? 3 : 2;
+    float *X = T.param[ti] + (int64_t)row * k;
+#pragma unroll
+    for (int r = 0; r < KR; ++r) {
+        const int f = lane + 64 * r;
+        if (f < k) {
+            float x = X[f];
+            const float g = (float)(acc[r] + cself * (double)x);
+            if (FUSED) {
+                float *M = T.exp_avg[ti] + (int64_t)row * k, *V = T.exp_avg_sq[ti] + (int64_t)row * k;
+                float m = M[f], v = V[f];
+                sparse_adam(x, m, v, g, H);
+                X[f] = x;
+                M[f] = m;
+                V[f] = v;
+            } else {
+                W.G[(g_off + e0) * k + f] = g;
+            }
+        }
+    }
+    if (lane == 0) {
+        if (T.param[tb]) {
+            float x = T.param[tb][row];
+            const float g = (float)(gb + cbias * (double)x);
+            if (FUSED) {
+                float m = T.exp_avg[tb][row], v = T.exp_avg_sq[tb][row];
+                sparse_adam(x, m, v, g, H);
+                T.param[tb][row] = x;
+                T.exp_avg[tb][row] = m;
+                T.exp_avg_sq[tb][row] = v;
+            } else {
+                W.gb[g_off + e0] = g;
+            }
+        }
+        if (!FUSED) slot[(ITEM ? T.n_users : 0) + row] = (int32_t)(g_off + e0);
+    }
+}
+
 static size_t carve(char *base, size_t &off, size_t bytes, void **out)
 {
     if (base) *out = base + off;
@@ -539,6 +678,64 @@ static int step_impl(const lk_flexmf_tables &T, const Scalars &H, bool adamw_opt
     hipLaunchKernelGGL(flexmf_loss_kernel, dim3(1), dim3(256), 0, st, W.lossv, B, loss, loss_sum);
     LK_HIP_CHECK(hipGetLastError());
     return LK_OK;
+}
+
+template <int KR>
+static int step_mse_impl(const lk_flexmf_tables &T, const Scalars &H, bool adamw_opt,
+                         const int32_t *users, const int32_t *items, const float *ratings,
+                         int64_t B, void *ws, int32_t *slot, float *loss, float *loss_sum,
+                         hipStream_t st)
+{
+    Scratch W;
+    layout(static_cast<char *>(ws), B, 0, T.k, &W);
+    const dim3 blk(64 * WPB), grid((unsigned)((B + WPB - 1) / WPB));
+    hipLaunchKernelGGL((flexmf_forward_mse_kernel<KR>), grid, blk, 0, st, T, H, users, items,
+                       ratings, B, W);
+    int rc = radix_sort_pairs<uint32_t, uint32_t>(W.ukey[0], W.uval[0], W.ukey[1], W.uval[1],
+                                                  W.ukey[2], W.uval[2], B, 0,
+                                                  bits_for(T.n_users), W.sort_tmp, st);
+    if (rc != LK_OK) return rc;
+    rc = radix_sort_pairs<uint32_t, uint32_t>(W.ikey[0], W.ival[0], W.ikey[1], W.ival[1],
+                                              W.ikey[2], W.ival[2], B, 0, bits_for(T.n_items),
+                                              W.sort_tmp, st);
+    if (rc != LK_OK) return rc;
+    if (adamw_opt) {
+        hipLaunchKernelGGL((flexmf_rowsum_mse_kernel<KR, false, false>), grid, blk, 0, st, T, H,
+                           W.ukey[1], W.uval[1], B, W, (int64_t)0, slot);
+        hipLaunchKernelGGL((flexmf_rowsum_mse_kernel<KR, true, false>), grid, blk, 0, st, T, H,
+                           W.ikey[1], W.ival[1], B, W, B, slot);
+        const int64_t rows = T.n_users + T.n_items;
+        hipLaunchKernelGGL((flexmf_adamw_kernel<KR>), dim3((unsigned)((rows + WPB - 1) / WPB)),
+                           blk, 0, st, T, H, W, slot);
+    } else {
+        hipLaunchKernelGGL((flexmf_rowsum_mse_kernel<KR, false, true>), grid, blk, 0, st, T, H,
+                           W.ukey[1], W.uval[1], B, W, (int64_t)0, slot);
+        hipLaunchKernelGGL((flexmf_rowsum_mse_kernel<KR, true, true>), grid, blk, 0, st, T, H,
+                           W.ikey[1], W.ival[1], B, W, B, slot);
+    }
+    hipLaunchKernelGGL(flexmf_loss_kernel, dim3(1), dim3(256), 0, st, W.lossv, B, loss, loss_sum);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
+// the hyper-parameters rounded to float32 where Torch's optimisers round them
+static Scalars scalars_of(const lk_flexmf_hyper &h)
+{
+    Scalars H{};
+    H.loss = h.loss;
+    H.l2 = h.l2 ? 1 : 0;
+    H.n_neg = h.n_neg;
+    H.pos_weight = (float)h.pos_weight;
+    H.reg = (float)h.reg;
+    H.omb1 = (float)(1.0 - h.beta1);
+    H.omb2 = (float)(1.0 - h.beta2);
+    H.eps = (float)h.eps;
+    H.sparse_step = (float)(h.lr * sqrt(h.bias_corr2) / h.bias_corr1);
+    H.decay = (float)(1.0 - h.lr * h.reg);
+    H.beta2 = (float)h.beta2;
+    H.adamw_step = (float)(h.lr / h.bias_corr1);
+    H.bc2_sqrt = (float)sqrt(h.bias_corr2);
+    return H;
 }
 
 }  // namespace fx
@@ -638,20 +835,7 @@ extern "C" int lk_flexmf_step(const lk_flexmf_tables *tables, const lk_flexmf_hy
     for (int t = 0; t < 4; ++t)
         LK_REQUIRE(!tables->param[t] || (tables->exp_avg[t] && tables->exp_avg_sq[t]),
                    "lk_flexmf_step: table %d has no optimiser state", t);
-    lk::fx::Scalars H{};
-    H.loss = h.loss;
-    H.l2 = h.l2 ? 1 : 0;
-    H.n_neg = h.n_neg;
-    H.pos_weight = (float)h.pos_weight;
-    H.reg = (float)h.reg;
-    H.omb1 = (float)(1.0 - h.beta1);
-    H.omb2 = (float)(1.0 - h.beta2);
-    H.eps = (float)h.eps;
-    H.sparse_step = (float)(h.lr * sqrt(h.bias_corr2) / h.bias_corr1);
-    H.decay = (float)(1.0 - h.lr * h.reg);
-    H.beta2 = (float)h.beta2;
-    H.adamw_step = (float)(h.lr / h.bias_corr1);
-    H.bc2_sqrt = (float)sqrt(h.bias_corr2);
+    const lk::fx::Scalars H = lk::fx::scalars_of(h);
     const bool aw = h.optimizer == LK_FLEXMF_ADAMW;
     hipStream_t st = lk::as_stream(stream);
     const int kr = (tables->k + 63) / 64;
@@ -663,4 +847,61 @@ extern "C" int lk_flexmf_step(const lk_flexmf_tables *tables, const lk_flexmf_hy
                                     d_slot, d_loss, d_loss_sum, st);
     return lk::fx::step_impl<4>(*tables, H, aw, d_users, d_pos, d_neg, d_weights, batch, d_ws,
                                 d_slot, d_loss, d_loss_sum, st);
+}
+
+extern "C" int lk_flexmf_gather_values(const int32_t *d_perm, int64_t n, const float *d_all,
+                                       float *d_out, void *stream)
+{
+    LK_REQUIRE(n >= 0, "lk_flexmf_gather_values: bad length");
+    if (n == 0) return LK_OK;
+    LK_REQUIRE(d_perm && d_all && d_out, "lk_flexmf_gather_values: null pointer");
+    hipLaunchKernelGGL(lk::fx::flexmf_gather_values_kernel, dim3((unsigned)((n + 255) / 256)),
+                       dim3(256), 0, lk::as_stream(stream), d_perm, n, d_all, d_out);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
+extern "C" size_t lk_flexmf_step_explicit_workspace_bytes(int64_t batch, int32_t k)
+{
+    if (batch < 1 || k < 1 || k > LK_FLEXMF_MAX_K) return 0;
+    return lk::fx::layout(nullptr, batch, 0, k, nullptr);
+}
+
+extern "C" int lk_flexmf_step_explicit(const lk_flexmf_tables *tables,
+                                       const lk_flexmf_hyper *hyper, const int32_t *d_users,
+                                       const int32_t *d_items, const float *d_ratings,
+                                       int64_t batch, void *d_ws, int32_t *d_slot, float *d_loss,
+                                       float *d_loss_sum, void *stream)
+{
+    int rc = lk::fx::check_tables(tables, "lk_flexmf_step_explicit");
+    if (rc != LK_OK) return rc;
+    LK_REQUIRE(hyper, "lk_flexmf_step_explicit: null hyper-parameters");
+    const lk_flexmf_hyper &h = *hyper;
+    LK_REQUIRE(h.loss == LK_FLEXMF_MSE && h.n_neg == 0,
+               "lk_flexmf_step_explicit: takes loss LK_FLEXMF_MSE and n_neg 0 (got %d, %d)",
+               h.loss, h.n_neg);
+    LK_REQUIRE(h.optimizer == LK_FLEXMF_ADAMW || h.optimizer == LK_FLEXMF_SPARSE_ADAM,
+               "lk_flexmf_step_explicit: unknown optimizer %d", h.optimizer);
+    LK_REQUIRE(batch >= 1 && batch < ((int64_t)1 << 30), "lk_flexmf_step_explicit: bad batch size");
+    LK_REQUIRE(d_users && d_items && d_ratings && d_ws && d_loss,
+               "lk_flexmf_step_explicit: null pointer");
+    LK_REQUIRE(h.optimizer != LK_FLEXMF_ADAMW || d_slot,
+               "lk_flexmf_step_explicit: AdamW needs d_slot");
+    LK_REQUIRE(h.bias_corr1 > 0.0 && h.bias_corr2 > 0.0,
+               "lk_flexmf_step_explicit: bad bias correction");
+    for (int t = 0; t < 4; ++t)
+        LK_REQUIRE(!tables->param[t] || (tables->exp_avg[t] && tables->exp_avg_sq[t]),
+                   "lk_flexmf_step_explicit: table %d has no optimiser state", t);
+    const lk::fx::Scalars H = lk::fx::scalars_of(h);
+    const bool aw = h.optimizer == LK_FLEXMF_ADAMW;
+    hipStream_t st = lk::as_stream(stream);
+    const int kr = (tables->k + 63) / 64;
+    if (kr == 1)
+        return lk::fx::step_mse_impl<1>(*tables, H, aw, d_users, d_items, d_ratings, batch, d_ws,
+                                        d_slot, d_loss, d_loss_sum, st);
+    if (kr == 2)
+        return lk::fx::step_mse_impl<2>(*tables, H, aw, d_users, d_items, d_ratings, batch, d_ws,
+                                        d_slot, d_loss, d_loss_sum, st);
+    return lk::fx::step_mse_impl<4>(*tables, H, aw, d_users, d_items, d_ratings, batch, d_ws,
+                                    d_slot, d_loss, d_loss_sum, st);
 }

@@ -1,5 +1,5 @@
 """
-FlexMF implicit: mirror of ``lenskit.flexmf.FlexMFImplicitScorer`` / ``FlexMFImplicitConfig`` /
+FlexMF: mirror of ``lenskit.flexmf.FlexMFImplicitScorer`` / ``FlexMFImplicitConfig`` /
 ``FlexMFImplicitTrainer`` / ``FlexMFWARPTrainer`` (src/lenskit/flexmf/_base.py:34-164,
 _implicit.py:32-415, _model.py, _training.py:39-358) -- matrix factorisation with biases,
 ``score = b_u + b_i + p_u . q_i``, trained by minibatch Adam on logistic, pairwise (BPR) or WARP
@@ -13,8 +13,14 @@ optimiser update are the kernels of ``csrc/flexmf.hip``, the loss is accumulated
 read once per epoch.  The parameter initialisation is the reference's own (a CPU
 ``torch.Generator`` seeded the same way), so the same seed starts from the same bits.
 
-Not here: the explicit-feedback FlexMF and LightGCN (``convolution_layers > 0`` validates, and
-``create_trainer`` raises ``NotImplementedError``).
+FlexMF explicit -- ``FlexMFExplicitScorer`` / ``FlexMFExplicitConfig`` / ``FlexMFExplicitTrainer``
+(_explicit.py:25-125) -- is the same model with both biases and a global one,
+``score = g + b_u + b_i + p_u . q_i``, trained on squared error against the centred ratings
+(``lk_flexmf_step_explicit``); it predicts the ratings of ragged (user, item) lists through
+``lk_mf_score_pairs`` instead of forming a row of scores per user.
+
+Not here: LightGCN (``convolution_layers > 0`` validates, and ``create_trainer`` raises
+``NotImplementedError``).
 """
 
 from __future__ import annotations
@@ -46,11 +52,8 @@ PRESETS = {
 }
 
 
-class FlexMFImplicitConfig(BaseModel):
-    """
-    The fields and defaults of the reference's configuration (_base.py:34-95,
-    _implicit.py:49-138), which pipeline files and callers address by name.
-    """
+class FlexMFConfigBase(BaseModel):
+    "``FlexMFConfigBase`` (_base.py:34-95): what the implicit and the explicit model share."
 
     embedding_size: PositiveInt = 64
     embedding_size_exp: PositiveInt | None = None
@@ -59,6 +62,31 @@ class FlexMFImplicitConfig(BaseModel):
     epochs: int = 10
     regularization: float = 0.01
     reg_method: Literal["AdamW", "L2"] | None = "AdamW"
+
+    def model_post_init(self, _ctx):
+        if self.embedding_size_exp is not None:
+            object.__setattr__(self, "embedding_size", 2 ** int(self.embedding_size_exp))
+        if self.embedding_size > _native.FLEXMF_MAX_K:
+            # fail at configuration time: the training kernels keep a row in at most four
+            # registers per lane (scoring, with its bias columns, takes far wider operands)
+            raise ValueError(f"embedding_size {self.embedding_size} exceeds the device kernels' "
+                             f"limit of {_native.FLEXMF_MAX_K}")
+        if self.batch_size < 1:
+            raise ValueError("batch_size must be positive")
+
+
+class FlexMFExplicitConfig(FlexMFConfigBase):
+    "``FlexMFExplicitConfig`` (_explicit.py:25-35): stronger regularisation, as an explicit L2 term."
+
+    regularization: float = 0.1
+    reg_method: Literal["AdamW", "L2"] | None = "L2"
+
+
+class FlexMFImplicitConfig(FlexMFConfigBase):
+    """
+    The fields and defaults of the reference's configuration (_base.py:34-95,
+    _implicit.py:49-138), which pipeline files and callers address by name.
+    """
 
     preset: Literal["bpr", "warp", "lightgcn", "logistic"] | None = None
     loss: Literal["logistic", "pairwise", "warp"] = "logistic"
@@ -103,26 +131,16 @@ class FlexMFImplicitConfig(BaseModel):
                              f"negative_count={self.negative_count} is not available with it")
         return self
 
-    def model_post_init(self, _ctx):
-        if self.embedding_size_exp is not None:
-            object.__setattr__(self, "embedding_size", 2 ** int(self.embedding_size_exp))
-        if self.embedding_size > _native.FLEXMF_MAX_K:
-            # fail at configuration time: the training kernels keep a row in at most four
-            # registers per lane (scoring, with its two bias columns, takes far wider operands)
-            raise ValueError(f"embedding_size {self.embedding_size} exceeds the device kernels' "
-                             f"limit of {_native.FLEXMF_MAX_K}")
-        if self.batch_size < 1:
-            raise ValueError("batch_size must be positive")
 
-
-class FlexMFImplicitScorer(UsesTrainer, Component):
+class FlexMFScorerBase(UsesTrainer, Component):
     """
-    Implicit-feedback FlexMF.  Learned state (host arrays, refreshed lazily from the device while
-    a trainer is live): ``user_embeddings`` [users x k], ``item_embeddings`` [items x k],
-    ``user_bias`` [users] | None, ``item_bias`` [items] | None, ``users``, ``items``.
+    What the FlexMF scorers share (``FlexMFScorerBase``, _base.py:98-164).  Learned state (host
+    arrays, refreshed lazily from the device while a trainer is live): ``user_embeddings``
+    [users x k], ``item_embeddings`` [items x k], ``user_bias`` [users] | None, ``item_bias``
+    [items] | None, ``users``, ``items``.  On the device the biases are extra columns of the two
+    operand matrices (``_bias_columns``), so that a score is one inner product.
     """
 
-    config: FlexMFImplicitConfig
     accepts_history_batch = True  # recommend_batch takes a lkpy_amd.basic.HistoryBatch
 
     users: Vocabulary
@@ -131,14 +149,6 @@ class FlexMFImplicitScorer(UsesTrainer, Component):
     item_embeddings = _DeviceBacked()
     user_bias = _DeviceBacked()
     item_bias = _DeviceBacked()
-
-    def create_trainer(self, data, options):
-        if self.config.convolution_layers > 0:
-            raise NotImplementedError(
-                "LightGCN (convolution_layers > 0) has no device trainer in lkpy_amd")
-        if self.config.selected_negative_strategy() == "misranked":
-            return FlexMFWARPTrainer(self, data, options)
-        return FlexMFImplicitTrainer(self, data, options)
 
     def __getstate__(self):
         return _scorer_state(self)
@@ -149,7 +159,11 @@ class FlexMFImplicitScorer(UsesTrainer, Component):
         state.pop("_pending_sync", None)
         self.__dict__.update(state)
 
-    # -- device state: the biases folded in as two extra columns -----------------------
+    # -- device state: the biases folded in as extra columns ----------------------------
+    def _bias_columns(self, one_u, bu, one_i, bi):
+        "(user columns, item columns) behind the embeddings: [p_u, 1, b_u] . [q_i, b_i, 1]"
+        return [one_u, bu], [bi, one_i]
+
     def _device_state(self):
         def upload():
             d = D.device()
@@ -159,9 +173,9 @@ class FlexMFImplicitScorer(UsesTrainer, Component):
                 np.asarray(self.user_bias, np.float32).reshape(-1, 1)
             bi = np.zeros_like(one_i) if self.item_bias is None else \
                 np.asarray(self.item_bias, np.float32).reshape(-1, 1)
-            # [p_u, 1, b_u] . [q_i, b_i, 1] = p_u . q_i + b_i + b_u
-            return {"device": d, "U": D.to_device_padded(np.hstack([P, one_u, bu]), d),
-                    "Q": D.to_device_padded(np.hstack([Q, bi, one_i]), d)}
+            ucols, icols = self._bias_columns(one_u, bu, one_i, bi)
+            return {"device": d, "U": D.to_device_padded(np.hstack([P, *ucols]), d),
+                    "Q": D.to_device_padded(np.hstack([Q, *icols]), d)}
 
         return self._device_cache("model", upload, self.user_embeddings, self.item_embeddings,
                                   self.user_bias, self.item_bias)
@@ -177,21 +191,6 @@ class FlexMFImplicitScorer(UsesTrainer, Component):
         valid = nums >= 0
         idx = torch.from_numpy(np.where(valid, nums, 0)).to(st["device"])
         return st["U"][idx].contiguous(), valid
-
-    # -- scoring (_base.py:116-164) -------------------------------------------------------
-    def __call__(self, query, items: ItemList) -> ItemList:
-        query = RecQuery.create(query)
-        u_row = None if query.user_id is None else self.users.number(query.user_id, missing=None)
-        if u_row is None:  # no fold-in from a history: an unknown user cannot be scored
-            return ItemList(items, scores=np.nan)
-        st = self._device_state()
-        u, _ = self._user_rows(np.array([u_row]))
-        all_scores = D.score_dense(u, st["Q"], self._score_k)[0].cpu().numpy()
-        item_nums = items.numbers(vocabulary=self.items, missing="negative")
-        mask = item_nums >= 0
-        scores = np.full(len(items), np.nan, dtype=np.float32)
-        scores[mask] = all_scores[item_nums[mask]]
-        return ItemList(items, scores=scores)
 
     def recommend_batch(self, queries, n: int, *, exclude_history: bool = True,
                         device_output: bool = False):
@@ -247,6 +246,109 @@ class FlexMFImplicitScorer(UsesTrainer, Component):
         return D.lists_to_host(idx, sc)
 
 
+class FlexMFImplicitScorer(FlexMFScorerBase):
+    "Implicit-feedback FlexMF: ``score = b_u + b_i + p_u . q_i``, either bias optional."
+
+    config: FlexMFImplicitConfig
+
+    def create_trainer(self, data, options):
+        if self.config.convolution_layers > 0:
+            raise NotImplementedError(
+                "LightGCN (convolution_layers > 0) has no device trainer in lkpy_amd")
+        if self.config.selected_negative_strategy() == "misranked":
+            return FlexMFWARPTrainer(self, data, options)
+        return FlexMFImplicitTrainer(self, data, options)
+
+    # -- scoring (_base.py:116-164) -------------------------------------------------------
+    def __call__(self, query, items: ItemList) -> ItemList:
+        query = RecQuery.create(query)
+        u_row = None if query.user_id is None else self.users.number(query.user_id, missing=None)
+        if u_row is None:  # no fold-in from a history: an unknown user cannot be scored
+            return ItemList(items, scores=np.nan)
+        st = self._device_state()
+        u, _ = self._user_rows(np.array([u_row]))
+        all_scores = D.score_dense(u, st["Q"], self._score_k)[0].cpu().numpy()
+        item_nums = items.numbers(vocabulary=self.items, missing="negative")
+        mask = item_nums >= 0
+        scores = np.full(len(items), np.nan, dtype=np.float32)
+        scores[mask] = all_scores[item_nums[mask]]
+        return ItemList(items, scores=scores)
+
+
+class FlexMFExplicitScorer(FlexMFScorerBase):
+    """
+    Explicit-feedback FlexMF (_explicit.py:38-55): ``score = g + b_u + b_i + p_u . q_i`` with the
+    global bias ``g`` = the float32 mean of the training ratings.  Ratings are predicted for
+    ragged (user, item) lists by ``lk_mf_score_pairs``: ``__call__`` is ``score_batch`` with one
+    query, so the two agree bit for bit.
+    """
+
+    config: FlexMFExplicitConfig
+    global_bias: float
+
+    def create_trainer(self, data, options):
+        return FlexMFExplicitTrainer(self, data, options)
+
+    def _bias_columns(self, one_u, bu, one_i, bi):
+        # [p_u, 1, b_u, 1] . [q_i, b_i, 1, g]: g is a float32 value (the mean's), carried exactly
+        g = np.full_like(one_i, np.float32(self.global_bias))
+        return [one_u, bu, one_u], [bi, one_i, g]
+
+    @property
+    def _score_k(self) -> int:
+        return self.config.embedding_size + 3
+
+    def score_pairs(self, user_nums, tgt_ptr, item_nums, *, device_output: bool = False):
+        """
+        Scores by number: query q is user ``user_nums[q]`` against the items
+        ``item_nums[tgt_ptr[q]:tgt_ptr[q + 1]]`` (-1: unknown -> NaN).  One upload, one
+        ``lk_mf_score_pairs`` launch, one download (none with ``device_output``).
+        """
+        st = self._device_state()
+        user_nums = np.ascontiguousarray(user_nums, dtype=np.int32).reshape(-1)
+        tgt_ptr = np.ascontiguousarray(tgt_ptr, dtype=np.int64).reshape(-1)
+        item_nums = np.ascontiguousarray(item_nums, dtype=np.int32).reshape(-1)
+        nq, total = len(user_nums), len(item_nums)
+        if len(tgt_ptr) != nq + 1 or tgt_ptr[0] != 0 or tgt_ptr[-1] != total or \
+                (np.diff(tgt_ptr) < 0).any():
+            raise ValueError("tgt_ptr must ascend from 0 to len(item_nums), one entry per query "
+                             "and one more")
+        if total == 0:
+            empty = np.zeros(0, np.float32)
+            return torch.from_numpy(empty).to(st["device"]) if device_output else empty
+        # one upload: offsets (int64) | user rows | item numbers (int32)
+        packed = np.empty(2 * (nq + 1) + nq + total, np.int32)
+        packed[:2 * (nq + 1)] = tgt_ptr.view(np.int32)
+        packed[2 * (nq + 1):2 * (nq + 1) + nq] = user_nums
+        packed[2 * (nq + 1) + nq:] = item_nums
+        d_packed = torch.from_numpy(packed).to(st["device"])
+        out = D.mf_score_pairs(st["U"], st["Q"], self._score_k,
+                               d_packed[2 * (nq + 1):2 * (nq + 1) + nq],
+                               d_packed[:2 * (nq + 1)].view(torch.int64),
+                               d_packed[2 * (nq + 1) + nq:])
+        return out if device_output else out.cpu().numpy()
+
+    def score_batch(self, queries, item_lists) -> list[ItemList]:
+        "``__call__`` for many queries: one vocabulary pass, one launch, the same bits."
+        qs = [RecQuery.create(q) for q in queries]
+        user_nums = np.full(len(qs), -1, dtype=np.int32)
+        for i, q in enumerate(qs):
+            num = None if q.user_id is None else self.users.number(q.user_id, missing=None)
+            if num is not None:
+                user_nums[i] = num
+        ptr = np.zeros(len(qs) + 1, np.int64)
+        np.cumsum([len(il) for il in item_lists], out=ptr[1:])
+        ids = [il.ids() for il in item_lists if len(il)]
+        nums = self.items.numbers(np.concatenate(ids), missing="negative") if ids else \
+            np.zeros(0, np.int32)
+        scores = self.score_pairs(user_nums, ptr, nums)
+        return [ItemList(il, scores=scores[ptr[i]:ptr[i + 1]])
+                for i, il in enumerate(item_lists)]
+
+    def __call__(self, query, items: ItemList) -> ItemList:
+        return self.score_batch([query], [items])[0]
+
+
 def initial_tables(n_users: int, n_items: int, k: int, gen: torch.Generator, *, user_bias: bool,
                    item_bias: bool, user_counts=None, item_counts=None) -> dict:
     """
@@ -270,12 +372,17 @@ def initial_tables(n_users: int, n_items: int, k: int, gen: torch.Generator, *, 
     return out
 
 
-class FlexMFImplicitTrainer(ModelTrainer):
-    "``FlexMFTrainerBase`` + ``FlexMFImplicitTrainer`` (_training.py:39-258, _implicit.py:164-290)."
+class FlexMFTrainerBase(ModelTrainer):
+    """
+    ``FlexMFTrainerBase`` (_training.py:39-258): seeding, initialisation and the epoch loop on the
+    device.  A subclass says which biases the model has, builds its ``FlexMFState``, uploads what
+    its samples carry (``prepare_data``) and queues one batch (``train_batch``).
+    """
 
-    def __init__(self, scorer: FlexMFImplicitScorer, data: Dataset, options: TrainingOptions):
+    def __init__(self, scorer, data: Dataset, options: TrainingOptions):
         self.scorer = scorer
         self.config = cfg = scorer.config
+        self.check_data(data)
         # the NumPy generator first, then Torch's (_training.py:102-103): with a Generator as the
         # seed the Torch seed is that generator's next draw
         self.rng = options.random_generator()
@@ -288,23 +395,21 @@ class FlexMFImplicitTrainer(ModelTrainer):
         ds = self.matrix._ds
         self.n_users, self.n_items = data.user_count, data.item_count
         self.n_samples = ds.interaction_count  # repeated pairs stay separate samples
+        user_bias, item_bias = self.model_biases()
         tabs = initial_tables(
             self.n_users, self.n_items, cfg.embedding_size, self.torch_rng,
-            user_bias=cfg.selected_user_bias(), item_bias=cfg.item_bias,
+            user_bias=user_bias, item_bias=item_bias,
             user_counts=np.diff(ds._indptr), item_counts=np.bincount(ds._cols,
                                                                      minlength=self.n_items))
-        self.state = D.FlexMFState(
-            tabs["u_embed.weight"], tabs["i_embed.weight"], tabs["u_bias.weight"],
-            tabs["i_bias.weight"], loss=cfg.loss, reg_method=cfg.reg_method,
-            regularization=cfg.regularization, learning_rate=cfg.learning_rate,
-            negative_count=cfg.negative_count, positive_weight=cfg.positive_weight, dev=dev)
+        self.state = self.create_state(tabs)
         self.d_users = torch.from_numpy(ds._rows).to(dev)
         self.d_items = torch.from_numpy(ds._cols).to(dev)
-        self.d_indptr, self.d_cols = self.matrix._device_csr(dev)
-        # the key of the negative sampler's counter-based stream
-        self.sample_key = int(self.rng.bit_generator.random_raw())
+        self.prepare_data(ds)
         self.epochs_trained = 0
         self._set_host(tabs)
+
+    def check_data(self, data: Dataset) -> None:
+        "what the model needs of the data, said before any device work"
 
     def _set_host(self, tabs: dict):
         s = self.scorer
@@ -314,14 +419,6 @@ class FlexMFImplicitTrainer(ModelTrainer):
         s.user_bias = None if ub is None else ub.reshape(-1)
         s.item_bias = None if ib is None else ib.reshape(-1)
 
-    def negatives(self, users: torch.Tensor, positives: torch.Tensor, counter: int):
-        "``scored_negatives`` (_implicit.py:276-290): (negatives [B x n], no weights)."
-        cfg = self.config
-        neg = D.flexmf_sample_negatives(self.d_indptr, self.d_cols, self.n_items, users,
-                                        cfg.negative_count, cfg.selected_negative_strategy(),
-                                        self.sample_key, counter)
-        return neg, None
-
     def train_epoch(self) -> dict[str, float]:
         bs = self.config.batch_size
         perm = np.require(self.rng.permutation(self.n_samples), dtype=np.int32)
@@ -329,10 +426,7 @@ class FlexMFImplicitTrainer(ModelTrainer):
         loss_sum = torch.zeros(1, dtype=torch.float32, device=self.dev)
         batches = 0
         for start in range(0, self.n_samples, bs):
-            users, items = D.flexmf_gather_batch(d_perm[start:start + bs], self.d_users,
-                                                 self.d_items)
-            neg, weights = self.negatives(users, items, (self.epochs_trained << 32) | batches)
-            self.state.step(users, items, neg, weights, loss_sum=loss_sum, check_indices=False)
+            self.train_batch(d_perm[start:start + bs], batches, loss_sum)
             batches += 1
         self.epochs_trained += 1
         # the tables stay in HBM; the host copies are refreshed on first read (_DeviceBacked)
@@ -352,6 +446,84 @@ class FlexMFImplicitTrainer(ModelTrainer):
     def load_parameters(self, state) -> None:
         self.state.load_tables(state)
         self.scorer.__dict__["_pending_sync"] = self._sync
+
+
+class FlexMFImplicitTrainer(FlexMFTrainerBase):
+    "``FlexMFImplicitTrainer`` (_implicit.py:164-290)."
+
+    def model_biases(self):
+        return self.config.selected_user_bias(), self.config.item_bias
+
+    def create_state(self, tabs: dict):
+        cfg = self.config
+        return D.FlexMFState(
+            tabs["u_embed.weight"], tabs["i_embed.weight"], tabs["u_bias.weight"],
+            tabs["i_bias.weight"], loss=cfg.loss, reg_method=cfg.reg_method,
+            regularization=cfg.regularization, learning_rate=cfg.learning_rate,
+            negative_count=cfg.negative_count, positive_weight=cfg.positive_weight, dev=self.dev)
+
+    def prepare_data(self, ds) -> None:
+        self.d_indptr, self.d_cols = self.matrix._device_csr(self.dev)
+        # the key of the negative sampler's counter-based stream
+        self.sample_key = int(self.rng.bit_generator.random_raw())
+
+    def negatives(self, users: torch.Tensor, positives: torch.Tensor, counter: int):
+        "``scored_negatives`` (_implicit.py:276-290): (negatives [B x n], no weights)."
+        cfg = self.config
+        neg = D.flexmf_sample_negatives(self.d_indptr, self.d_cols, self.n_items, users,
+                                        cfg.negative_count, cfg.selected_negative_strategy(),
+                                        self.sample_key, counter)
+        return neg, None
+
+    def train_batch(self, d_sel: torch.Tensor, batch: int, loss_sum: torch.Tensor) -> None:
+        users, items = D.flexmf_gather_batch(d_sel, self.d_users, self.d_items)
+        neg, weights = self.negatives(users, items, (self.epochs_trained << 32) | batch)
+        self.state.step(users, items, neg, weights, loss_sum=loss_sum, check_indices=False)
+
+
+def centred_ratings(data: Dataset):
+    """
+    (global bias, ratings minus it) as the reference's ``prepare_data`` computes them
+    (_explicit.py:65-79): the float32 mean by Torch's CPU reduction, as a Python float, and the
+    float32 differences, in the order of the interactions (row-major COO).
+    """
+    ratings = data.interactions().matrix()._ds._attrs.get("rating")
+    if ratings is None:
+        raise ValueError("FlexMF explicit trains on the interactions' 'rating' field, which this "
+                         "dataset does not have")
+    values = torch.from_numpy(np.ascontiguousarray(ratings, dtype=np.float32))
+    mean = values.mean()
+    return mean.item(), (values - mean).numpy()
+
+
+class FlexMFExplicitTrainer(FlexMFTrainerBase):
+    """
+    ``FlexMFExplicitTrainer`` (_explicit.py:58-125): every interaction with its centred rating is
+    a sample, both biases are learned, a batch is one ``lk_flexmf_step_explicit``; the epoch's
+    reported loss is the mean of the batches' mean squared errors.
+    """
+
+    def check_data(self, data: Dataset) -> None:
+        self.scorer.global_bias, self._centred = centred_ratings(data)
+
+    def model_biases(self):
+        return True, True
+
+    def create_state(self, tabs: dict):
+        cfg = self.config
+        return D.FlexMFState(
+            tabs["u_embed.weight"], tabs["i_embed.weight"], tabs["u_bias.weight"],
+            tabs["i_bias.weight"], loss="mse", reg_method=cfg.reg_method,
+            regularization=cfg.regularization, learning_rate=cfg.learning_rate, dev=self.dev)
+
+    def prepare_data(self, ds) -> None:
+        self.d_ratings = torch.from_numpy(self._centred).to(self.dev)
+        del self._centred
+
+    def train_batch(self, d_sel: torch.Tensor, batch: int, loss_sum: torch.Tensor) -> None:
+        users, items = D.flexmf_gather_batch(d_sel, self.d_users, self.d_items)
+        ratings = D.flexmf_gather_values(d_sel, self.d_ratings)
+        self.state.step_explicit(users, items, ratings, loss_sum=loss_sum, check_indices=False)
 
 
 class FlexMFWARPTrainer(FlexMFImplicitTrainer):
