@@ -4,8 +4,9 @@ how the index arithmetic of csrc/als_chol.hip (accumulator-tile layout, L image,
 transposition) is checked without a GPU.  Likewise the LDS placement of the DMA-staged top-K
 filter kernel (csrc/topk.hip::score_filter64_kernel), the per-target accumulator of the kNN
 scoring kernels (csrc/iknn_score.hip: rounds, rank sort, BinaryHeap replay, in-place heapify)
-against the C oracle, the folded 8-way reduction of the CG kernel (csrc/als_cg.hip), and the
-wave-per-row selection of the fused top-N path (csrc/topk.hip::cand_select_wave_kernel).
+against the C oracle, the folded 8-way reduction of the CG kernel (csrc/als_cg.hip), the
+wave-per-row selection of the fused top-N path (csrc/topk.hip::cand_select_wave_kernel), and one
+pass of the stable radix sort (csrc/radix_sort.h: histogram, scan with its carry, scatter ranks).
 """
 import sys
 from pathlib import Path
@@ -127,3 +128,134 @@ def test_wave_select_model_equals_a_sort():
     import wave_select as w
 
     assert w.main(trials=120) > 32  # the index-half search ran (more than 128 equal scores)
+
+
+# ---- csrc/radix_sort.h ----------------------------------------------------------------------------
+def _digits(kind, n, mask, rng):
+    i = np.arange(n, dtype=np.uint64)
+    top = np.uint64(mask)
+    if kind == "all 0":
+        return np.zeros(n, np.uint64)
+    if kind == "all top":
+        return np.full(n, top, np.uint64)
+    if kind == "two alternating":
+        return np.where(i % np.uint64(2) == 0, top, np.uint64(min(3, mask - 1)))
+    if kind == "uniform":
+        return rng.integers(0, mask + 1, n, dtype=np.uint64)
+    if kind == "ascending":
+        return (i * np.uint64(mask + 1)) // np.uint64(n)
+    assert kind == "descending"
+    return top - (i * np.uint64(mask + 1)) // np.uint64(n)
+
+
+RADIX_DISTRIBUTIONS = ["all 0", "all top", "two alternating", "uniform", "ascending", "descending"]
+
+
+@pytest.mark.parametrize("mask", [255, 1])
+@pytest.mark.parametrize("tile_n", [1, 63, 64, 65, 4095, 4096])
+def test_radix_scatter_model_is_a_stable_pass(tile_n, mask):
+    """tools/emul/radix_scatter.py: the eight-ballot peers mask and rank, the uint16 per-(chunk,
+    digit) table and its running offsets, the four-per-lane wave scan of tile_start, the uint16 pos,
+    the digit-major reorder and the destination from goff -- one pass over a single tile (and over
+    that tile behind a full one) equals a stable sort by the digit, for every digit distribution;
+    mask 1 is the 1-bit last digit of a 33- or 41-bit key."""
+    import radix_scatter as rs
+
+    rng = np.random.default_rng(1000 * tile_n + mask)
+    shift = 16
+    for kind in RADIX_DISTRIBUTIONS:
+        for n in (tile_n, rs.TILE + tile_n):
+            dig = _digits(kind, n, mask, rng)
+            assert int(dig.max()) <= mask
+            if kind == "all top":
+                assert (dig == mask).all()
+            if kind == "two alternating":
+                assert len(np.unique(dig)) == min(2, n)
+            # bits around the digit are noise the pass must ignore; equal digits everywhere
+            noise = rng.integers(0, 1 << 16, n, dtype=np.uint64)
+            high = rng.integers(0, 1 << 20, n, dtype=np.uint64) << np.uint64(shift + 8)
+            keys = noise | (dig << np.uint64(shift)) | (high if mask == 255 else np.uint64(0))
+            vals = np.arange(n, dtype=np.uint32)
+            assert np.array_equal(rs.digit_of(keys, shift, mask), dig.astype(np.uint32))
+            gk, gv = rs.radix_pass(keys, vals, shift, mask)
+            order = np.argsort(dig, kind="stable")
+            assert np.array_equal(gv, vals[order]), (kind, n)
+            assert np.array_equal(gk, keys[order]), (kind, n)
+            k32 = (keys & np.uint64(0xffffffff)).astype(np.uint32)  # the <uint32, uint64> pairs
+            gk, gv = rs.radix_pass(k32, vals.astype(np.uint64), shift, mask)
+            assert np.array_equal(gv, vals[order]) and np.array_equal(gk, k32[order]), (kind, n)
+
+
+@pytest.mark.parametrize("n_tiles", [1, 2, 256, 257])
+def test_radix_scan_model_trips_and_carry(n_tiles):
+    """rs_hist / rs_rowsum / rs_scan: where tile i's keys of digit d start = the totals of the
+    smaller digits + digit d's counts in the tiles before i; 257 tiles take a second 256-wide trip
+    whose first entry is the carry of the first."""
+    import radix_scatter as rs
+
+    rng = np.random.default_rng(n_tiles)
+    hist = rng.integers(0, rs.TILE + 1, (rs.RADIX, n_tiles)).astype(np.uint64)
+    hist[rng.random(hist.shape) < 0.3] = 0
+    hist[7, :] = rs.TILE  # a digit every tile is full of
+    total = rs.rowsum_model(hist)
+    assert np.array_equal(total, hist.sum(axis=1))
+    offs, trips = rs.scan_model(hist, total)
+    assert trips == (n_tiles + 255) // 256 == (2 if n_tiles == 257 else 1)
+    before = np.concatenate([[0], np.cumsum(total)[:-1]]).astype(np.uint64)
+    want = before[:, None] + np.cumsum(hist, axis=1) - hist
+    assert np.array_equal(offs, want)
+    if n_tiles == 257:
+        assert offs[7, 256] == before[7] + 256 * rs.TILE  # what the carry brings over
+    # ... and the histogram itself, on keys that end inside the last tile
+    n = min(n_tiles, 3) * rs.TILE - 5
+    keys = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+    h = rs.hist_model(keys, 8, 255)
+    assert h.shape == (rs.RADIX, rs.tiles_of(n))
+    for tile in range(h.shape[1]):
+        d = rs.digit_of(keys[tile * rs.TILE:(tile + 1) * rs.TILE], 8, 255)
+        assert np.array_equal(h[:, tile], np.bincount(d, minlength=rs.RADIX))
+
+
+def test_radix_pass_model_across_257_tiles():
+    "one whole modelled pass whose scan makes the second trip: 257 tiles, the last holding one key"
+    import radix_scatter as rs
+
+    rng = np.random.default_rng(257)
+    n = 256 * rs.TILE + 1
+    keys = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+    keys[: rs.TILE] = 0x00AB0000  # a full tile in which every key has the same digit
+    vals = np.arange(n, dtype=np.uint32)
+    assert rs.tiles_of(n) == 257
+    gk, gv = rs.radix_pass(keys, vals, 16, 255)
+    order = np.argsort(rs.digit_of(keys, 16, 255), kind="stable")
+    assert np.array_equal(gv, vals[order]) and np.array_equal(gk, keys[order])
+
+
+@pytest.mark.parametrize("end_bit", [32, 34, 41])
+def test_radix_chained_passes_sort_64_bit_keys(end_bit):
+    """radix_sort_pairs over (row << 32) | key as topn_sort builds them: 4, 5 and 6 passes, the last
+    digit 8, 2 and 1 bits wide, the ping-pong ending in the out pair; equal keys keep their order"""
+    import radix_scatter as rs
+
+    rng = np.random.default_rng(end_bit)
+    n = 2 * rs.TILE + 77
+    plan = rs.pass_plan(0, end_bit)
+    assert len(plan) == {32: 4, 34: 5, 41: 6}[end_bit]
+    assert plan[-1][1] == {32: 255, 34: 3, 41: 1}[end_bit] and plan[-1][2]
+    assert plan[0][2] == (len(plan) % 2 == 1)  # an even count: the first pass goes to the tmp pair
+    rows = np.sort(rng.integers(0, 1 << (end_bit - 32), n, dtype=np.uint64)) if end_bit > 32 \
+        else np.zeros(n, np.uint64)
+    low = rng.integers(0, 1 << 32, n, dtype=np.uint64)
+    low[rng.random(n) < 0.5] = 0xFFFFFFFF - 0x3F800000  # heavy ties
+    keys = (rows << np.uint64(32)) | low
+    vals = rng.permutation(n).astype(np.uint32)
+    assert n - len(np.unique(keys)) > n // 4 and int(keys.max()) < (1 << end_bit)
+    gk, gv = rs.radix_sort_pairs(keys, vals, 0, end_bit)
+    order = np.argsort(keys, kind="stable")
+    assert np.array_equal(gk, keys[order]) and np.array_equal(gv, vals[order])
+
+
+def test_radix_scatter_model_self_check():
+    import radix_scatter as rs
+
+    rs.main()

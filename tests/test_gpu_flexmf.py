@@ -137,6 +137,48 @@ def test_one_user_batch(ml, gpu, reg_method):
             regularization=0.01, learning_rate=0.01, negative_count=1, positive_weight=2.0)
 
 
+def _bits_for(n):
+    b = 1
+    while b < 32 and (1 << b) < n:
+        b += 1
+    return b
+
+
+@pytest.mark.parametrize("reg_method", ["AdamW", "L2"])
+def test_step_parity_at_other_sort_sizes(gpu, reg_method):
+    """Synthetic tables whose per-batch sorts are not the 2 + 2 passes of every other case here:
+    200 users (8 key bits, one pass) and 70 000 items (17 bits, three passes), batches of 4097
+    samples (two tiles of the sort, the second holding one key) with one negative each (8194 item
+    keys: three tiles, the third holding two); one batch is a single user throughout, with
+    negatives equal to their positives."""
+    from lkpy_amd.flexmf import initial_tables
+
+    n_users, n_items, k, B, tile = 200, 70_000, 8, 4097, 4096
+    assert (_bits_for(n_users) + 7) // 8 == 1 and (_bits_for(n_items) + 7) // 8 == 3
+    assert ((B + tile - 1) // tile, B % tile) == (2, 1)
+    assert ((2 * B + tile - 1) // tile, (2 * B) % tile) == (3, 2)
+    tabs = initial_tables(n_users, n_items, k, torch.Generator().manual_seed(7), user_bias=True,
+                          item_bias=True)
+    rng = np.random.default_rng(21)
+    batches = []
+    for b in range(3):
+        users = rng.integers(0, n_users, B).astype(np.int32)
+        pos = rng.integers(0, n_items, B).astype(np.int32)
+        neg = rng.integers(0, n_items, (B, 1)).astype(np.int32)
+        if b == 1:
+            users[:] = 137
+            neg[:100, 0] = pos[:100]
+            neg[100:200, 0] = pos[300:400]  # ... and equal to another sample's item
+        batches.append((users, pos, neg, None))
+    assert len(batches) == 3 and all(len(u) == B and n.shape == (B, 1) for u, _p, n, _w in batches)
+    assert len(np.unique(batches[1][0])) == 1 and len(np.unique(batches[0][0])) == n_users
+    assert (batches[1][2][:100, 0] == batches[1][1][:100]).all()
+    assert max(int(p.max()) for _u, p, _n, _w in batches) >= 1 << 16  # the third digit is in use
+    _parity(tabs, batches, gpu, f"sort sizes/{reg_method}", loss="logistic",
+            reg_method=reg_method, regularization=0.01, learning_rate=0.01, negative_count=1,
+            positive_weight=2.0)
+
+
 # ---- sampler ------------------------------------------------------------------------------
 def _dev_csr(indptr, cols, gpu):
     return (torch.from_numpy(np.asarray(indptr, np.int64)).to(gpu),
