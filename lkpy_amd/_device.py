@@ -146,13 +146,21 @@ def lists_to_host(idx: torch.Tensor, scores: torch.Tensor, rows: torch.Tensor | 
     return host[:, :cols].view(np.int32), host[:, cols:]
 
 
+def blank_rows(idx: torch.Tensor, scores: torch.Tensor, valid: np.ndarray) -> None:
+    "The rows of a [B x n] top-N result whose query is not ``valid`` (host bool [B]): -1 / NaN."
+    if not valid.all():
+        bad = torch.from_numpy(np.flatnonzero(~valid)).to(idx.device)
+        idx[bad] = -1
+        scores[bad] = float("nan")
+
+
 @dataclass
 class DeviceCSR:
     "CSR in HBM: the SparseRowArray layout (offsets i32/i64, indices i32, values f32)."
 
     indptr: torch.Tensor
     indices: torch.Tensor
-    values: torch.Tensor
+    values: torch.Tensor | None  # None: structure only
     shape: tuple[int, int]
     h_indptr: np.ndarray  # host copy of the offsets (plans are built from it)
 
@@ -166,18 +174,20 @@ class DeviceCSR:
 
     @classmethod
     def from_arrays(cls, indptr, indices, values, shape, dev) -> "DeviceCSR":
+        "Host arrays uploaded; ``values=None``: a CSR of structure only (``values`` stays None)."
         indptr = np.ascontiguousarray(indptr)
         if indptr.dtype not in (np.int32, np.int64):
             indptr = indptr.astype(np.int64)
         indices = np.ascontiguousarray(indices, dtype=np.int32)
-        values = np.ascontiguousarray(values, dtype=np.float32)
+        if values is not None:
+            values = np.ascontiguousarray(values, dtype=np.float32)
         # zero-copy views of Arrow buffers are read-only; torch.from_numpy wants writable memory
-        indptr, indices, values = (a if a.flags.writeable else a.copy()
+        indptr, indices, values = (a if a is None or a.flags.writeable else a.copy()
                                    for a in (indptr, indices, values))
         return cls(
             torch.from_numpy(indptr).to(dev),
             torch.from_numpy(indices).to(dev),
-            torch.from_numpy(values).to(dev),
+            None if values is None else torch.from_numpy(values).to(dev),
             (int(shape[0]), int(shape[1])),
             indptr,
         )

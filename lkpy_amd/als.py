@@ -22,7 +22,8 @@ from pydantic import AliasChoices, BaseModel, Field, PositiveFloat, PositiveInt
 from . import _device as D
 from . import _native
 from ._als_engine import HipBackend, ImplicitALSEngine
-from .basic import BiasModel
+from ._queries import item_scores, pack_histories, resolve_queries, user_numbers
+from .basic import BiasModel, HistoryBatch
 from .data import Dataset, ItemList, RecQuery, Vocabulary
 from .pipeline import Component
 from .training import ModelTrainer, TrainingOptions, UsesTrainer
@@ -183,34 +184,26 @@ class ImplicitMFScorer(UsesTrainer, Component):
         return _SOLVERS[name.lower()]
 
     # -- fold-in --------------------------------------------------------------------
+    def _confidence(self, hist: ItemList, nums: np.ndarray, kept: np.ndarray) -> np.ndarray:
+        """
+        The confidence values of one history's kept items (_implicit.py:83-92): ``rating *
+        weight`` in the ratings' own dtype (the caller casts to float32), or the constant
+        ``weight``.
+        """
+        if not self.config.use_ratings:
+            return np.full(int(kept.sum()), self.config.weight)
+        ratings = hist.field("rating")
+        if ratings is None:
+            raise ValueError("no ratings in user items")  # (_implicit.py:85-86)
+        return np.asarray(ratings)[kept] * self.config.weight
+
     def _history_rows(self, queries: list[RecQuery]):
         """
-        histories -> CSR (queries x items) of confidence values (_implicit.py:77-99).
-        History items the model does not know are DROPPED: the reference builds the ``ri_good``
-        mask for exactly that (_implicit.py:82-90) although its ``numbers()`` call raises
-        ``KeyError`` first (default ``missing="error"``, data/_items.py:617,654-655); a batch
-        must not fail because one history mentions a new item.
+        histories -> CSR (queries x items) of confidence values (_implicit.py:77-99), rows sorted
+        by item number, history items the model does not know DROPPED.
         """
-        idx, val, ptr = [], [], [0]
-        for q in queries:
-            hist = q.query_items
-            if hist is not None and len(hist) > 0:
-                ri = hist.numbers(vocabulary=self.items, missing="negative")
-                good = ri >= 0
-                if self.config.use_ratings:
-                    ratings = hist.field("rating")
-                    if ratings is None:
-                        raise ValueError("no ratings in user items")
-                    v = np.asarray(ratings)[good] * self.config.weight
-                else:
-                    v = np.full(int(good.sum()), self.config.weight)
-                order = np.argsort(ri[good], kind="stable")
-                idx.append(ri[good][order])
-                val.append(np.asarray(v, dtype=np.float32)[order])
-            ptr.append(ptr[-1] + (len(idx[-1]) if hist is not None and len(hist) > 0 else 0))
-        indices = np.concatenate(idx).astype(np.int32) if idx else np.zeros(0, np.int32)
-        values = np.concatenate(val).astype(np.float32) if val else np.zeros(0, np.float32)
-        return np.asarray(ptr, dtype=np.int64), indices, values
+        return pack_histories(queries, self.items, unknown="drop", sort=True,
+                              values=self._confidence)
 
     def _query_csr(self, queries: list[RecQuery]) -> D.DeviceCSR:
         "``_history_rows`` uploaded: the list front-end's histories as a device CSR."
@@ -263,12 +256,11 @@ class ImplicitMFScorer(UsesTrainer, Component):
         hist = self._query_csr(queries)
         has_hist = np.array([q.query_items is not None and len(q.query_items) > 0
                              for q in queries], dtype=bool)
-        stored = np.full(len(queries), -1, dtype=np.int64)
-        if self.user_embeddings is not None and self.users is not None:
-            for i, q in enumerate(queries):
-                num = None if q.user_id is None else self.users.number(q.user_id, missing=None)
-                stored[i] = -1 if num is None else num
-        return (*self._embeddings(hist, has_hist, stored, pending), hist)
+        return (*self._embeddings(hist, has_hist, self._stored_rows(queries), pending), hist)
+
+    def _stored_rows(self, queries) -> np.ndarray:
+        "per query: the user's row of ``user_embeddings``, -1 = none"
+        return user_numbers(queries, None if self.user_embeddings is None else self.users)
 
     def _history_batch_embeddings(self, batch, pending: list | None = None):
         """
@@ -277,14 +269,9 @@ class ImplicitMFScorer(UsesTrainer, Component):
         rows are found by user number.  Returns (device [B x KP], valid, history CSR).
         """
         cfg = self.config
-        stored = np.full(len(batch), -1, dtype=np.int64)
-        if self.user_embeddings is not None and self.users is not None:
-            if batch.users is self.users or batch.users == self.users:
-                stored = batch.user_nums.astype(np.int64)
-            else:
-                stored = self.users.numbers(batch.user_ids, missing="negative").astype(np.int64)
         hist = batch.csr(use_ratings=cfg.use_ratings, scale=cfg.weight)
-        return (*self._embeddings(hist, batch.lengths > 0, stored, pending), hist)
+        return (*self._embeddings(hist, batch.lengths > 0, self._stored_rows(batch), pending),
+                hist)
 
     # -- scoring (src/lenskit/als/_common.py:133-175) -----------------------------------
     def __call__(self, query, items: ItemList) -> ItemList:
@@ -294,11 +281,7 @@ class ImplicitMFScorer(UsesTrainer, Component):
             return ItemList(items, scores=np.nan)
         st = self._device_state()
         all_scores = D.score_dense(u, st["Q"], self.config.embedding_size)[0].cpu().numpy()
-        item_nums = items.numbers(vocabulary=self.items, missing="negative")
-        mask = item_nums >= 0
-        scores = np.full(len(items), np.nan, dtype=np.float32)
-        scores[mask] = all_scores[item_nums[mask]]
-        return ItemList(items, scores=scores)
+        return ItemList(items, scores=item_scores(items, self.items, all_scores))
 
     def recommend_batch(self, queries, n: int, *, exclude_history: bool = True,
                         device_output: bool = False):
@@ -310,17 +293,12 @@ class ImplicitMFScorer(UsesTrainer, Component):
         padding, scores [B x n] with NaN padding) as host arrays (``device_output``: as device
         tensors, nothing downloaded).
         """
-        from .basic import HistoryBatch
-
-        if isinstance(queries, HistoryBatch) and not (
-                queries.items is self.items or queries.items == self.items):
-            queries = queries.queries()  # (another item vocabulary: the per-query mapping)
+        queries = resolve_queries(queries, self.items)
         pending: list = []  # the fold-in's status is read once the scoring is queued behind it
         if isinstance(queries, HistoryBatch):
             u, valid, hist = self._history_batch_embeddings(queries, pending)
         else:
-            u, valid, hist = self._query_embeddings([RecQuery.create(q) for q in queries],
-                                                    pending)
+            u, valid, hist = self._query_embeddings(queries, pending)
         st = self._device_state()
         if exclude_history:
             idx, sc = D.score_topk(u, st["Q"], self.config.embedding_size, n, hist.indptr,
@@ -329,10 +307,7 @@ class ImplicitMFScorer(UsesTrainer, Component):
             idx, sc = D.score_topk(u, st["Q"], self.config.embedding_size, n)
         for plan in pending:
             plan.check_status()  # RuntimeError("ALS solve error: ...") like the fold-in alone
-        if not valid.all():
-            bad = torch.from_numpy(np.flatnonzero(~valid)).to(st["device"])
-            idx[bad] = -1
-            sc[bad] = float("nan")
+        D.blank_rows(idx, sc, valid)
         if device_output:
             return idx, sc
         return D.lists_to_host(idx, sc)
@@ -519,10 +494,7 @@ class BiasedMFScorer(UsesTrainer, Component):
         u = D.to_device_padded(np.ascontiguousarray(u_feat, dtype=np.float32)[None, :],
                                st["device"])
         all_scores = D.score_dense(u, st["Q"], k)[0].cpu().numpy()
-        item_nums = items.numbers(vocabulary=self.items, missing="negative")
-        mask = item_nums >= 0
-        scores = np.full(len(items), np.nan, dtype=np.float32)
-        scores[mask] = all_scores[item_nums[mask]]
+        scores = item_scores(items, self.items, all_scores)
         return self.finalize_scores(user_num, ItemList(items, scores=scores), u_off)
 
 

@@ -53,15 +53,10 @@ class UserTrainingHistoryLookup(Component):
             ds = self.interactions._ds
             dev = D.device()
             rat = ds._attrs.get("rating")
-            st = {"device": dev,
-                  "csr": D.DeviceCSR.from_arrays(
-                      ds._indptr, ds._cols,
-                      np.zeros(0, np.float32) if rat is None else rat,
-                      (ds.user_count, ds.item_count), dev),
-                  "has_ratings": rat is not None}
-            if rat is None:
-                st["csr"].values = None
-            return st
+            return {"device": dev,
+                    "csr": D.DeviceCSR.from_arrays(ds._indptr, ds._cols, rat,
+                                                   (ds.user_count, ds.item_count), dev),
+                    "has_ratings": rat is not None}
 
         return self._device_cache("matrix", upload, self.interactions)
 

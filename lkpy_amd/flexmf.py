@@ -33,7 +33,9 @@ from pydantic import BaseModel, NonNegativeInt, PositiveFloat, PositiveInt, mode
 
 from . import _device as D
 from . import _native
+from ._queries import item_scores, pack_histories, resolve_queries, user_numbers
 from .als import _DeviceBacked, _scorer_state
+from .basic import HistoryBatch
 from .data import Dataset, ItemList, RecQuery, Vocabulary
 from .pipeline import Component
 from .training import ModelTrainer, TrainingOptions, UsesTrainer
@@ -200,47 +202,21 @@ class FlexMFScorerBase(UsesTrainer, Component):
         :class:`lkpy_amd.basic.HistoryBatch`.  Returns (item numbers [B x n] with -1 padding,
         scores [B x n] with NaN padding); an unknown user's row is all padding.
         """
-        from .basic import HistoryBatch
-
-        if isinstance(queries, HistoryBatch) and not (
-                queries.items is self.items or queries.items == self.items):
-            queries = queries.queries()
+        queries = resolve_queries(queries, self.items)
         st = self._device_state()
         hist = None
-        if isinstance(queries, HistoryBatch):
-            if queries.users is self.users or queries.users == self.users:
-                nums = queries.user_nums.astype(np.int64)
-            else:
-                nums = self.users.numbers(queries.user_ids, missing="negative").astype(np.int64)
-            if exclude_history:
-                hist = queries.csr(with_values=False)
-        else:
-            qs = [RecQuery.create(q) for q in queries]
-            nums = np.full(len(qs), -1, dtype=np.int64)
-            idx, ptr = [], [0]
-            for i, q in enumerate(qs):
-                num = None if q.user_id is None else self.users.number(q.user_id, missing=None)
-                nums[i] = -1 if num is None else num
-                h = q.query_items
-                cnt = 0
-                if exclude_history and h is not None and len(h) > 0:
-                    ri = h.numbers(vocabulary=self.items, missing="negative")
-                    idx.append(np.sort(ri[ri >= 0]))
-                    cnt = len(idx[-1])
-                ptr.append(ptr[-1] + cnt)
-            if exclude_history:
-                indices = np.concatenate(idx).astype(np.int32) if idx else np.zeros(0, np.int32)
-                hist = D.DeviceCSR.from_arrays(np.asarray(ptr, np.int64), indices, None,
-                                               (len(qs), len(self.items)), st["device"])
-        u, valid = self._user_rows(nums)
+        if exclude_history and isinstance(queries, HistoryBatch):
+            hist = queries.csr(with_values=False)
+        elif exclude_history:  # the items to strike: known ones, sorted, no values
+            ptr, idx, _ = pack_histories(queries, self.items, unknown="drop", sort=True)
+            hist = D.DeviceCSR.from_arrays(ptr, idx, None, (len(queries), len(self.items)),
+                                           st["device"])
+        u, valid = self._user_rows(user_numbers(queries, self.users))
         if hist is not None:
             idx, sc = D.score_topk(u, st["Q"], self._score_k, n, hist.indptr, hist.indices)
         else:
             idx, sc = D.score_topk(u, st["Q"], self._score_k, n)
-        if not valid.all():
-            bad = torch.from_numpy(np.flatnonzero(~valid)).to(st["device"])
-            idx[bad] = -1
-            sc[bad] = float("nan")
+        D.blank_rows(idx, sc, valid)
         if device_output:
             return idx, sc
         return D.lists_to_host(idx, sc)
@@ -268,11 +244,7 @@ class FlexMFImplicitScorer(FlexMFScorerBase):
         st = self._device_state()
         u, _ = self._user_rows(np.array([u_row]))
         all_scores = D.score_dense(u, st["Q"], self._score_k)[0].cpu().numpy()
-        item_nums = items.numbers(vocabulary=self.items, missing="negative")
-        mask = item_nums >= 0
-        scores = np.full(len(items), np.nan, dtype=np.float32)
-        scores[mask] = all_scores[item_nums[mask]]
-        return ItemList(items, scores=scores)
+        return ItemList(items, scores=item_scores(items, self.items, all_scores))
 
 
 class FlexMFExplicitScorer(FlexMFScorerBase):
@@ -331,11 +303,7 @@ class FlexMFExplicitScorer(FlexMFScorerBase):
     def score_batch(self, queries, item_lists) -> list[ItemList]:
         "``__call__`` for many queries: one vocabulary pass, one launch, the same bits."
         qs = [RecQuery.create(q) for q in queries]
-        user_nums = np.full(len(qs), -1, dtype=np.int32)
-        for i, q in enumerate(qs):
-            num = None if q.user_id is None else self.users.number(q.user_id, missing=None)
-            if num is not None:
-                user_nums[i] = num
+        user_nums = user_numbers(qs, self.users)
         ptr = np.zeros(len(qs) + 1, np.int64)
         np.cumsum([len(il) for il in item_lists], out=ptr[1:])
         ids = [il.ids() for il in item_lists if len(il)]

@@ -21,6 +21,8 @@ import torch
 from pydantic import AliasChoices, BaseModel, Field, PositiveFloat, PositiveInt, field_validator
 
 from . import _device as D
+from ._queries import item_scores, pack_histories, resolve_queries
+from .basic import HistoryBatch
 from .data import Dataset, ItemList, RecQuery, SparseRowArray, Vocabulary
 from .pipeline import Component
 from .training import TrainingOptions
@@ -137,36 +139,22 @@ class ItemKNNScorer(Component):
                                   lookup.interactions, self.sim_matrix)
 
     # -- the two front-ends: histories as a device CSR in query order -------------------------
+    def _centred_ratings(self, hist: ItemList, nums: np.ndarray, kept: np.ndarray) -> np.ndarray:
+        "One history's float32 ratings minus the float32 item means; unknown items not centred."
+        rv = hist.field("rating")
+        if rv is None:
+            raise RuntimeError("explicit-feedback scorer must have ratings")
+        rv = np.asarray(rv).astype(np.float32, copy=True)
+        m = nums >= 0
+        rv[m] -= self.item_means[nums[m]]  # mean-centre (item.py:268-271)
+        return rv
+
     def _query_csr(self, queries: list[RecQuery]) -> D.DeviceCSR:
-        """
-        The histories of a list of queries: item numbers (-1 = unknown) and, explicit, the
-        float32 ratings minus the float32 item means (item.py:268-271; unknown items are not
-        centred), uploaded in query order.
-        """
-        r_idx, r_val, r_ptr = [], [], [0]
-        for q in queries:
-            ratings = q.query_items
-            if ratings is None or len(ratings) == 0:
-                r_ptr.append(r_ptr[-1])
-                continue
-            ri = ratings.numbers(vocabulary=self.items, missing="negative")
-            if self.config.explicit:
-                rv = ratings.field("rating")
-                if rv is None:
-                    raise RuntimeError("explicit-feedback scorer must have ratings")
-                rv = np.asarray(rv).astype(np.float32, copy=True)
-                m = ri >= 0
-                rv[m] -= self.item_means[ri[m]]  # mean-centre (item.py:268-271)
-                r_val.append(rv)
-            r_idx.append(ri)
-            r_ptr.append(r_ptr[-1] + len(ri))
-        cat = lambda xs, dt: np.concatenate(xs).astype(dt) if xs else np.zeros(0, dt)  # noqa: E731
-        hist = D.DeviceCSR.from_arrays(np.asarray(r_ptr, np.int64), cat(r_idx, np.int32),
-                                       cat(r_val, np.float32), (len(queries), len(self.items)),
+        "The histories of a list of queries, uploaded: -1 = unknown item; explicit: with values."
+        values = self._centred_ratings if self.config.explicit else None
+        ptr, idx, val = pack_histories(queries, self.items, unknown="keep", values=values)
+        return D.DeviceCSR.from_arrays(ptr, idx, val, (len(queries), len(self.items)),
                                        self._device_sims()["device"])
-        if not self.config.explicit:
-            hist.values = None
-        return hist
 
     def _batch_csr(self, batch) -> D.DeviceCSR:
         """
@@ -247,18 +235,14 @@ class ItemKNNScorer(Component):
         for every training user on the device).  Returns (item numbers [B x n] with -1 padding,
         scores [B x n] with NaN padding), like ``ImplicitMFScorer.recommend_batch``.
         """
-        from .basic import HistoryBatch
-
-        if isinstance(queries, HistoryBatch) and not (
-                queries.items is self.items or queries.items == self.items):
-            queries = queries.queries()  # (another item vocabulary: the per-query mapping)
+        queries = resolve_queries(queries, self.items)
         if isinstance(queries, HistoryBatch):
             batch = queries
             nums = batch.user_nums
             hits = np.where(nums >= 0, self._user_hits(batch.lookup)[np.maximum(nums, 0)], 0)
             return self._recommend(lambda order: self._batch_csr(batch.subset(order)),
                                    hits.astype(np.int64), n, exclude_history)
-        hist = self._query_csr([RecQuery.create(q) for q in queries])
+        hist = self._query_csr(queries)
         return self._recommend(
             lambda order: D.gather_rows(hist, order, with_values=self.config.explicit),
             self._row_hits(hist), n, exclude_history)
@@ -519,35 +503,14 @@ class EASEScorer(Component):
     def score_batch(self, queries, item_lists) -> list[ItemList]:
         "Scores for a batch of (query, items) pairs; one device call for all of them."
         w = self._device_weights()
-        hists, ok = [], []
-        for query in queries:
-            query = RecQuery.create(query)
-            q_items = query.query_items
-            good = np.empty(0, np.int32)
-            if q_items is not None:
-                q_inos = q_items.numbers(vocabulary=self.items, missing="negative")
-                # a repeated history item counts ONCE: the reference sets q_vec[q_good] = 1.0
-                # (src/lenskit/knn/ease.py), it does not add per occurrence
-                good = np.unique(q_inos[q_inos >= 0]).astype(np.int32)
-            hists.append(good)
-            ok.append(len(good) > 0)  # ease.py:150-158: no usable history => all NaN
-        ptr = np.zeros(len(hists) + 1, dtype=np.int64)
-        np.cumsum([len(h) for h in hists], out=ptr[1:])
-        cat = np.concatenate(hists) if hists else np.empty(0, np.int32)
+        ptr, idx, _ = pack_histories([RecQuery.create(q) for q in queries], self.items,
+                                     unknown="drop", unique=True)
         scores = D.ease_score_batch(torch.from_numpy(ptr).to(w.device),
-                                    torch.from_numpy(np.ascontiguousarray(cat)).to(w.device),
-                                    w).cpu().numpy()
-        out = []
-        for i, items in enumerate(item_lists):
-            if not ok[i]:
-                out.append(ItemList(items, scores=np.nan))
-                continue
-            t_inos = items.numbers(vocabulary=self.items, missing="negative")
-            sc = np.full(len(items), np.nan, dtype=np.float32)
-            t_ok = t_inos >= 0
-            sc[t_ok] = scores[i][t_inos[t_ok]]
-            out.append(ItemList(items, scores=sc))
-        return out
+                                    torch.from_numpy(idx).to(w.device), w).cpu().numpy()
+        # ease.py:150-158: no usable history => all NaN
+        return [ItemList(items, scores=item_scores(items, self.items, scores[i])
+                         if ptr[i] < ptr[i + 1] else np.nan)
+                for i, items in enumerate(item_lists)]
 
     def __call__(self, query, items: ItemList) -> ItemList:
         return self.score_batch([query], [items])[0]
@@ -632,18 +595,10 @@ class SLIMScorer(Component):
         return max(1, self.PANEL_BYTES // (4 * max(len(self.items), 1)))
 
     def _query_csr(self, queries: list[RecQuery]) -> D.DeviceCSR:
-        "The histories of a list of queries in query order: item numbers, -1 = unknown."
-        r_idx, r_ptr = [], [0]
-        for q in queries:
-            hist = q.query_items
-            if hist is not None and len(hist) > 0:
-                r_idx.append(hist.numbers(vocabulary=self.items, missing="negative"))
-            r_ptr.append(r_ptr[-1] + (0 if hist is None else len(hist)))
-        idx = np.concatenate(r_idx).astype(np.int32) if r_idx else np.zeros(0, np.int32)
-        d = self._device_weights().indices.device
-        ptr = np.asarray(r_ptr, np.int64)
-        return D.DeviceCSR(torch.from_numpy(ptr).to(d), torch.from_numpy(idx).to(d), None,
-                           (len(queries), len(self.items)), ptr)
+        "The histories of a list of queries in query order, uploaded: item numbers, -1 = unknown."
+        ptr, idx, _ = pack_histories(queries, self.items, unknown="keep")
+        return D.DeviceCSR.from_arrays(ptr, idx, None, (len(queries), len(self.items)),
+                                       self._device_weights().indices.device)
 
     def score_batch(self, queries, item_lists) -> list[ItemList]:
         "Scores for a batch of (query, items) pairs (slim.py:121-152 per pair)."
@@ -659,11 +614,7 @@ class SLIMScorer(Component):
                 if hist.h_indptr[i] == hist.h_indptr[i + 1]:
                     out.append(ItemList(items, scores=np.nan))  # no / empty history: 125-130
                     continue
-                t_inos = items.numbers(vocabulary=self.items, missing="negative")
-                sc = np.full(len(items), np.nan, dtype=np.float32)
-                t_ok = t_inos >= 0
-                sc[t_ok] = panel[i - lo][t_inos[t_ok]]
-                out.append(ItemList(items, scores=sc))
+                out.append(ItemList(items, scores=item_scores(items, self.items, panel[i - lo])))
         return out
 
     def __call__(self, query, items: ItemList) -> ItemList:
@@ -684,16 +635,12 @@ class SLIMScorer(Component):
         through in panels of at most ``PANEL_BYTES``.  Returns (item numbers [B x n] with -1
         padding, scores [B x n] with NaN padding), like ``ItemKNNScorer.recommend_batch``.
         """
-        from .basic import HistoryBatch
-
-        if isinstance(queries, HistoryBatch) and not (
-                queries.items is self.items or queries.items == self.items):
-            queries = queries.queries()  # (another item vocabulary: the per-query mapping)
+        queries = resolve_queries(queries, self.items)
         w = self._device_weights()
         if isinstance(queries, HistoryBatch):
             hist = queries.csr(with_values=False)
         else:
-            hist = self._query_csr([RecQuery.create(q) for q in queries])
+            hist = self._query_csr(queries)
         B = hist.shape[0]
         n = int(n)
         cols = len(self.items) if n < 0 else n

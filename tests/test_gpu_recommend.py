@@ -67,6 +67,22 @@ def test_gather_rows_matches_numpy(gpu, wide):
     assert got.shape[0] == 0 and got.indices.numel() == 0
 
 
+def test_csr_without_values_uploads_and_gathers(gpu):
+    "``from_arrays(values=None)``: a 2 x 4 CSR of structure only, cut by ``gather_rows``."
+    import torch
+
+    from lkpy_amd import _device as D
+
+    csr = D.DeviceCSR.from_arrays(np.array([0, 2, 3], np.int64), np.array([1, 3, 0], np.int32),
+                                  None, (2, 4), gpu)
+    assert csr.values is None and csr.shape == (2, 4) and csr.nnz == 3
+    assert csr.indptr.dtype == torch.int64 and csr.indices.dtype == torch.int32
+    got = D.gather_rows(csr, np.array([1, -1, 0, 1], np.int32), with_values=False)
+    assert got.values is None and got.shape == (4, 4)
+    assert got.indptr.cpu().tolist() == [0, 1, 1, 3, 4] == got.h_indptr.tolist()
+    assert got.indices.cpu().tolist() == [0, 1, 3, 0]
+
+
 @pytest.fixture(scope="module")
 def ml_ds():
     from lkpy_amd.data import load_movielens_npz
