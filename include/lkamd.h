@@ -904,6 +904,47 @@ int lk_mf_score_pairs(const float *d_users, int32_t ld_users, int64_t n_users,
                       const int32_t *d_user_rows, int64_t n_queries, const int64_t *d_tgt_ptr,
                       const int32_t *d_tgt_items, int64_t total, float *d_out, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Stochastic top-N ranking (csrc/stochastic.hip): the sort keys of
+ * `StochasticTopNRanker._compute_keys` (src/lenskit/stochastic/_ranker.py:119-156) for a panel
+ * of score rows; lk_argtopn of a key row is one Plackett-Luce sample, lk_take_scores its keys
+ * (replacing `valid_items.top_n(n, scores=keys)`, _ranker.py:113-117).
+ *   x = score * scale (_ranker.py:123).  Only finite scores outside the row's exclusion CSR row
+ *   (int64 offsets, int32 ascending items, as lk_score_topk takes it; NULL: none) take part --
+ *   `valid_mask`, _ranker.py:104-105; N = their count.
+ *   transform  LK_STOCHASTIC_SOFTMAX: log w = x - max - log sum exp(x - max)   (_ranker.py:140-144)
+ *              LK_STOCHASTIC_LINEAR:  w = t / sum t, t = (x - min) / (max - min); w = 1 / N when
+ *                                     max == min or the sum is 0                (_ranker.py:125-139)
+ *              LK_STOCHASTIC_NONE:    w = x                                     (_ranker.py:145-146)
+ *   key        g = max(log w, log FLT_MIN) - log(-log u).  The reference's key
+ *              log(u) / max(w, FLT_MIN) (_ranker.py:149-153) is -exp(-g): the same order, kept in
+ *              the log domain because its float32 value is -inf for every weight on the clamp.
+ *   u          Philox4x32-10 with key `seed` and counter (item >> 2, sample, stream lo, stream hi);
+ *              word (item & 3) = b gives u = (2 (b >> 9) + 1) 2^-24.  A draw depends on (seed,
+ *              stream, sample, item number) only.
+ * lk_stochastic_row_stats: d_stats [n_rows x 4] = max x, min x, the sum (of exp(x - max), of t, 0
+ *   for NONE) as float32 and N as int32, per row.  One pass shared by every sample of a call.
+ * lk_stochastic_keys: d_keys [n_rows x ld_keys] = g, NaN for the entries that take no part
+ *   (lk_argtopn skips them).  d_streams: uint64 [n_rows].
+ * lk_stochastic_key_of_bits: d_out[i] = max(d_log_weight[i], log FLT_MIN) - log(-log u(d_bits[i])),
+ *   the key function on given random words (tests: both ends of u).
+ * Reductions run in an order fixed by row_len alone and use no atomics: a row has the same stats
+ * and keys alone, in any batch, at any leading dimension.
+ * ---------------------------------------------------------------------- */
+#define LK_STOCHASTIC_NONE 0
+#define LK_STOCHASTIC_SOFTMAX 1
+#define LK_STOCHASTIC_LINEAR 2
+int lk_stochastic_row_stats(const float *d_scores, int64_t n_rows, int64_t row_len, int64_t ld,
+                            const int64_t *d_excl_ptr, const int32_t *d_excl_items,
+                            int32_t transform, float scale, float *d_stats, void *stream);
+int lk_stochastic_keys(const float *d_scores, int64_t n_rows, int64_t row_len, int64_t ld,
+                       const int64_t *d_excl_ptr, const int32_t *d_excl_items, int32_t transform,
+                       float scale, const float *d_stats, uint64_t seed,
+                       const uint64_t *d_streams, uint32_t sample, float *d_keys, int64_t ld_keys,
+                       void *stream);
+int lk_stochastic_key_of_bits(const float *d_log_weight, const uint32_t *d_bits, int64_t n,
+                              float *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

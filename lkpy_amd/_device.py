@@ -154,6 +154,12 @@ def blank_rows(idx: torch.Tensor, scores: torch.Tensor, valid: np.ndarray) -> No
         scores[bad] = float("nan")
 
 
+def blank_panel_rows(panel: torch.Tensor, valid: np.ndarray) -> None:
+    "The rows of a [B x items] score panel whose query is not ``valid`` (host bool [B]): NaN."
+    if not valid.all():
+        panel[torch.from_numpy(np.flatnonzero(~valid)).to(panel.device)] = float("nan")
+
+
 @dataclass
 class DeviceCSR:
     "CSR in HBM: the SparseRowArray layout (offsets i32/i64, indices i32, values f32)."
@@ -1154,6 +1160,69 @@ def score_dense(users: torch.Tensor, items: torch.Tensor, k: int) -> torch.Tenso
         lib.lk_score_dense(_ptr(users), kp, B, _ptr(items), kp, I, int(k), _ptr(out), I, _stream()),
         "lk_score_dense",
     )
+    return out
+
+
+def _row_streams(streams, rows: int, dev) -> torch.Tensor:
+    "uint64 [rows] stream numbers (NumPy, or a device int64 tensor holding the bits) in HBM"
+    if isinstance(streams, torch.Tensor):
+        assert streams.dtype == torch.int64 and streams.is_contiguous()
+        streams = streams.to(dev)
+    else:
+        host = np.ascontiguousarray(streams, dtype=np.uint64).reshape(-1)
+        streams = torch.from_numpy(host.view(np.int64)).to(dev)
+    assert streams.shape == (rows,)
+    return streams
+
+
+def stochastic_keys(panel: torch.Tensor, streams, *, transform, scale: float, seed: int,
+                    sample: int = 0, excl=None, stats: torch.Tensor | None = None,
+                    out: torch.Tensor | None = None):
+    """
+    The sort keys of the stochastic ranker (lk_stochastic_row_stats, lk_stochastic_keys) for a
+    [rows x len] f32 device panel of scores (rows ``stride(0)`` apart): ``argtopn`` of a key row is
+    one sampled ranking.  ``streams``: uint64 [rows]; ``seed``: 64 bits; ``excl``: a ``DeviceCSR``
+    or (int64 offsets, int32 sorted items) whose entries take no part.  ``stats`` from an earlier
+    call on the same panel skips the statistics pass (the samples of one call share it); ``out``:
+    a contiguous [rows x len] f32 buffer to write the keys into.  Returns (keys, stats): stats is
+    [rows x 4] f32 -- max, min, sum, and the count's int32 bits.
+    """
+    lib = _native.require_gpu()
+    assert panel.dtype == torch.float32 and panel.dim() == 2
+    rows, ln = panel.shape
+    assert ln <= 1 or panel.stride(1) == 1
+    ld = panel.stride(0) if rows > 1 and ln > 0 else max(ln, 1)
+    assert ld >= ln
+    dev = panel.device
+    code = _native.STOCHASTIC_TRANSFORMS[transform]
+    ptr = items = None
+    if excl is not None:
+        ptr, items = (excl.indptr, excl.indices) if isinstance(excl, DeviceCSR) else excl
+        assert ptr.dtype == torch.int64 and items.dtype == torch.int32 and ptr.shape == (rows + 1,)
+    if stats is None:
+        stats = torch.empty((rows, 4), dtype=torch.float32, device=dev)
+        check(lib.lk_stochastic_row_stats(_ptr(panel), rows, ln, ld, _ptr(ptr), _ptr(items), code,
+                                          float(scale), _ptr(stats), _stream()),
+              "lk_stochastic_row_stats")
+    assert stats.shape == (rows, 4) and stats.is_contiguous()
+    if out is None:
+        out = torch.empty((rows, ln), dtype=torch.float32, device=dev)
+    assert out.shape == (rows, ln) and out.is_contiguous() and out.dtype == torch.float32
+    check(lib.lk_stochastic_keys(_ptr(panel), rows, ln, ld, _ptr(ptr), _ptr(items), code,
+                                 float(scale), _ptr(stats), int(seed) & (2**64 - 1),
+                                 _ptr(_row_streams(streams, rows, dev)), int(sample), _ptr(out), ln,
+                                 _stream()), "lk_stochastic_keys")
+    return out, stats
+
+
+def stochastic_key_of_bits(log_weight: torch.Tensor, bits: torch.Tensor) -> torch.Tensor:
+    "The key function on given random words (lk_stochastic_key_of_bits); ``bits``: int32 bits."
+    lib = _native.require_gpu()
+    assert log_weight.dtype == torch.float32 and bits.dtype == torch.int32
+    assert log_weight.is_contiguous() and bits.is_contiguous() and log_weight.shape == bits.shape
+    out = torch.empty_like(log_weight)
+    check(lib.lk_stochastic_key_of_bits(_ptr(log_weight), _ptr(bits), log_weight.numel(),
+                                        _ptr(out), _stream()), "lk_stochastic_key_of_bits")
     return out
 
 

@@ -38,6 +38,8 @@ FLEXMF_ADAMW = 0
 FLEXMF_SPARSE_ADAM = 1
 FLEXMF_MAX_K = 256
 
+STOCHASTIC_TRANSFORMS = {None: 0, "softmax": 1, "linear": 2}
+
 
 class FlexMFTables(ctypes.Structure):
     "``lk_flexmf_tables``: u_embed, i_embed, u_bias, i_bias and their two moment tables."
@@ -237,6 +239,14 @@ def _declare(lib):
             c_int, [vp, c_int32, c_int64, vp, c_int32, c_int64, c_int32, vp, c_int64, vp, vp,
                     c_int64, vp, vp]
         ),
+        "lk_stochastic_row_stats": (
+            c_int, [vp, c_int64, c_int64, c_int64, vp, vp, c_int32, c_float, vp, vp]
+        ),
+        "lk_stochastic_keys": (
+            c_int, [vp, c_int64, c_int64, c_int64, vp, vp, c_int32, c_float, vp, ctypes.c_uint64,
+                    vp, ctypes.c_uint32, vp, c_int64, vp]
+        ),
+        "lk_stochastic_key_of_bits": (c_int, [vp, vp, c_int64, vp, vp]),
         "lk_als_implicit_half_epoch_host": (
             c_int,
             [vp, c_int, vp, vp, c_int64, c_int64, c_int32, vp, vp, vp, c_int32, vp],

@@ -293,12 +293,7 @@ class ImplicitMFScorer(UsesTrainer, Component):
         padding, scores [B x n] with NaN padding) as host arrays (``device_output``: as device
         tensors, nothing downloaded).
         """
-        queries = resolve_queries(queries, self.items)
-        pending: list = []  # the fold-in's status is read once the scoring is queued behind it
-        if isinstance(queries, HistoryBatch):
-            u, valid, hist = self._history_batch_embeddings(queries, pending)
-        else:
-            u, valid, hist = self._query_embeddings(queries, pending)
+        u, valid, hist, pending = self._batch_operands(queries)
         st = self._device_state()
         if exclude_history:
             idx, sc = D.score_topk(u, st["Q"], self.config.embedding_size, n, hist.indptr,
@@ -311,6 +306,30 @@ class ImplicitMFScorer(UsesTrainer, Component):
         if device_output:
             return idx, sc
         return D.lists_to_host(idx, sc)
+
+    def _batch_operands(self, queries):
+        """
+        What scoring a batch starts from: (device [B x KP] embeddings, valid, history CSR, the
+        fold-in plans whose status is read once the scoring is queued behind them).
+        """
+        queries = resolve_queries(queries, self.items)
+        pending: list = []
+        if isinstance(queries, HistoryBatch):
+            return (*self._history_batch_embeddings(queries, pending), pending)
+        return (*self._query_embeddings(queries, pending), pending)
+
+    def dense_scores_batch(self, queries):
+        """
+        Every item's score for many queries at once, left on the device: (panel f32 [B x items],
+        valid, history CSR) -- ``recommend_batch``'s operands scored by ``lk_score_dense``.  The
+        row of a query that cannot be scored is NaN; the history is for the caller to exclude.
+        """
+        u, valid, hist, pending = self._batch_operands(queries)
+        panel = D.score_dense(u, self._device_state()["Q"], self.config.embedding_size)
+        for plan in pending:
+            plan.check_status()
+        D.blank_panel_rows(panel, valid)
+        return panel, valid, hist
 
 
 class ImplicitMFTrainer(ModelTrainer):

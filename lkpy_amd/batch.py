@@ -18,9 +18,20 @@ def recommend(pipe: Pipeline, users, n: int, *, batch_size: int = 16384) -> Item
     """Ordered lists of ``n`` recommendations as an ``ItemListCollection`` keyed by ``user_id``
     (what ``BatchResults.output("recommendations")`` is in the reference,
     src/lenskit/batch/_runner.py:157-191): ``out.lookup(user)`` / ``out.lookup(user_id=user)``,
-    iteration over ``(key, list)``, ``out.to_df()``."""
+    iteration over ``(key, list)``, ``out.to_df()``.  A pipeline whose ranker is a
+    ``StochasticTopNRanker`` gets sampled rankings (``_sample_panels``), any other the scorer's
+    own top-N."""
     scorer = pipe.node("scorer").component
     lookup = pipe.node("history-lookup").component
+    if _stochastic_ranker(pipe) is not None:
+        # a sampled ranking is not the scorer's own top-N: the lists come from the ranker, by
+        # panels where the scorer has them, else through the pipeline user by user
+        if not _has_panels(scorer, lookup):
+            return ItemListCollection.from_dict(
+                {u: pipe.run("recommender", query=u, n=n) for u in users}, key=("user_id",))
+        ids, idx, keys = _sample_panels(pipe, users, n, 1, batch_size)
+        return ItemListCollection.from_arrays(ids, idx[:, 0], keys[:, 0], scorer.items,
+                                              key=("user_id",))
     if hasattr(scorer, "recommend_batch") and hasattr(lookup, "batch") and \
             getattr(scorer, "accepts_history_batch", False):
         # the whole batch by user number: the histories are rows of the HBM-resident training
@@ -53,6 +64,77 @@ def recommend(pipe: Pipeline, users, n: int, *, batch_size: int = 16384) -> Item
         for u in users:
             out[u] = pipe.run("recommender", query=u, n=n)
     return ItemListCollection.from_dict(out, key=("user_id",))
+
+
+# what the score panel and the key panel of one chunk of a stochastic batch may take together
+STOCHASTIC_PANEL_BYTES = 4 << 30
+
+
+def _stochastic_ranker(pipe: Pipeline):
+    "the pipeline's ranker when it is a ``StochasticTopNRanker``, else None"
+    from .stochastic import StochasticTopNRanker
+
+    node = pipe.nodes.get(pipe.aliases.get("ranker", "ranker"))
+    comp = None if node is None else node.component
+    return comp if isinstance(comp, StochasticTopNRanker) else None
+
+
+def _has_panels(scorer, lookup) -> bool:
+    return hasattr(scorer, "dense_scores_batch") and hasattr(lookup, "batch") and \
+        getattr(scorer, "accepts_history_batch", False)
+
+
+def _sample_panels(pipe: Pipeline, users, n: int, samples: int, batch_size: int):
+    """
+    ``samples`` sampled rankings per user, whole batches at a time: the scorer's
+    ``dense_scores_batch`` panel -> the stochastic ranker's ``rank_panel``, in chunks of
+    ``STOCHASTIC_PANEL_BYTES / (8 n_items)`` rows (a float32 score and a float32 key per item).
+    Returns (user ids, item numbers [B x S x n], keys [B x S x n]).
+    """
+    ranker = _stochastic_ranker(pipe)
+    scorer = pipe.node("scorer").component
+    lookup = pipe.node("history-lookup").component
+    ids = users if isinstance(users, np.ndarray) else np.asarray(list(users))
+    n = ranker._length(n)
+    width = len(scorer.items) if n < 0 else n
+    rows = max(1, min(batch_size, STOCHASTIC_PANEL_BYTES // (8 * max(1, len(scorer.items)))))
+    hb = lookup.batch(ids)
+    streams = ranker.streams(hb.user_ids)  # (the ids as the lookup types them, like a query's)
+    idx = np.full((len(ids), samples, width), -1, np.int32)
+    keys = np.full((len(ids), samples, width), np.nan, np.float32)
+    for s in range(0, len(ids), rows):
+        panel, _valid, hist = scorer.dense_scores_batch(hb.subset(slice(s, s + rows)))
+        i, k = ranker.rank_panel(panel, streams[s:s + rows], n, excl=hist, samples=samples)
+        idx[s:s + rows, :, :i.shape[2]] = i
+        keys[s:s + rows, :, :i.shape[2]] = k
+    return ids, idx, keys
+
+
+def recommend_samples(pipe: Pipeline, users, n: int, samples: int, *,
+                      batch_size: int = 16384) -> ItemListCollection:
+    """
+    ``samples`` sampled rankings of ``n`` items per user from a pipeline whose ranker is a
+    :class:`lkpy_amd.stochastic.StochasticTopNRanker`, keyed by ``(user_id, sample)``; sample 0 is
+    what ``recommend`` draws.  A scorer without ``dense_scores_batch`` is scored through the
+    pipeline user by user and ranked ``samples`` times.
+    """
+    ranker = _stochastic_ranker(pipe)
+    if ranker is None:
+        raise TypeError("recommend_samples needs a pipeline whose ranker is a StochasticTopNRanker")
+    samples = int(samples)
+    scorer = pipe.node("scorer").component
+    if not _has_panels(scorer, pipe.node("history-lookup").component):
+        out = {}
+        for u in users:
+            got = pipe.run_all("history-lookup", "scorer", query=u)
+            lists = ranker.sample(got["scorer"], got["history-lookup"], n, samples=samples)
+            out.update({(u, s): il for s, il in enumerate(lists)})
+        return ItemListCollection.from_dict(out, key=("user_id", "sample"))
+    ids, idx, keys = _sample_panels(pipe, users, n, samples, batch_size)
+    pairs = [(u, s) for u in ids.tolist() for s in range(samples)]
+    flat = idx.shape[0] * idx.shape[1]
+    return ItemListCollection.from_arrays(pairs, idx.reshape(flat, -1), keys.reshape(flat, -1),
+                                          scorer.items, key=("user_id", "sample"))
 
 
 def predict(pipe: Pipeline, pairs, *, batch_size: int = 16384) -> ItemListCollection:

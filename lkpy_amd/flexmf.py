@@ -202,6 +202,19 @@ class FlexMFScorerBase(UsesTrainer, Component):
         :class:`lkpy_amd.basic.HistoryBatch`.  Returns (item numbers [B x n] with -1 padding,
         scores [B x n] with NaN padding); an unknown user's row is all padding.
         """
+        u, valid, hist = self._batch_operands(queries, exclude_history)
+        st = self._device_state()
+        if hist is not None:
+            idx, sc = D.score_topk(u, st["Q"], self._score_k, n, hist.indptr, hist.indices)
+        else:
+            idx, sc = D.score_topk(u, st["Q"], self._score_k, n)
+        D.blank_rows(idx, sc, valid)
+        if device_output:
+            return idx, sc
+        return D.lists_to_host(idx, sc)
+
+    def _batch_operands(self, queries, exclude_history: bool = True):
+        "(device [B x KP] user rows, valid, the CSR of items to strike | None) of a batch"
         queries = resolve_queries(queries, self.items)
         st = self._device_state()
         hist = None
@@ -212,14 +225,18 @@ class FlexMFScorerBase(UsesTrainer, Component):
             hist = D.DeviceCSR.from_arrays(ptr, idx, None, (len(queries), len(self.items)),
                                            st["device"])
         u, valid = self._user_rows(user_numbers(queries, self.users))
-        if hist is not None:
-            idx, sc = D.score_topk(u, st["Q"], self._score_k, n, hist.indptr, hist.indices)
-        else:
-            idx, sc = D.score_topk(u, st["Q"], self._score_k, n)
-        D.blank_rows(idx, sc, valid)
-        if device_output:
-            return idx, sc
-        return D.lists_to_host(idx, sc)
+        return u, valid, hist
+
+    def dense_scores_batch(self, queries):
+        """
+        Every item's score for many queries at once, left on the device: (panel f32 [B x items],
+        valid, history CSR) -- ``recommend_batch``'s operands scored by ``lk_score_dense``.  An
+        unknown user's row is NaN; the history is for the caller to exclude.
+        """
+        u, valid, hist = self._batch_operands(queries)
+        panel = D.score_dense(u, self._device_state()["Q"], self._score_k)
+        D.blank_panel_rows(panel, valid)
+        return panel, valid, hist
 
 
 class FlexMFImplicitScorer(FlexMFScorerBase):

@@ -130,13 +130,15 @@ class Pipeline:
         self.nodes[name] = Node(name, comp, wiring)
         return name
 
-    def replace_component(self, name, comp, config=None):
-        "keeps the node's slot and wiring (``_builder.py:441-443``)"
+    def replace_component(self, name, comp, config=None, **wiring):
+        """keeps the node's slot and wiring (``_builder.py:441-443``); ``wiring`` adds inputs the
+        new component takes beyond them (a stochastic ranker's ``query="history-lookup"``)"""
         node = self.nodes[name]
         if inspect.isclass(comp):
             comp = comp(config) if config is not None else comp()
         node.component = comp
         node.kind = "component"
+        node.wiring.update(wiring)
 
     def use_first_of(self, name, *sources):
         self.nodes[name] = Node(name, kind="first-of", wiring={"sources": list(sources)})
@@ -204,7 +206,7 @@ class Pipeline:
             comp_cls = import_path_string(path)
             config = spec.get("config", None)
             if name in pipe.nodes:
-                pipe.replace_component(name, comp_cls, config)
+                pipe.replace_component(name, comp_cls, config, **spec.get("inputs", {}))
             else:
                 pipe.add_component(name, comp_cls, config, **spec.get("inputs", {}))
         return pipe

@@ -1,0 +1,208 @@
+"""
+Stochastic top-N ranking: ``lenskit.stochastic.StochasticTopNRanker``
+(src/lenskit/stochastic/_ranker.py:19-156) -- a ranking sampled from the Plackett-Luce
+distribution over the (transformed) scores by exponential-sort sampling -- on the device, for one
+list and for whole panels of score rows with many samples per row.
+
+The keys come from ``lk_stochastic_row_stats`` / ``lk_stochastic_keys`` (csrc/stochastic.hip), the
+list from ``lk_argtopn`` + ``lk_take_scores``.  The key is ``g = log w~ - log(-log u)``; the
+reference's ``log(u) / max(w, tiny)`` is ``-exp(-g)``, the same order.
+
+**Random numbers.**  The reference draws from a NumPy generator derived per query
+(``derivable_rng``, src/lenskit/random.py:269-345); a device kernel cannot reproduce that stream,
+so the draws are defined here: Philox4x32-10 keyed by a 64-bit ``seed`` with the counter
+``(item >> 2, sample, stream)``, one 64-bit *stream* per ranked row.
+
+- ``seed``: ``np.random.SeedSequence(s).generate_state(1, np.uint64)[0]`` for the seed ``s`` of the
+  ``rng`` spec (``None`` and a bare ``"user"``: fresh entropy; a ``Generator`` / ``BitGenerator``:
+  one raw draw from it).
+- ``rng="user"`` or ``(s, "user")``: the stream is the user id -- an integer id itself (mod 2^64),
+  a ``str`` / ``bytes`` id folded the way the reference's ``_bytes_seed`` does (the four int32 words
+  of its md5 digest XOR-ed, absolute value) -- so the same user always gets the same ranking, in
+  any batch.  A query without a user id takes a counted stream, below.
+- any other spec: the stream is ``(calls so far << 32) | row position`` -- every call (``__call__``,
+  ``streams`` for a batch) draws afresh, the rows of one batch differ.
+
+An item's draw is addressed by its *item number*: its number in the list's vocabulary (its
+position for a list without one), the column of a panel.  One list and the same list inside a
+batch therefore agree bit for bit.
+"""
+
+from __future__ import annotations
+
+from hashlib import md5
+from typing import Any, Literal
+
+import numpy as np
+from pydantic import BaseModel
+
+from .data import ItemList, RecQuery
+from .pipeline import Component
+
+_MASK64 = (1 << 64) - 1
+
+
+class StochasticTopNConfig(BaseModel, arbitrary_types_allowed=True):
+    "src/lenskit/stochastic/_ranker.py:19-56"
+
+    n: int | None = None  # the list length; -1 or None: every scored item
+    rng: Any = None  # DerivableSeed: a seed, "user", or (seed, "user")
+    transform: Literal["softmax", "linear"] | None = "softmax"
+    scale: float = 1.0  # multiplies the scores before the transform (the softmax's beta)
+
+
+def _bytes_stream(key: bytes) -> int:
+    words = np.frombuffer(md5(key).digest(), np.int32)
+    return abs(int(np.bitwise_xor.reduce(words)))
+
+
+def user_stream(user_id) -> int | None:
+    "The stream of a user id (module docstring); None for an id that cannot give one."
+    if isinstance(user_id, (int, np.integer)):
+        return int(user_id) & _MASK64
+    if isinstance(user_id, str):
+        return _bytes_stream(user_id.encode("utf8"))
+    if isinstance(user_id, (bytes, np.bytes_)):
+        return _bytes_stream(bytes(user_id))
+    return None
+
+
+def _seed_state(seed) -> int:
+    "64 bits of a seed: SeedSequence(seed).generate_state(1, uint64)"
+    if isinstance(seed, np.random.Generator):
+        seed = seed.bit_generator
+    if isinstance(seed, np.random.BitGenerator):
+        return int(seed.random_raw()) & _MASK64
+    if not isinstance(seed, np.random.SeedSequence):
+        seed = np.random.SeedSequence(seed)
+    return int(seed.generate_state(1, np.uint64)[0])
+
+
+def parse_rng(spec) -> tuple[int, bool]:
+    "An ``rng`` spec (random.py:315-349) -> (64-bit seed, streams by user id?)"
+    if isinstance(spec, str):
+        if spec != "user":
+            raise ValueError(f"unrecognized rng specification {spec!r}")
+        return _seed_state(None), True
+    if isinstance(spec, tuple):
+        if len(spec) != 2 or spec[1] != "user":
+            raise ValueError(f"unrecognized key in rng specification {spec!r}")
+        return _seed_state(spec[0]), True
+    return _seed_state(spec), False
+
+
+class StochasticTopNRanker(Component):
+    """
+    Stochastic top-N ranking with an optional weight transformation (``StochasticTopNRanker``,
+    _ranker.py:59-156).  ``__call__`` ranks one scored list; :meth:`rank_panel` ranks every row of
+    a device panel of scores, ``samples`` times, from one statistics pass.
+    """
+
+    config: StochasticTopNConfig
+
+    def __init__(self, config=None, **kwargs):
+        if isinstance(config, dict) and isinstance(config.get("rng"), list):
+            config = {**config, "rng": tuple(config["rng"])}  # (a TOML / JSON [seed, "user"])
+        super().__init__(config, **kwargs)
+        self.seed, self.by_user = parse_rng(self.config.rng)
+        self.calls = 0
+
+    # -- streams ------------------------------------------------------------------------------
+    def streams(self, user_ids, count: int | None = None) -> np.ndarray:
+        """
+        The uint64 streams of one call's rows: ``user_ids`` per row (None: ``count`` rows without
+        ids).  Counts as one call.
+        """
+        n = len(user_ids) if user_ids is not None else int(count)
+        out = (np.uint64(self.calls << 32) | np.arange(n, dtype=np.uint64))
+        self.calls = (self.calls + 1) & 0xFFFFFFFF
+        if self.by_user and user_ids is not None:
+            if isinstance(user_ids, np.ndarray) and user_ids.dtype.kind in "iu":
+                out = user_ids.astype(np.int64).view(np.uint64) if user_ids.dtype.kind == "i" \
+                    else user_ids.astype(np.uint64)
+            else:  # id by id: strings, bytes, a list of mixed ids
+                ids = user_ids.tolist() if isinstance(user_ids, np.ndarray) and \
+                    user_ids.dtype.kind != "O" else user_ids
+                for i, u in enumerate(ids):
+                    s = None if u is None else user_stream(u)
+                    if s is not None:
+                        out[i] = s
+        return np.ascontiguousarray(out, dtype=np.uint64)
+
+    def _length(self, n: int | None) -> int:
+        if n is None or n < 0:
+            n = self.config.n or -1  # (_ranker.py:110-111)
+        return int(n)
+
+    # -- panels -------------------------------------------------------------------------------
+    def rank_panel(self, panel, streams, n: int | None, *, excl=None, samples: int = 1,
+                   first_sample: int = 0, device_output: bool = False):
+        """
+        ``samples`` sampled rankings of every row of ``panel`` (device f32 [B x items]; non-finite
+        and ``excl``-uded entries take no part): (item numbers int32 [B x S x n] with -1 padding,
+        keys f32 [B x S x n] with NaN padding), sample ``first_sample + s`` at ``[:, s]``.  The row
+        statistics are computed once and one key panel is reused by every sample.
+        """
+        import torch
+
+        from . import _device as D
+
+        n = self._length(n)
+        B, I = panel.shape
+        cols = I if n < 0 else min(n, I)
+        samples = int(samples)
+        idx = torch.full((B, samples, max(n, cols)), -1, dtype=torch.int32, device=panel.device)
+        keys = torch.full(idx.shape, float("nan"), dtype=torch.float32, device=panel.device)
+        if B and cols and samples:
+            d_streams = D._row_streams(streams, B, panel.device)
+            buf = stats = None
+            for s in range(samples):
+                buf, stats = D.stochastic_keys(
+                    panel, d_streams, transform=self.config.transform, scale=self.config.scale,
+                    seed=self.seed, sample=first_sample + s, excl=excl, stats=stats, out=buf)
+                picked = D.argtopn(buf, n)
+                idx[:, s, :cols] = picked
+                keys[:, s, :cols] = D.take_scores(buf, picked)
+        if device_output:
+            return idx, keys
+        return D.to_host(idx), D.to_host(keys)
+
+    # -- one list -------------------------------------------------------------------------------
+    def sample(self, items: ItemList, query=None, n: int | None = None, *, samples: int = 1,
+               include_weights: bool = False) -> list[ItemList]:
+        "``samples`` rankings of one scored list (``__call__`` is the first)."
+        import torch
+
+        from . import _device as D
+
+        query = RecQuery.create(query)
+        scores = items.scores()
+        if scores is None:
+            raise ValueError("item list must have scores")  # (_ranker.py:100-102)
+        stream = self.streams(None if query.user_id is None else [query.user_id], 1)
+        valid = np.isfinite(scores)
+        if not valid.any():
+            return [ItemList(items[valid], ordered=True) for _ in range(samples)]
+        # a one-row panel over the item numbers: the kernels, and the draws, of a batch row
+        if items.vocabulary is not None:
+            nums, width = items.numbers(), len(items.vocabulary)
+        else:
+            nums, width = np.arange(len(items)), len(items)
+        row = np.full((1, width), np.nan, dtype=np.float32)
+        row[0, nums] = scores
+        position = np.full(width, -1, dtype=np.int64)
+        position[nums] = np.arange(len(items))
+        idx, keys = self.rank_panel(torch.from_numpy(row).to(D.device()), stream, n,
+                                    samples=samples)
+        out = []
+        for s in range(samples):
+            keep = idx[0, s] >= 0
+            g = keys[0, s][keep]
+            ranked = items._take(position[idx[0, s][keep]], ordered=True)
+            extra = {"weight": -np.exp(-g.astype(np.float64))} if include_weights else {}
+            out.append(ItemList(ranked, ordered=True, scores=g, **extra))
+        return out
+
+    def __call__(self, items: ItemList, query=None, n: int | None = None, *,
+                 include_weights: bool = False) -> ItemList:
+        return self.sample(items, query, n, include_weights=include_weights)[0]
