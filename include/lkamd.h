@@ -777,6 +777,64 @@ int lk_predict_errors(int64_t n_lists, const int64_t *d_pred_ptr, const int32_t 
                       void *stream);
 
 /* ------------------------------------------------------------------------
+ * Exposure, diversity, popularity and reranking metrics (csrc/diversity.hip; the values are
+ * composed on the host by lkpy_amd/metrics.py and lkpy_amd/reranking_metrics.py).  Item NUMBERS
+ * throughout.  Lists are the dense int32 [n_lists x ld] panels of lk_rank_stats: the first `len`
+ * columns are read, entries < 0 are dropped BEFORE ranks are assigned, `cutoff` keeps the ranks
+ * <= cutoff (0 = whole list); an item number >= n_items is an UNKNOWN item: it keeps its rank.
+ * A rank-weight table is float64 with d_weights[rank - 1] = w(rank), w_ld >= the longest kept
+ * list; NULL = every weight is 1.  All calls are asynchronous on `stream`, wave64, no float
+ * atomics; a product and the sum it enters are two roundings.
+ *
+ * lk_item_exposure: d_totals[item] += w(rank) over every kept known entry inside the cutoff
+ *   (`GiniAccumulator.add`, ranking/_gini.py:127-129, with the weights of `ListGini` /
+ *   `ExposureGini.measure_list`, _gini.py:72-75, 112-116).  d_totals float64 [n_items] is
+ *   accumulated ONTO; an item's additions happen in list order, then rank order, as ONE chain
+ *   that starts at the value already there: the result is bit-identical to
+ *   `for list in lists: totals[items] += weights` and to the same lists fed in several calls.
+ *   d_ws: lk_item_exposure_workspace_bytes(n_lists, len) bytes (a stable radix sort of
+ *   item -> entry, then one wave per item walks its run).
+ * lk_list_category_stats: the item x category matrix as CSR (int64 offsets [n_items + 1], int32
+ *   columns without duplicates inside a row, float64 values), n_cats <= lk_list_category_max()
+ *   (7168: the column sums s_c = sum_i w_i M[item_i, c] of a list live in LDS, 8 bytes each).
+ *   s_c is added over the known kept items in rank order, w_i the weight of the item's own rank:
+ *   bit-identical to a sequential float64 column sum of `matrix * weights[:, None]`
+ *   (ranking/_entropy.py:78-81).  d_out_known int32 [n_lists]: known items inside the cutoff;
+ *   d_out_stats float64 [3 x n_lists]: sq_sum = sum_c s_c^2, self_sum = sum_i sum_c M[i, c]^2
+ *   (with unit weights sum_{i<j} v_i . v_j = (sq_sum - self_sum) / 2: `intra_list_similarity`,
+ *   ranking/_ils.py:39-44), entropy = -sum_c p_c log2 p_c, p = (s + 1e-6) / sum(s + 1e-6)
+ *   (`matrix_column_entropy`, _entropy.py:81-86).
+ * lk_list_gather_mean: d_out_sum[list] = sum, in rank order, of d_table[item] (float64
+ *   [n_items]) over the kept entries inside the cutoff, an unknown item adding 0;
+ *   d_out_len[list] = those entries, unknown ones included (`MeanPopRank.measure_list`,
+ *   ranking/_pop.py:77-84).
+ * lk_list_pair_stats: ragged lists (int64 offsets, item numbers >= 0, distinct inside a list):
+ *   pair q is reference list d_a_rows[q] (q itself when d_a_rows is NULL; < 0 = no reference
+ *   list, treated as an empty one) and reranked list q.  Depth 1 <= n <= 1024, d_weights
+ *   float64 [n].  d_out_rbo[q] = sum_{d=1..n} (overlap_d / d) * w_d with overlap_d =
+ *   |a[:d] & b[:d]|, added sequentially in d (reranking/_rbo.py:45-55; the host divides by the
+ *   total weight); d_out_lip[q] = max(n, largest 0-based position in a of an item of b[:n]) - n
+ *   and d_out_flag[q] = 1 where a is empty (reranking/_lip.py:37-48).  a is scanned once.
+ * ---------------------------------------------------------------------- */
+int32_t lk_list_category_max(void);
+size_t lk_item_exposure_workspace_bytes(int64_t n_lists, int64_t len);
+int lk_item_exposure(const int32_t *d_lists, int64_t n_lists, int64_t ld, int64_t len,
+                     int32_t cutoff, const double *d_weights, int64_t w_ld, int32_t n_items,
+                     double *d_totals, void *d_ws, void *stream);
+int lk_list_category_stats(const int32_t *d_lists, int64_t n_lists, int64_t ld, int64_t len,
+                           int32_t cutoff, int32_t n_items, const int64_t *d_cat_ptr,
+                           const int32_t *d_cat_cols, const double *d_cat_vals, int32_t n_cats,
+                           const double *d_weights, int64_t w_ld, int32_t *d_out_known,
+                           double *d_out_stats, void *stream);
+int lk_list_gather_mean(const int32_t *d_lists, int64_t n_lists, int64_t ld, int64_t len,
+                        int32_t cutoff, const double *d_table, int32_t n_items,
+                        double *d_out_sum, int32_t *d_out_len, void *stream);
+int lk_list_pair_stats(int64_t n_pairs, const int32_t *d_a_rows, const int64_t *d_a_ptr,
+                       const int32_t *d_a_items, const int64_t *d_b_ptr, const int32_t *d_b_items,
+                       int32_t n, const double *d_weights, double *d_out_rbo, int32_t *d_out_lip,
+                       int32_t *d_out_flag, void *stream);
+
+/* ------------------------------------------------------------------------
  * FlexMF implicit (csrc/flexmf.hip): the minibatch trainer of `lenskit.flexmf.FlexMFImplicitScorer`
  * -- score = b_u + b_i + p_u . q_i, logistic / pairwise (BPR) / WARP loss, AdamW or SparseAdam.
  * All tables are float32, row-major and UNPADDED ([rows x k], biases [rows]); a NULL bias table

@@ -1509,6 +1509,146 @@ def predict_errors(pred_ptr: torch.Tensor, pred_items: torch.Tensor | None,
 
 
 # ---------------------------------------------------------------------------------------
+# exposure / diversity / popularity / reranking metrics (csrc/diversity.hip)
+# ---------------------------------------------------------------------------------------
+
+CATEGORY_MAX = 7168  # category columns of lk_list_category_stats (lk_list_category_max())
+PAIR_STATS_MAX_DEPTH = 1024  # depth n of lk_list_pair_stats
+
+
+def _list_shape(lists: torch.Tensor, length):
+    assert lists.dtype == torch.int32 and lists.dim() == 2 and lists.is_contiguous()
+    B, ld = int(lists.shape[0]), int(lists.shape[1])
+    return B, ld, ld if length is None else int(length)
+
+
+def _check_table(weights, need: int):
+    if weights is None:
+        return 0
+    assert weights.dtype == torch.float64 and weights.dim() == 1 and weights.is_contiguous()
+    assert int(weights.shape[0]) >= need
+    return int(weights.shape[0])
+
+
+def item_exposure(lists: torch.Tensor, totals: torch.Tensor, cutoff: int = 0,
+                  weights: torch.Tensor | None = None, length: int | None = None) -> None:
+    """
+    ``totals[item] += w(rank)`` over the kept entries of ``lists`` (lk_item_exposure): device
+    int32 [B x ld] lists, float64 [n_items] ``totals`` accumulated in place, ``weights`` a device
+    float64 rank table or None (every weight 1).
+    """
+    lib = _native.require_gpu()
+    B, ld, ln = _list_shape(lists, length)
+    assert totals.dtype == torch.float64 and totals.dim() == 1 and totals.is_contiguous()
+    w_ld = _check_table(weights, min(ln, cutoff) if cutoff else ln)
+    wb = lib.lk_item_exposure_workspace_bytes(B, ln)
+    ws = torch.empty(max(wb, 1), dtype=torch.uint8, device=lists.device)
+    check(
+        lib.lk_item_exposure(_ptr(lists), B, ld, ln, int(cutoff), _ptr(weights), w_ld,
+                             int(totals.shape[0]), _ptr(totals), _ptr(ws), _stream()),
+        "lk_item_exposure",
+    )
+
+
+@dataclass
+class DeviceCategories:
+    "An item x category matrix in HBM: CSR with int64 offsets, int32 columns, float64 values."
+    indptr: torch.Tensor
+    indices: torch.Tensor
+    values: torch.Tensor
+    shape: tuple
+
+    @classmethod
+    def from_scipy(cls, mat, dev) -> "DeviceCategories":
+        import scipy.sparse as sps
+
+        m = sps.csr_array(mat)
+        m.sum_duplicates()
+        if m.shape[1] > CATEGORY_MAX:
+            raise ValueError(f"{m.shape[1]} category columns: the device keeps a list's column "
+                             f"sums in LDS and supports at most {CATEGORY_MAX}")
+        return cls(torch.from_numpy(np.ascontiguousarray(m.indptr, dtype=np.int64)).to(dev),
+                   torch.from_numpy(np.ascontiguousarray(m.indices, dtype=np.int32)).to(dev),
+                   torch.from_numpy(np.ascontiguousarray(m.data, dtype=np.float64)).to(dev),
+                   tuple(m.shape))
+
+
+def list_category_stats(lists: torch.Tensor, cats: DeviceCategories, cutoff: int = 0,
+                        weights: torch.Tensor | None = None, length: int | None = None):
+    """
+    Per list the category column sums' statistics (lk_list_category_stats).  Returns device
+    (known int32 [B], stats float64 [3 x B]: sq_sum, self_sum, entropy).
+    """
+    lib = _native.require_gpu()
+    B, ld, ln = _list_shape(lists, length)
+    n_items, C = int(cats.shape[0]), int(cats.shape[1])
+    if C > CATEGORY_MAX:
+        raise ValueError(f"{C} category columns: at most {CATEGORY_MAX} are supported")
+    assert cats.indptr.dtype == torch.int64 and int(cats.indptr.shape[0]) == n_items + 1
+    assert cats.indices.dtype == torch.int32 and cats.values.dtype == torch.float64
+    w_ld = _check_table(weights, min(ln, cutoff) if cutoff else ln)
+    known = torch.empty(B, dtype=torch.int32, device=lists.device)
+    stats = torch.empty((3, B), dtype=torch.float64, device=lists.device)
+    check(
+        lib.lk_list_category_stats(_ptr(lists), B, ld, ln, int(cutoff), n_items,
+                                   _ptr(cats.indptr), _ptr(cats.indices), _ptr(cats.values), C,
+                                   _ptr(weights), w_ld, _ptr(known), _ptr(stats), _stream()),
+        "lk_list_category_stats",
+    )
+    return known, stats
+
+
+def list_gather_mean(lists: torch.Tensor, table: torch.Tensor, cutoff: int = 0,
+                     length: int | None = None):
+    """
+    Per list the rank-order sum of ``table[item]`` (device float64 [n_items]) and the number of
+    kept entries (lk_list_gather_mean).  Returns device (sum float64 [B], length int32 [B]).
+    """
+    lib = _native.require_gpu()
+    B, ld, ln = _list_shape(lists, length)
+    assert table.dtype == torch.float64 and table.dim() == 1 and table.is_contiguous()
+    sums = torch.empty(B, dtype=torch.float64, device=lists.device)
+    lens = torch.empty(B, dtype=torch.int32, device=lists.device)
+    check(
+        lib.lk_list_gather_mean(_ptr(lists), B, ld, ln, int(cutoff), _ptr(table),
+                                int(table.shape[0]), _ptr(sums), _ptr(lens), _stream()),
+        "lk_list_gather_mean",
+    )
+    return sums, lens
+
+
+def list_pair_stats(a_ptr: torch.Tensor, a_items: torch.Tensor, b_ptr: torch.Tensor,
+                    b_items: torch.Tensor, n: int, weights: torch.Tensor,
+                    a_rows: torch.Tensor | None = None):
+    """
+    Rank-biased overlap's weighted agreement sum and least-item-promoted per pair of ragged lists
+    (lk_list_pair_stats): reference lists ``a`` (pair ``q`` takes row ``a_rows[q]``, ``q`` itself
+    without ``a_rows``), reranked lists ``b``.  Returns device (rbo_sum float64 [P], lip int32
+    [P], flag int32 [P]: 1 where the reference list is empty).
+    """
+    lib = _native.require_gpu()
+    P = int(b_ptr.shape[0]) - 1
+    dev = b_ptr.device
+    assert a_ptr.dtype == torch.int64 and b_ptr.dtype == torch.int64
+    assert a_items.dtype == torch.int32 and b_items.dtype == torch.int32
+    assert weights.dtype == torch.float64 and int(weights.shape[0]) >= n
+    if a_rows is None:
+        assert int(a_ptr.shape[0]) == P + 1
+    else:
+        assert a_rows.dtype == torch.int32 and int(a_rows.shape[0]) == P
+    rbo = torch.empty(P, dtype=torch.float64, device=dev)
+    lip = torch.empty(P, dtype=torch.int32, device=dev)
+    flag = torch.empty(P, dtype=torch.int32, device=dev)
+    check(
+        lib.lk_list_pair_stats(P, _ptr(a_rows), _ptr(a_ptr), _ptr(a_items), _ptr(b_ptr),
+                               _ptr(b_items), int(n), _ptr(weights), _ptr(rbo), _ptr(lip),
+                               _ptr(flag), _stream()),
+        "lk_list_pair_stats",
+    )
+    return rbo, lip, flag
+
+
+# ---------------------------------------------------------------------------------------
 # FlexMF implicit and explicit (csrc/flexmf.hip), ragged pair scoring (csrc/mf_pairs.hip)
 # ---------------------------------------------------------------------------------------
 

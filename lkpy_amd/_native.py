@@ -216,6 +216,21 @@ def _declare(lib):
                     c_int64, vp, vp, vp]
         ),
         "lk_predict_errors": (c_int, [c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "lk_list_category_max": (c_int32, []),
+        "lk_item_exposure_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+        "lk_item_exposure": (
+            c_int, [vp, c_int64, c_int64, c_int64, c_int32, vp, c_int64, c_int32, vp, vp, vp]
+        ),
+        "lk_list_category_stats": (
+            c_int, [vp, c_int64, c_int64, c_int64, c_int32, c_int32, vp, vp, vp, c_int32, vp,
+                    c_int64, vp, vp, vp]
+        ),
+        "lk_list_gather_mean": (
+            c_int, [vp, c_int64, c_int64, c_int64, c_int32, vp, c_int32, vp, vp, vp]
+        ),
+        "lk_list_pair_stats": (
+            c_int, [c_int64, vp, vp, vp, vp, vp, c_int32, vp, vp, vp, vp, vp]
+        ),
         "lk_flexmf_sample_negatives": (
             c_int, [vp, vp, c_int64, c_int64, vp, c_int64, c_int32, c_int, c_int, c_int32,
                     ctypes.c_uint64, ctypes.c_uint64, vp, vp]

@@ -659,6 +659,9 @@ class Dataset:
         self._rows = np.require(rows, dtype=np.int32)[order]
         self._cols = np.require(cols, dtype=np.int32)[order]
         self._attrs = {k: np.asarray(v)[order] for k, v in attrs.items()}
+        # item x category matrices (dense or scipy.sparse, row i = item number i) by attribute
+        # name: what the diversity metrics read (``items.attribute(name).cat_matrix()``)
+        self.item_attrs: dict[str, Any] = {}
         # repeated (user, item) pairs are kept as separate interactions (as the reference's
         # interaction tables do); consumers that need a MATRIX sum them, as SciPy's COO -> CSR
         # conversion does on the reference's path (src/lenskit/als/_implicit.py:141-149)

@@ -12,10 +12,17 @@ cases.  The rank-weight tables are computed on the host with the reference's Num
 (``ranking/_weighting.py:79-122``) and uploaded, so the kernels contain no ``log`` / ``exp`` and
 any :class:`RankWeight` subclass works.
 
+The exposure, diversity and popularity metrics (csrc/diversity.hip) need no test data:
+``lk_item_exposure`` keeps the per-item totals of :class:`ListGini` / :class:`ExposureGini` on the
+device across the collector's ``add_*`` calls, ``lk_list_category_stats`` yields the category
+column-sum statistics of :class:`ILS` / :class:`Entropy` / :class:`RankBiasedEntropy` and
+``lk_list_gather_mean`` the sums of :class:`MeanPopRank`.  The comparisons of two rankings
+(rank-biased overlap, least item promoted) are in :mod:`lkpy_amd.reranking_metrics`.
+
 There is no host-only implementation: ``measure_list`` on one pair of lists is the same path with
 a batch of one.  Only :class:`FunctionMetric` (plain callables) runs list by list on the host.
 
-Out of scope: Gini / entropy / popularity / ILS / RBO / LIP, ``weight_field=`` of RBP.
+Out of scope: ``weight_field=`` of RBP.
 """
 
 from __future__ import annotations
@@ -29,7 +36,7 @@ from typing import Any, NamedTuple
 import numpy as np
 import pandas as pd
 
-from .data import ItemList, ItemListCollection, Vocabulary, _LazyLists, _RaggedLists
+from .data import Dataset, ItemList, ItemListCollection, Vocabulary, _LazyLists, _RaggedLists
 from .knn import DataWarning
 
 _log = logging.getLogger(__name__)
@@ -317,6 +324,317 @@ class RBP(ListMetric, RankingMetricBase):
             return _nan_where(s.n_test == 0, s.w_hits(self.n, self.weight) / norm)
 
 
+# ---------------------------------------------------------------------------------------
+# exposure, diversity and popularity (csrc/diversity.hip): metrics of the lists alone.  A metric
+# launches its kernel over the batch's device lists numbered by ITS vocabulary (``_launch``) and
+# composes the values from what the kernel left once everything is queued (``_finish``).
+# ---------------------------------------------------------------------------------------
+
+
+_SHARED: dict = {}  # (id(host object), tag) -> (weak reference to it, what was derived from it)
+
+
+def _derived(source, tag, build):
+    """
+    What ``build()`` makes of the host object ``source`` (a normalised matrix, a device copy), made
+    once per (object, tag) and kept while the object lives -- the rule of the components' device
+    cache (the same object: the same state), held here per host object so that metric objects
+    built from one matrix share one normalised form and one upload.  Nothing of it is pickled.
+    """
+    key = (id(source), tag)
+    hit = _SHARED.get(key)
+    if hit is None or hit[0]() is not source:
+        _SHARED.pop(key, None)  # (a stale entry's device memory goes before the build)
+        hit = _SHARED[key] = (weakref.ref(source, lambda _r, key=key: _SHARED.pop(key, None)),
+                              build())
+    return hit[1]
+
+
+class _ListsMetric(RankingMetricBase):
+    _kind = "lists"
+
+    def measure_list(self, output: ItemList, test: ItemList | None = None, /):
+        return _scalar(_measure_pairs([self], [output], [None])[0][0][0])
+
+    @property
+    def _cutoff(self) -> int:
+        return 0 if self.n is None else int(self.n)
+
+
+class GiniBase(_ListsMetric):
+    """
+    ``ranking/_gini.py:24-51``: no value per list; the per-item totals of a whole run
+    (``GiniAccumulator``) stay on the device with the collector, and the summary is the Gini
+    coefficient of their distribution.  Items the vocabulary does not know are skipped.
+    """
+
+    default = None
+    weight: RankWeight | None = None
+
+    def __init__(self, n: int | None = None, *, k: int | None = None,
+                 items: "Vocabulary | Dataset"):
+        super().__init__(n, k=k)
+        self.item_vocab = items.items if isinstance(items, Dataset) else items
+
+    def _numbers(self, output: ItemList) -> np.ndarray:
+        recs = output if self.n is None else output[:self.n]
+        return recs.numbers(vocabulary=self.item_vocab)
+
+    def _launch(self, p: "_ListPass"):
+        from . import _device as D
+
+        totals = p.state.get(id(self))
+        if totals is None:
+            totals = p.state[id(self)] = p.zeros(len(self.item_vocab))
+        lists = p.lists(self.item_vocab)
+        if self.n != 0 and lists.shape[1] and len(self.item_vocab):
+            D.item_exposure(lists, totals, self._cutoff,
+                            None if self.weight is None else p.table(self.weight))
+        return None
+
+    def _finish(self, pending, B):
+        return None
+
+    def _summarize_state(self, totals) -> float:
+        "``GiniAccumulator.accumulate`` (``_gini.py:131-133``)"
+        from .stats import gini
+
+        totals = np.zeros(len(self.item_vocab)) if totals is None else totals.cpu().numpy()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            dist = totals / totals.sum()
+        return gini(dist)
+
+
+class ListGini(GiniBase):
+    "``_gini.py:54-75``: the Gini coefficient of the number of lists each item appears in."
+
+    def measure_list(self, output: ItemList, test=None, /):
+        return (self._numbers(output), 1.0)
+
+
+class ExposureGini(GiniBase):
+    "``_gini.py:78-116``: the Gini coefficient of the items' total rank-weighted exposure."
+
+    def __init__(self, n: int | None = None, *, k: int | None = None,
+                 items: "Vocabulary | Dataset", weight: RankWeight = GeometricRankWeight()):
+        super().__init__(n=n, k=k, items=items)
+        self.weight = weight
+
+    def measure_list(self, output: ItemList, test=None, /):
+        ids = self._numbers(output)
+        return (ids, self.weight.weight(np.arange(1, len(ids) + 1, dtype=np.int32)))
+
+
+def normalize_rows(matrix, normalize: str | None):
+    """
+    ``normalize_matrix`` (data/matrix.py:643-678) on a dense array or any SciPy sparse matrix:
+    ``"unit"`` divides every row by its L2 norm, ``"distribution"`` by its sum (a row of zeros
+    stays).  Returns a float64 dense array or ``csr_array``.
+    """
+    import scipy.sparse as sps
+
+    sparse = sps.issparse(matrix)
+    matrix = sps.csr_array(matrix, dtype=np.float64) if sparse else \
+        np.asarray(matrix, dtype=np.float64)
+    if matrix.ndim != 2:
+        raise ValueError("the category matrix must be two-dimensional")
+    if normalize is None:
+        return matrix
+    if normalize == "unit":
+        stats = sps.linalg.norm(matrix, axis=1) if sparse else np.linalg.norm(matrix, axis=1)
+    elif normalize == "distribution":
+        data = matrix.data if sparse else matrix
+        if data.size and data.min() < 0:
+            raise ValueError("Cannot normalize to distribution: negative values present")
+        stats = np.asarray(matrix.sum(axis=1), dtype=np.float64)
+    else:
+        raise ValueError(f"invalid normalization {normalize}")
+    stats = np.array(stats, dtype=np.float64).reshape(-1)
+    stats[stats == 0] = 1.0
+    if sparse:
+        return sps.csr_array(matrix / stats[:, None])
+    return matrix / stats[:, None]
+
+
+class _CategoryMetric(ListMetric, _ListsMetric):
+    """
+    The metrics of an item x category matrix.  ``(dataset, attribute, n)`` as the reference
+    (the matrix is ``dataset.item_attrs[attribute]``, its rows the dataset's items), or
+    ``categories=`` (a dense array or any SciPy sparse matrix) with ``items=`` (the vocabulary of
+    its rows).  The rows are normalised here as ``cat_matrix(normalize=...)`` does; metrics
+    built from the same matrix object share the normalised matrix and its one copy in HBM.
+    """
+
+    _normalize: str | None = None
+    _name = ""
+    weight: RankWeight | None = None
+
+    def __init__(self, dataset: Dataset | None = None, attribute: str | None = None,
+                 n: int | None = None, *, categories=None, items: Vocabulary | None = None):
+        super().__init__(n)
+        from . import _device as D
+
+        if dataset is not None:
+            if categories is not None or items is not None:
+                raise TypeError("give a dataset and attribute, or categories= and items=")
+            if attribute is None:
+                raise TypeError("a dataset needs the attribute's name")
+            attrs = getattr(dataset, "item_attrs", {})
+            if attribute not in attrs:
+                raise KeyError(f"items have no attribute {attribute}")
+            categories, items = attrs[attribute], dataset.items
+        elif categories is None or items is None:
+            raise TypeError("give a dataset and attribute, or categories= and items=")
+        self.attribute = "categories" if attribute is None else attribute
+        if not hasattr(categories, "tocsr"):
+            categories = np.asarray(categories)  # (an array is itself: one matrix, one upload)
+        mat = _derived(categories, ("rows", self._normalize),
+                       lambda: normalize_rows(categories, self._normalize))
+        if mat.shape[0] != len(items):
+            raise ValueError(f"{mat.shape[0]} matrix rows for {len(items)} items")
+        if mat.shape[1] > D.CATEGORY_MAX:
+            raise ValueError(f"{mat.shape[1]} category columns: the device keeps a list's column "
+                             f"sums in LDS and supports at most {D.CATEGORY_MAX}")
+        self._cat_matrix = mat
+        self._item_vocab = items
+
+    @property
+    def label(self):
+        base = f"{self._name}({self.attribute})"
+        return f"{base}@{self.n}" if self.n is not None else base
+
+    def _device_matrix(self, dev):
+        """the matrix as a CSR in HBM (a dense one keeps every column), uploaded once per
+        normalised matrix -- which the metrics built from one source matrix share"""
+        def upload():
+            import scipy.sparse as sps
+
+            from . import _device as D
+
+            m = self._cat_matrix
+            if sps.issparse(m):
+                return D.DeviceCategories.from_scipy(m, dev)
+            R, C = m.shape
+            return D.DeviceCategories(_to_dev(np.arange(R + 1, dtype=np.int64) * C, dev),
+                                      _to_dev(np.tile(np.arange(C, dtype=np.int32), R), dev),
+                                      _to_dev(m.reshape(-1), dev), (R, C))
+
+        return _derived(self._cat_matrix, ("device", str(dev)), upload)
+
+    def _launch(self, p: "_ListPass"):
+        from . import _device as D
+
+        lists = p.lists(self._item_vocab)
+        if self.n == 0 or self._cat_matrix.shape[1] == 0:
+            return None
+        return D.list_category_stats(lists, self._device_matrix(p.dev), self._cutoff,
+                                     None if self.weight is None else p.table(self.weight))
+
+    def _finish(self, pending, B):
+        if pending is None:
+            return np.full(B, np.nan)
+        known, stats = pending
+        return self._value(known.cpu().numpy().astype(np.int64), stats.cpu().numpy())
+
+
+def _to_dev(arr, dev):
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(arr)).to(dev)
+
+
+class ILS(_CategoryMetric):
+    """
+    ``ranking/_ils.py:18-104``: the mean pairwise cosine similarity of the known items' unit
+    vectors, from the identity ``sum_{i<j} v_i . v_j = (|sum_i v_i|^2 - sum_i |v_i|^2) / 2``.
+    NaN without a known item, 1.0 with one.
+    """
+
+    _normalize = "unit"
+    _name = "ILS"
+
+    def _value(self, k, stats):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            val = ((stats[0] - stats[1]) / 2) / (k * (k - 1) / 2)
+        val[k == 1] = 1.0
+        return _nan_where(k == 0, val)
+
+
+class Entropy(_CategoryMetric):
+    "``ranking/_entropy.py:91-145``: Shannon entropy of the known items' category distribution."
+
+    _normalize = "distribution"
+    _name = "Entropy"
+
+    def _value(self, k, stats):
+        return _nan_where(k == 0, stats[2])
+
+
+class RankBiasedEntropy(Entropy):
+    """
+    ``ranking/_entropy.py:148-206``.  One deviation: with an item the vocabulary does not know in
+    the list, the reference multiplies the known items' rows by the weights of ALL ranks and
+    fails on the shape mismatch; here every known item keeps the weight of its own rank.
+    """
+
+    _name = "RBEntropy"
+
+    def __init__(self, dataset: Dataset | None = None, attribute: str | None = None,
+                 n: int | None = None, *, weight: RankWeight | None = None, categories=None,
+                 items: Vocabulary | None = None):
+        super().__init__(dataset, attribute, n, categories=categories, items=items)
+        self.weight = weight if weight is not None else GeometricRankWeight(0.85)
+
+
+def popularity_quantiles(data: Dataset, count: str = "users") -> np.ndarray:
+    """
+    ``MeanPopRank.__init__`` (``ranking/_pop.py:59-73``): per item number the average rank of its
+    count among the positive counts, divided by their number; 0 for an item without any.
+    """
+    if count == "users":  # distinct users: a repeated (user, item) pair counts once
+        pairs = np.unique(data._rows.astype(np.int64) * max(data.item_count, 1) + data._cols)
+        counts = np.bincount(pairs % max(data.item_count, 1), minlength=data.item_count)
+    elif count == "interactions":
+        w = data._attrs.get("count")
+        counts = np.bincount(data._cols, weights=w, minlength=data.item_count)
+    else:
+        raise ValueError(f"invalid count {count}")
+    table = np.zeros(data.item_count, dtype=np.float64)
+    pos = np.flatnonzero(counts > 0)
+    if len(pos):
+        ranks = pd.Series(counts[pos]).rank(method="average", ascending=True)
+        ranks /= len(pos)
+        table[pos] = ranks.to_numpy()
+    return table
+
+
+class MeanPopRank(ListMetric, _ListsMetric):
+    "``ranking/_pop.py:19-84``: the mean popularity quantile of the recommended items."
+
+    def __init__(self, data: Dataset, *, n: int | None = None, k: int | None = None,
+                 count: str = "users"):
+        super().__init__(n, k=k)
+        self._item_vocab = data.items
+        self.item_ranks = popularity_quantiles(data, count)
+
+    def _launch(self, p: "_ListPass"):
+        from . import _device as D
+
+        table = _derived(self.item_ranks, ("device", str(p.dev)),
+                         lambda: _to_dev(self.item_ranks, p.dev))
+        lists = p.lists(self._item_vocab)
+        if self.n == 0:
+            return None
+        return D.list_gather_mean(lists, table, self._cutoff)
+
+    def _finish(self, pending, B):
+        if pending is None:
+            return np.full(B, np.nan)
+        sums, lens = (t.cpu().numpy() for t in pending)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return _nan_where(lens == 0, sums / lens)
+
+
 class PredictMetric(Metric):
     """``predict.py:37-111``: the two ``missing_*`` dispositions.  A prediction list holds every
     item once (the kernel matches a repeated item to its truth entry once per occurrence)."""
@@ -577,24 +895,35 @@ class TruthState:
         Row of the test list of every output key, -1 without one: the output keys projected onto
         the test collection's key fields (``lookup_projected``); of equal test keys the last wins.
         """
-        missing = [f for f in self.key_fields if f not in out_keys]
-        if missing:
-            raise KeyError(f"output keys lack the test key fields {missing}")
         if self._index is None:
-            cols = [self.keys[f] for f in self.key_fields]
-            idx = pd.Index(cols[0]) if len(cols) == 1 else pd.MultiIndex.from_arrays(cols)
-            pos = np.arange(len(idx))
-            if not idx.is_unique:
-                keep = ~idx.duplicated(keep="last")
-                idx, pos = idx[keep], pos[keep]
-            self._index = (idx, pos)
-        idx, pos = self._index
-        cols = [np.asarray(out_keys[f]) for f in self.key_fields]
-        probe = cols[0] if len(cols) == 1 else pd.MultiIndex.from_arrays(cols)
-        if len(idx) == 0:
-            return np.full(n, -1, np.int32)
-        loc = idx.get_indexer(probe)
-        return np.where(loc >= 0, pos[np.maximum(loc, 0)], -1).astype(np.int32)
+            self._index = key_index(self.key_fields, self.keys)
+        return project_rows(self._index, self.key_fields, out_keys, n, "test")
+
+
+def key_index(key_fields, keys: dict[str, np.ndarray]):
+    "(index over a collection's keys, position of each index entry); of equal keys the last wins"
+    cols = [keys[f] for f in key_fields]
+    idx = pd.Index(cols[0]) if len(cols) == 1 else pd.MultiIndex.from_arrays(cols)
+    pos = np.arange(len(idx))
+    if not idx.is_unique:
+        keep = ~idx.duplicated(keep="last")
+        idx, pos = idx[keep], pos[keep]
+    return idx, pos
+
+
+def project_rows(index, key_fields, out_keys: dict[str, np.ndarray], n: int,
+                 what: str = "test") -> np.ndarray:
+    "row in the indexed collection of every output key projected onto its key fields, -1 = none"
+    missing = [f for f in key_fields if f not in out_keys]
+    if missing:
+        raise KeyError(f"output keys lack the {what} key fields {missing}")
+    idx, pos = index
+    cols = [np.asarray(out_keys[f]) for f in key_fields]
+    probe = cols[0] if len(cols) == 1 else pd.MultiIndex.from_arrays(cols)
+    if len(idx) == 0:
+        return np.full(n, -1, np.int32)
+    loc = idx.get_indexer(probe)
+    return np.where(loc >= 0, pos[np.maximum(loc, 0)], -1).astype(np.int32)
 
 
 _TRUTH: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
@@ -837,12 +1166,71 @@ def _predict_pass(packed: _Packed, truth: TruthState | None, rows, dev, timing=N
             "n_missing_truth": counts[2]}
 
 
+class _ListPass:
+    """
+    The lists of one batch on the device, numbered by the vocabulary a metric asks for, with the
+    rank-weight tables: a dense panel is uploaded once and shared by every metric (renumbered on
+    the device for a metric whose vocabulary is another one); ragged lists are numbered on the
+    host once per vocabulary.
+    """
+
+    def __init__(self, packed: _Packed, dev, state: dict):
+        self.packed, self.dev, self.state = packed, dev, state
+        self._lists: list = []  # (vocabulary, device int32 [B x L])
+        self._tables: dict = {}
+
+    def zeros(self, n: int):
+        import torch
+
+        return torch.zeros(n, dtype=torch.float64, device=self.dev)
+
+    def _upload(self, nums):
+        import torch
+
+        if isinstance(nums, np.ndarray):
+            nums = torch.from_numpy(np.ascontiguousarray(nums, dtype=np.int32)).to(self.dev)
+        return nums.contiguous()
+
+    def lists(self, vocab: Vocabulary):
+        import torch
+
+        for v, t in self._lists:
+            if v is vocab or v == vocab:
+                return t
+        if self.packed.dense is not None:
+            if not self._lists:
+                nums, own = self.packed.dense
+                self._lists.append((own, self._upload(nums)))
+                return self.lists(vocab)
+            own, panel = self._lists[0]
+            to = vocab.numbers(own.ids(), missing="negative") if len(own) else \
+                np.zeros(0, np.int32)
+            to = self._upload(np.append(np.where(to < 0, UNKNOWN_ITEM, to), UNKNOWN_ITEM))
+            at = torch.clamp(panel, min=0, max=len(own)).to(torch.int64)
+            t = torch.where(panel >= 0, to[at], panel).contiguous()
+        else:
+            t = self._upload(dense_lists(self.packed, vocab)[0])
+        self._lists.append((vocab, t))
+        return t
+
+    def table(self, weight: RankWeight):
+        "``weight``'s table over the ranks of the batch's lists (device float64 [L])"
+        L = max(int(self._lists[0][1].shape[1]), 1)
+        hit = self._tables.get(weight._table_key())
+        if hit is None:
+            w = np.ascontiguousarray(weight.weight(np.arange(1, L + 1)), dtype=np.float64)
+            hit = self._tables[weight._table_key()] = _to_dev(w, self.dev)
+        return hit
+
+
 def measure_arrays(metrics, packed: _Packed, test: ItemListCollection | None, *, outputs=None,
-                   timing: dict | None = None):
+                   timing: dict | None = None, state: dict | None = None):
     """
     Every metric of ``metrics`` for every list of ``packed`` in one batched pass.  Returns
-    (values: one float64 [B] array per metric, extras: per metric None or the prediction metrics'
-    {"sum", "n"} arrays, number of lists without test data).
+    (values: one float64 [B] array per metric -- None for a metric without per-list values --,
+    extras: per metric None or the prediction metrics' {"sum", "n"} arrays, number of lists
+    without test data).  ``state``: the collector's device state of the metrics that accumulate
+    over a run (the Gini totals), by ``id(metric)``.
     """
     import time
 
@@ -853,6 +1241,8 @@ def measure_arrays(metrics, packed: _Packed, test: ItemListCollection | None, *,
     rank_ms = [m for m in metrics if m._kind == "rank"]
     pred_ms = [m for m in metrics if m._kind == "predict"]
     func_ms = [m for m in metrics if m._kind == "function"]
+    list_ms = [m for m in metrics if m._kind == "lists"]
+    dlists = _ListPass(packed, dev, {} if state is None else state)
     t0 = time.perf_counter()
     truth = rows = None
     n_test = np.zeros(B, np.int64)
@@ -867,15 +1257,10 @@ def measure_arrays(metrics, packed: _Packed, test: ItemListCollection | None, *,
     values: dict[int, Any] = {}
     extras: dict[int, Any] = {}
     if rank_ms:
-        import torch
-
         if test is None:
             raise TypeError("ranking metrics need test data")
-        lists, _v = dense_lists(packed, truth.vocab)
-        if isinstance(lists, np.ndarray):
-            lists = torch.from_numpy(np.ascontiguousarray(lists, dtype=np.int32)).to(dev)
-        stats = _rank_pass(rank_ms, lists.contiguous(), truth if truth.size else None, rows,
-                           n_test, dev, timing)
+        stats = _rank_pass(rank_ms, dlists.lists(truth.vocab), truth if truth.size else None,
+                           rows, n_test, dev, timing)
         t1 = time.perf_counter()
         for m in rank_ms:
             values[id(m)] = np.asarray(m._compose(stats), dtype=np.float64)
@@ -884,6 +1269,16 @@ def measure_arrays(metrics, packed: _Packed, test: ItemListCollection | None, *,
             warnings.warn(f"test item list is empty for {empty} lists", DataWarning, stacklevel=3)
         if timing is not None:
             timing["compose_s"] = timing.get("compose_s", 0.0) + (time.perf_counter() - t1)
+    if list_ms:
+        t1 = time.perf_counter()
+        pending = [m._launch(dlists) for m in list_ms]
+        _sync(timing)
+        t2 = time.perf_counter()
+        for m, pend in zip(list_ms, pending):
+            values[id(m)] = m._finish(pend, B)
+        if timing is not None:
+            timing["kernel_s"] = timing.get("kernel_s", 0.0) + (t2 - t1)
+            timing["download_s"] = timing.get("download_s", 0.0) + (time.perf_counter() - t2)
     if pred_ms:
         p = _predict_pass(packed, truth if test is not None else None, rows, dev, timing)
         for m in pred_ms:
@@ -902,7 +1297,7 @@ def measure_arrays(metrics, packed: _Packed, test: ItemListCollection | None, *,
     return [values[id(m)] for m in metrics], [extras.get(id(m)) for m in metrics], no_test
 
 
-def _measure_pairs(metrics, outputs: list, tests: list):
+def _measure_pairs(metrics, outputs: list, tests: list, state: dict | None = None):
     "``measure_list``: the batched pass over a batch built from the given pairs"
     out = ItemListCollection(("list",))
     for i, il in enumerate(outputs):
@@ -914,7 +1309,8 @@ def _measure_pairs(metrics, outputs: list, tests: list):
             test.add(il if il is not None else ItemList([]), i)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore", DataWarning)
-        vals, extras, _ = measure_arrays(metrics, pack_collection(out), test, outputs=out)
+        vals, extras, _ = measure_arrays(metrics, pack_collection(out), test, outputs=out,
+                                         state=state)
     return vals, extras
 
 
@@ -962,6 +1358,7 @@ class MeasurementCollector:
     def __init__(self):
         self._metrics: list[tuple[str, Metric]] = []
         self._chunks: list[tuple[dict, list, list]] = []  # key columns, values, extras
+        self._state: dict = {}  # id(metric) -> device state kept over the add_* calls (Gini totals)
         self.key_fields: list[str] = []
 
     def empty_copy(self):
@@ -972,6 +1369,7 @@ class MeasurementCollector:
     def reset(self):
         self.key_fields = []
         self._chunks = []
+        self._state = {}
 
     @property
     def metric_names(self) -> list[str]:
@@ -998,12 +1396,13 @@ class MeasurementCollector:
 
     def add_list_measurement(self, output: ItemList, test: ItemList, **keys: Any):
         ms = [m for _l, m in self._metrics]
-        vals, extras = _measure_pairs(ms, [output], [test])
+        vals, extras = _measure_pairs(ms, [output], [test], self._state)
         self._record({k: np.asarray([v]) for k, v in keys.items()}, vals, extras)
 
     def _add_packed(self, packed: _Packed, test, keys: dict, outputs=None, timing=None):
         ms = [m for _l, m in self._metrics]
-        vals, extras, no_test = measure_arrays(ms, packed, test, outputs=outputs, timing=timing)
+        vals, extras, no_test = measure_arrays(ms, packed, test, outputs=outputs, timing=timing,
+                                               state=self._state)
         cols = {k: np.full(len(packed), v) for k, v in keys.items()}
         cols.update(packed.key_columns())
         self._record(cols, vals, extras)
@@ -1041,8 +1440,9 @@ class MeasurementCollector:
         cols = {}
         for f in self.key_fields:
             cols[f] = np.concatenate([k[f] for k, _v, _e in self._chunks])
-        for j, (label, _m) in enumerate(self._metrics):
-            cols[label] = self._column(j)
+        for j, (label, m) in enumerate(self._metrics):
+            if not hasattr(m, "_summarize_state"):  # (a metric without per-list values)
+                cols[label] = self._column(j)
         df = pd.DataFrame(cols)
         if self.key_fields:
             df.set_index(self.key_fields, inplace=True, drop=True)
@@ -1051,6 +1451,9 @@ class MeasurementCollector:
     def summary_metrics(self) -> dict:
         results: dict = {}
         for j, (label, m) in enumerate(self._metrics):
+            if hasattr(m, "_summarize_state"):
+                _add_values(results, label, m._summarize_state(self._state.get(id(m))))
+                continue
             ex = [e[j] for _k, _v, e in self._chunks if e[j] is not None]
             extra = {k: np.concatenate([e[k] for e in ex]) for k in ex[0]} if ex else \
                 {"sum": np.zeros(0), "n": np.zeros(0, np.int64)}

@@ -148,6 +148,7 @@ def _make_split(data: Dataset, test_us, method: HoldoutMethod, *, test_only=Fals
         keep = ~np.isin(pair, pair[pos])
     train = Dataset(data.users, data.items, data._rows[keep], data._cols[keep],
                     {k: v[keep] for k, v in data._attrs.items()})
+    train.item_attrs = dict(data.item_attrs)  # (the items, and what is known of them, stay)
     return TTSplit(train, test)
 
 
