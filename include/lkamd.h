@@ -641,6 +641,38 @@ int lk_slim_score_batch(const int64_t *d_hist_ptr, const int32_t *d_hist_items, 
 int lk_take_scores(const float *d_scores, int64_t n_rows, int64_t row_len, const int32_t *d_idx,
                    int64_t n, float *d_out, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Association rules (`AssociationScorer`, src/lenskit/knn/association.py:59-163; csrc/assoc.hip).
+ * The co-occurrence counts are the similarity build on unit values (lk_iknn_build_*, threshold
+ * 0.5: `interact.co_occurrences("item")`, association.py:103).
+ * lk_assoc_scale: the in-place scaling of association.py:110-124 on that CSR (int64 offsets):
+ *   v = float32(double(count) / (double(item_counts[row]) + damping)); for LK_ASSOC_LIFT then
+ *   v = v * float32(n_groups) in float32 and v = float32(double(v) / (double(item_counts[col]) +
+ *   damping)) -- NumPy's `/=` by an int32 + float array and `*=` by a Python int, bit for bit.
+ * lk_assoc_score_batch: `assoc_scores[ref_items, :].todense()` reduced over the rows
+ *   (association.py:149-153) for a batch of queries, into a dense panel: for a query with m known
+ *   reference items (items outside [0, n_items) are skipped, repeats count, order kept)
+ *   LK_ASSOC_MEAN gives float32(double(s) / double(m)) with s the sequential float32 sum of the m
+ *   cells in reference-item order (`np.mean(..., axis=0)`), LK_ASSOC_MAX their maximum; absent
+ *   cells are 0.  No atomics: a query has the same bits alone or in any batch.  mark_history as
+ *   lk_slim_score_batch: bit 0 turns the query's own items into NaN, bit 1 the whole row of a
+ *   query without a known reference item (0 otherwise).  The panel is ready for lk_argtopn.
+ * lk_assoc_window: the most item columns one workgroup accumulates (a test hook: item counts
+ *   around its multiples take one more window).
+ * ---------------------------------------------------------------------- */
+#define LK_ASSOC_PROBABILITY 0
+#define LK_ASSOC_LIFT 1
+#define LK_ASSOC_MEAN 0
+#define LK_ASSOC_MAX 1
+int32_t lk_assoc_window(void);
+int lk_assoc_scale(const int64_t *d_indptr, const int32_t *d_indices, float *d_values,
+                   const int32_t *d_item_counts, int64_t n_items, int64_t n_groups, int method,
+                   double damping, void *stream);
+int lk_assoc_score_batch(const int64_t *d_ref_ptr, const int32_t *d_ref_items, int64_t n_queries,
+                         const int64_t *d_s_indptr, const int32_t *d_s_indices,
+                         const float *d_s_values, int64_t n_items, int reduce, float *d_out,
+                         int64_t ld_out, int mark_history, void *stream);
+
 /* Batched fold-in (new-user embeddings) -- `ImplicitMFScorer.new_user_embedding` /
  * `_train_new_row` (src/lenskit/als/_implicit.py:77-130) -- is the SAME algebra as one ALS
  * row with OtOr = Q^T Q + user_reg I: build a plan over the histories' CSR offsets and call

@@ -1138,6 +1138,73 @@ def slim_score_batch(hist_ptr: torch.Tensor, hist_items: torch.Tensor, weights: 
     return out
 
 
+def assoc_window() -> int:
+    "The most item columns one workgroup of ``lk_assoc_score_batch`` accumulates (lk_assoc_window)."
+    return int(_native.load().lk_assoc_window())
+
+
+def assoc_scale(cooc: DeviceCSR, item_counts: torch.Tensor, n_groups: int, method: str,
+                damping: float) -> DeviceCSR:
+    """
+    Co-occurrence counts -> association scores, IN PLACE (lk_assoc_scale;
+    src/lenskit/knn/association.py:110-124): ``cooc`` is the square CSR ``iknn_build`` returns for
+    the binary matrix (int64 offsets, threshold 0.5), ``item_counts`` the items' int32 interaction
+    counts on the device, ``n_groups`` the interaction matrix's row count.  ``method``:
+    ``"probability"`` or ``"lift"``.  Returns ``cooc``.
+    """
+    lib = _native.require_gpu()
+    n = int(cooc.shape[0])
+    if method not in _native.ASSOC_METHODS:
+        raise ValueError(f"assoc_scale: unknown method {method!r}")
+    assert cooc.shape[1] == n and cooc.indptr.dtype == torch.int64
+    assert cooc.values is not None and cooc.values.dtype == torch.float32
+    assert item_counts.dtype == torch.int32 and item_counts.numel() == n
+    check(
+        lib.lk_assoc_scale(_ptr(cooc.indptr), _ptr(cooc.indices), _ptr(cooc.values),
+                           _ptr(item_counts), n, int(n_groups), _native.ASSOC_METHODS[method],
+                           float(damping), _stream()),
+        "lk_assoc_scale",
+    )
+    return cooc
+
+
+def assoc_score_batch(ref_ptr: torch.Tensor, ref_items: torch.Tensor, s: DeviceCSR,
+                      reduce: str, rows: tuple[int, int] | None = None,
+                      strike_history: bool = False, nan_empty: bool = True,
+                      out: torch.Tensor | None = None) -> torch.Tensor:
+    """
+    The mean or the maximum of the reference items' rows of the association matrix ``s`` per query
+    (lk_assoc_score_batch; src/lenskit/knn/association.py:149-153), a dense [B x n_items] f32
+    panel: reference items in the order given, repeats counted, -1 (unknown) skipped, absent cells
+    0.  ``reduce``: ``"mean"`` or ``"max"``.  ``rows = (lo, hi)``: those queries only.  The panel
+    as ``argtopn`` wants it: ``strike_history`` makes the query's own items NaN, ``nan_empty`` the
+    whole row of a query without a known reference item (else it is 0).  ``out``: write into
+    the first ``n_items`` columns of this [hi - lo x ld] f32 device matrix (ld >= n_items) instead
+    of a fresh panel; the other columns are left alone.
+    """
+    lib = _native.require_gpu()
+    n = int(s.shape[1])
+    if reduce not in _native.ASSOC_REDUCTIONS:
+        raise ValueError(f"assoc_score_batch: unknown reduction {reduce!r}")
+    lo, hi = (0, int(ref_ptr.shape[0]) - 1) if rows is None else (int(rows[0]), int(rows[1]))
+    assert 0 <= lo <= hi < int(ref_ptr.shape[0])
+    assert ref_ptr.dtype == torch.int64 and ref_items.dtype == torch.int32
+    assert s.indptr.dtype == torch.int64 and s.shape[0] == n
+    if out is None:
+        out = torch.empty((hi - lo, n), dtype=torch.float32, device=s.indices.device)
+    assert out.dtype == torch.float32 and out.dim() == 2 and out.is_contiguous()
+    assert out.shape[0] == hi - lo and out.shape[1] >= n
+    check(
+        lib.lk_assoc_score_batch(_ptr(ref_ptr[lo:]), _ptr(ref_items), hi - lo, _ptr(s.indptr),
+                                 _ptr(s.indices), _ptr(s.values), n,
+                                 _native.ASSOC_REDUCTIONS[reduce], _ptr(out), int(out.shape[1]),
+                                 (1 if strike_history else 0) | (2 if nan_empty else 0),
+                                 _stream()),
+        "lk_assoc_score_batch",
+    )
+    return out
+
+
 def take_scores(scores: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     "The scores of the lists ``argtopn`` selected: [B x n] f32, NaN under -1 (lk_take_scores)."
     lib = _native.require_gpu()

@@ -40,6 +40,9 @@ FLEXMF_MAX_K = 256
 
 STOCHASTIC_TRANSFORMS = {None: 0, "softmax": 1, "linear": 2}
 
+ASSOC_METHODS = {"probability": 0, "lift": 1}  # LK_ASSOC_PROBABILITY / LK_ASSOC_LIFT
+ASSOC_REDUCTIONS = {"mean": 0, "max": 1}  # LK_ASSOC_MEAN / LK_ASSOC_MAX
+
 
 class FlexMFTables(ctypes.Structure):
     "``lk_flexmf_tables``: u_embed, i_embed, u_bias, i_bias and their two moment tables."
@@ -186,6 +189,13 @@ def _declare(lib):
             c_int, [vp, vp, c_int64, vp, vp, vp, c_int64, vp, c_int64, c_int, vp]
         ),
         "lk_take_scores": (c_int, [vp, c_int64, c_int64, vp, c_int64, vp, vp]),
+        "lk_assoc_window": (c_int32, []),
+        "lk_assoc_scale": (
+            c_int, [vp, vp, vp, vp, c_int64, c_int64, c_int, ctypes.c_double, vp]
+        ),
+        "lk_assoc_score_batch": (
+            c_int, [vp, vp, c_int64, vp, vp, vp, c_int64, c_int, vp, c_int64, c_int, vp]
+        ),
         "lk_score_topk_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
         "lk_score_topk": (
             c_int,

@@ -694,6 +694,28 @@ class Dataset:
     def user_row(self, user_id) -> ItemList | None:
         return _Matrix(self).row_items(user_id)
 
+    def item_stats(self):
+        """
+        ``Dataset.item_stats`` (src/lenskit/data/_dataset.py:490-504, ``_compute_stats``
+        _relationships.py:877-920), the counting columns: a frame indexed by item id, aligned with
+        the vocabulary, with ``record_count`` (interaction records of the item), ``user_count``
+        (distinct users) and ``count`` (the sum of the ``count`` attribute where the interactions
+        have one, else ``record_count``), int32; an item without interactions has zeros.
+        """
+        import pandas as pd
+
+        n = self.item_count
+        records = np.bincount(self._cols, minlength=n).astype(np.int32)
+        first = np.ones(len(self._rows), dtype=bool)  # (sorted by user, then item)
+        first[1:] = (self._rows[1:] != self._rows[:-1]) | (self._cols[1:] != self._cols[:-1])
+        users = np.bincount(self._cols[first], minlength=n).astype(np.int32)
+        count = records
+        if "count" in self._attrs:
+            count = np.rint(np.bincount(self._cols, weights=self._attrs["count"],
+                                        minlength=n)).astype(np.int32)
+        return pd.DataFrame({"record_count": records, "user_count": users, "count": count},
+                            index=pd.Index(self.items.ids(), name="item_id"))
+
     @classmethod
     def from_arrays(cls, user_ids, item_ids, ratings=None, *, all_item_ids=None, **attrs):
         user_ids, item_ids = np.asarray(user_ids), np.asarray(item_ids)

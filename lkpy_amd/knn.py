@@ -1,8 +1,9 @@
 """
 Component seam for neighbourhood models -- item-based k-NN and user-based
 k-NN (mirror of ``lenskit.knn.UserKNNScorer``, src/lenskit/knn/user.py:25-316), EASE (mirror of
-``lenskit.knn.EASEScorer``, src/lenskit/knn/ease.py) and SLIM / fsSLIM (end of the file, mirror of
-``lenskit.knn.SLIMScorer``, src/lenskit/knn/slim.py).
+``lenskit.knn.EASEScorer``, src/lenskit/knn/ease.py), SLIM / fsSLIM (mirror of
+``lenskit.knn.SLIMScorer``, src/lenskit/knn/slim.py) and association rules (end of the file, mirror
+of ``lenskit.knn.AssociationScorer``, src/lenskit/knn/association.py).
 
 Item-based k-NN: mirror of ``lenskit.knn.ItemKNNScorer`` /
 ``ItemKNNConfig`` (src/lenskit/knn/item.py:41-295).  Matrix preparation is the reference's
@@ -18,7 +19,8 @@ from typing import Literal
 import numpy as np
 import scipy.sparse as sps
 import torch
-from pydantic import AliasChoices, BaseModel, Field, PositiveFloat, PositiveInt, field_validator
+from pydantic import (AliasChoices, BaseModel, Field, NonNegativeFloat, PositiveFloat, PositiveInt,
+                      field_validator)
 
 from . import _device as D
 from ._queries import item_scores, pack_histories, resolve_queries
@@ -655,3 +657,186 @@ class SLIMScorer(Component):
             oi[lo:hi, :idx.shape[1]] = idx
             osc[lo:hi, :idx.shape[1]] = D.take_scores(panel, idx)
         return D.lists_to_host(oi, osc)
+
+
+# ---------------------------------------------------------------------------------------
+# Association rules: conditional probability, lift, biased lift
+# ---------------------------------------------------------------------------------------
+
+
+class AssociationConfig(BaseModel, extra="forbid"):
+    "``AssociationConfig`` (src/lenskit/knn/association.py:32-56)."
+
+    method: Literal["probability", "lift"] = "probability"
+    "The formula for the item association level."
+    damping: NonNegativeFloat = 0.0
+    "Damping factor (kappa) of biased lift."
+    max_nbrs: PositiveInt | None = None
+    "``None``: the mean over the reference items; 1: the maximum.  Other values are not offered."
+
+
+class AssociationScorer(Component):
+    """
+    Association rules between items (``AssociationScorer``, src/lenskit/knn/association.py:59-163):
+    conditional probability ``P[c|r]``, lift, and -- with ``damping`` -- biased lift, from the
+    co-occurrence counts of the training matrix.  Training counts co-occurrences with the
+    similarity-build kernel on unit values (as ``EASEScorer`` does), scales them in place
+    (``lk_assoc_scale``, NumPy's float64 divisions and float32 multiply bit for bit) and downloads
+    the matrix; scoring reduces the reference items' rows by mean or max for whole batches of
+    queries (``lk_assoc_score_batch``: a cell's additions in reference-item order, as ``np.mean``
+    over the reference's dense rows), and ``recommend_batch`` selects the lists from bounded panels
+    with ``lk_argtopn``.  The learned state stays on the host: ``items``, ``item_freqs`` and
+    ``assoc_scores`` (SciPy CSR, reference items on rows, target items on columns).
+    """
+
+    config: AssociationConfig
+
+    items: Vocabulary
+    item_freqs: np.ndarray
+    assoc_scores: sps.csr_array
+
+    PANEL_BYTES = 1 << 30  # score panel of one recommend / score step
+
+    def is_trained(self) -> bool:
+        return hasattr(self, "assoc_scores")
+
+    def train(self, data: Dataset, options: TrainingOptions = TrainingOptions()):
+        "association.py:91-130"
+        n_items = data.item_count
+        ui = data.interactions().matrix().scipy(attribute=None).astype(np.float32)
+        ui = sps.csr_array(ui)
+        n_groups = ui.shape[0]  # the matrix's rows, not user_count: there might be sessions (99)
+        ui.sum_duplicates()
+        ui.data[:] = 1.0  # co-occurrences count (user, item) pairs once
+        ui.sort_indices()
+        iu = sps.csr_array(ui.T)
+        iu.sort_indices()
+        d = D.device()
+        cooc = D.iknn_build(D.DeviceCSR.from_scipy(ui, d), D.DeviceCSR.from_scipy(iu, d), 0.5)
+        # the marginals count interaction RECORDS (item_stats, association.py:113)
+        item_counts = np.ascontiguousarray(data.item_stats()["count"].values, dtype=np.int32)
+        D.assoc_scale(cooc, torch.from_numpy(item_counts).to(d), n_groups, self.config.method,
+                      float(self.config.damping))
+        # handed back like ItemKNNScorer's sim_matrix: D.to_host moves it at PCIe speed
+        scores = sps.csr_array(
+            (D.to_host(cooc.values), D.to_host(cooc.indices, index_bound=n_items),
+             cooc.indptr.cpu().numpy()), shape=(n_items, n_items))
+        scores.has_sorted_indices = True  # (the build's rows ascend)
+        self.items = data.items
+        self.item_freqs = item_counts
+        self.assoc_scores = scores
+        # the scaled build output IS the device copy of the new matrix: not uploaded again
+        self._device_cache("assoc_scores", lambda: cooc, self.assoc_scores)
+
+    def _device_scores(self) -> D.DeviceCSR:
+        "The association matrix in HBM (int64 offsets), uploaded once per model."
+        def upload():
+            s = self.assoc_scores
+            s.sort_indices()
+            d = D.device()
+            return D.DeviceCSR(torch.from_numpy(np.array(s.indptr, dtype=np.int64)).to(d),
+                               torch.from_numpy(np.array(s.indices, dtype=np.int32)).to(d),
+                               torch.from_numpy(np.array(s.data, dtype=np.float32)).to(d),
+                               (int(s.shape[0]), int(s.shape[1])), None)
+
+        return self._device_cache("assoc_scores", upload, self.assoc_scores)
+
+    def _reduction(self) -> str:
+        if self.config.max_nbrs is None:
+            return "mean"
+        if self.config.max_nbrs == 1:
+            return "max"
+        raise NotImplementedError("limited reference items not yet implemented")  # 155
+
+    def _panel_rows(self) -> int:
+        return max(1, self.PANEL_BYTES // (4 * max(len(self.items), 1)))
+
+    def _query_csr(self, queries: list[RecQuery]) -> D.DeviceCSR:
+        "The reference items of a list of queries in query order, uploaded: -1 = unknown item."
+        ptr, idx, _ = pack_histories(queries, self.items, unknown="keep")
+        return D.DeviceCSR.from_arrays(ptr, idx, None, (len(queries), len(self.items)),
+                                       self._device_scores().indices.device)
+
+    def score_batch(self, queries, item_lists) -> list[ItemList]:
+        "Scores for a batch of (query, items) pairs (association.py:132-163 per pair)."
+        s = self._device_scores()
+        hist = self._query_csr([RecQuery.create(q) for q in queries])
+        if hist.nnz and bool((hist.indices >= 0).any()):
+            reduce = self._reduction()  # (the reference raises once it has reference items)
+        else:
+            reduce = "mean"
+        out = []
+        step = self._panel_rows()
+        for lo in range(0, len(item_lists), step):
+            hi = min(len(item_lists), lo + step)
+            # a query without a known reference item: every score NaN (association.py:144-146)
+            panel = D.to_host(D.assoc_score_batch(hist.indptr, hist.indices, s, reduce,
+                                                  rows=(lo, hi), nan_empty=True))
+            for i in range(lo, hi):
+                items = item_lists[i]
+                out.append(ItemList(items, scores=item_scores(items, self.items, panel[i - lo])))
+        return out
+
+    def __call__(self, query, items: ItemList) -> ItemList:
+        return self.score_batch([query], [items])[0]
+
+    # -- top-n --------------------------------------------------------------------------------
+    accepts_history_batch = True  # recommend_batch takes a lkpy_amd.basic.HistoryBatch
+
+    def _batch_csr(self, queries) -> D.DeviceCSR:
+        "The reference items of a batch as a device CSR: a HistoryBatch's training rows, or a list's"
+        queries = resolve_queries(queries, self.items)
+        if isinstance(queries, HistoryBatch):
+            return queries.csr(with_values=False)
+        return self._query_csr(queries)
+
+    def recommend_batch(self, queries, n: int | None, *, exclude_history: bool = True):
+        """
+        Top-``n`` lists for many queries at once -- what the ``recommender`` pipeline of
+        ``biased-lift.toml`` computes one query at a time: candidates = every training item minus
+        the query's own (src/lenskit/basic/candidates.py:77-94), this scorer over them,
+        ``TopNRanker`` (basic/topn.py:45-69).  Items no reference item is associated with score
+        0.0 and are listed when fewer than ``n`` score above it; a query without a known reference
+        item gets an empty list.  ``queries``: a list of queries, or a
+        :class:`lkpy_amd.basic.HistoryBatch`.  The batch goes through in panels of at most
+        ``PANEL_BYTES``.  ``n = None``: every candidate, ranked.  Returns (item numbers [B x n]
+        with -1 padding, scores [B x n] with NaN padding), like ``SLIMScorer.recommend_batch``.
+        """
+        reduce = self._reduction()
+        hist = self._batch_csr(queries)
+        s = self._device_scores()
+        B = hist.shape[0]
+        n = -1 if n is None else int(n)
+        cols = len(self.items) if n < 0 else n
+        oi = torch.full((B, cols), -1, dtype=torch.int32, device=s.indices.device)
+        osc = torch.full((B, cols), float("nan"), dtype=torch.float32, device=s.indices.device)
+        step = self._panel_rows()
+        for lo in range(0, B, step):
+            hi = min(B, lo + step)
+            panel = D.assoc_score_batch(hist.indptr, hist.indices, s, reduce, rows=(lo, hi),
+                                        strike_history=exclude_history, nan_empty=True)
+            idx = D.argtopn(panel, n)
+            oi[lo:hi, :idx.shape[1]] = idx
+            osc[lo:hi, :idx.shape[1]] = D.take_scores(panel, idx)
+        return D.lists_to_host(oi, osc)
+
+    def dense_scores_batch(self, queries):
+        """
+        Every item's score for many queries at once, left on the device: (panel f32 [B x items],
+        valid, history CSR), the contract of ``FlexMFScorerBase.dense_scores_batch``.  The row of a
+        query without a known reference item is NaN (``valid`` False); the history CSR (known
+        items, ascending) is for the caller to exclude.  The caller bounds the batch.
+        """
+        reduce = self._reduction()
+        queries = resolve_queries(queries, self.items)
+        s = self._device_scores()
+        if isinstance(queries, HistoryBatch):
+            hist = excl = queries.csr(with_values=False)  # training rows: known items, ascending
+            valid = queries.lengths > 0
+        else:
+            hist = self._query_csr(queries)
+            ptr, idx, _ = pack_histories(queries, self.items, unknown="drop", sort=True)
+            excl = D.DeviceCSR.from_arrays(ptr, idx, None, hist.shape, s.indices.device)
+            valid = np.diff(ptr) > 0
+        panel = D.assoc_score_batch(hist.indptr, hist.indices, s, reduce, nan_empty=True)
+        return panel, valid, excl
