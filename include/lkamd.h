@@ -1035,6 +1035,37 @@ int lk_stochastic_keys(const float *d_scores, int64_t n_rows, int64_t row_len, i
 int lk_stochastic_key_of_bits(const float *d_log_weight, const uint32_t *d_bits, int64_t n,
                               float *d_out, void *stream);
 
+/* ------------------------------------------------------------------------
+ * FA*IR top-N reranking (csrc/fair.hip): the greedy loop of `FAIRReranker.__call__`
+ * (src/lenskit/reranking/fair.py:198-248) for a batch of ranked lists, a wave per list.
+ *   d_lists        int32 [n_rows x ld], row_len entries of a row are looked at: item numbers in list
+ *                  order.  d_lengths (int32 [n_rows], clamped to 0..row_len) gives each row's
+ *                  length; NULL: a row ends at its first negative entry (trailing -1 padding).
+ *                  With lengths a negative entry inside a row is an item unknown to the vocabulary.
+ *   d_scores       float32 in the layout of d_lists, or NULL; copied as bits, never computed with.
+ *   d_is_protected uint8 [n_items]: non-zero = protected.  An item number outside 0..n_items-1
+ *                  is unprotected and stays in the list (fair.py:202-205).
+ *   d_m_table      int32 [n_table]: slot i needs m[i] protected items among slots 0..i (`m_list`,
+ *                  fair.py:176); n_table <= LK_FAIR_MAX_N (the kernel's LDS queues: 12 n_out bytes
+ *                  per row), n_out <= n_table.
+ *   outputs        d_out_items [n_rows x n_out] (-1 past min(n_out, length)), d_out_scores (NaN
+ *                  past it; NULL, or with d_scores) and d_out_pos (NULL or the slot's position in
+ *                  its input row, -1 past it), all dense.
+ * With P / U the positions of the protected / other entries in list order and c the protected
+ * count so far, slot i takes P's head when c < m[i] and P is not empty, else the smaller of the two
+ * heads, else the head of the queue that is not empty (fair.py:231-245).  No float arithmetic, no
+ * atomics: a row has the same result alone and in any batch.  Bad arguments (null pointers,
+ * n_out > n_table, n_table > LK_FAIR_MAX_N) are LK_E_INVALID.
+ * lk_fair_max_n: LK_FAIR_MAX_N as the library was built.
+ * ---------------------------------------------------------------------- */
+#define LK_FAIR_MAX_N 1024
+int32_t lk_fair_max_n(void);
+int lk_fair_rerank(const int32_t *d_lists, int64_t n_rows, int64_t row_len, int64_t ld,
+                   const int32_t *d_lengths, const float *d_scores,
+                   const uint8_t *d_is_protected, int64_t n_items, const int32_t *d_m_table,
+                   int32_t n_table, int32_t n_out, int32_t *d_out_items, float *d_out_scores,
+                   int32_t *d_out_pos, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1715,6 +1715,47 @@ def list_pair_stats(a_ptr: torch.Tensor, a_items: torch.Tensor, b_ptr: torch.Ten
     return rbo, lip, flag
 
 
+def fair_rerank(lists: torch.Tensor, is_protected: torch.Tensor, m_table: torch.Tensor,
+                n_out: int, *, lengths: torch.Tensor | None = None,
+                scores: torch.Tensor | None = None, want_pos: bool = False):
+    """
+    FA*IR reranking of a batch of ranked lists (lk_fair_rerank): device int32 [B x L] ``lists``
+    (rows ``stride(0)`` apart) of item numbers, ``is_protected`` uint8 [n_items], ``m_table`` int32
+    (at most ``_native.FAIR_MAX_N`` entries, ``n_out`` of them used).  ``lengths``: int32 [B] or
+    None (a row ends at its first negative entry); ``scores``: float32 in the layout of ``lists``,
+    copied as bits.  Returns device (items int32 [B x n_out] with -1 padding, scores [B x n_out]
+    with NaN padding or None, positions into the input rows or None).
+    """
+    lib = _native.require_gpu()
+    assert lists.dtype == torch.int32 and lists.dim() == 2
+    B, L = int(lists.shape[0]), int(lists.shape[1])
+    assert B == 0 or L <= 1 or lists.stride(1) == 1
+    ld = int(lists.stride(0)) if B > 1 and L > 0 else max(L, 1)
+    assert ld >= L
+    dev = lists.device
+    assert is_protected.dtype == torch.uint8 and is_protected.dim() == 1 and \
+        is_protected.is_contiguous()
+    assert m_table.dtype == torch.int32 and m_table.dim() == 1 and m_table.is_contiguous()
+    if lengths is not None:
+        assert lengths.dtype == torch.int32 and lengths.shape == (B,) and lengths.is_contiguous()
+    if scores is not None:
+        assert scores.dtype == torch.float32 and scores.shape == lists.shape
+        assert B == 0 or ((L <= 1 or scores.stride(1) == 1) and
+                          (int(scores.stride(0)) == ld or B == 1 or L == 0))
+    n_out = int(n_out)
+    out = torch.empty((B, n_out), dtype=torch.int32, device=dev)
+    out_sc = torch.empty((B, n_out), dtype=torch.float32, device=dev) if scores is not None \
+        else None
+    out_pos = torch.empty((B, n_out), dtype=torch.int32, device=dev) if want_pos else None
+    check(
+        lib.lk_fair_rerank(_ptr(lists), B, L, ld, _ptr(lengths), _ptr(scores), _ptr(is_protected),
+                           int(is_protected.shape[0]), _ptr(m_table), int(m_table.shape[0]), n_out,
+                           _ptr(out), _ptr(out_sc), _ptr(out_pos), _stream()),
+        "lk_fair_rerank",
+    )
+    return out, out_sc, out_pos
+
+
 # ---------------------------------------------------------------------------------------
 # FlexMF implicit and explicit (csrc/flexmf.hip), ragged pair scoring (csrc/mf_pairs.hip)
 # ---------------------------------------------------------------------------------------

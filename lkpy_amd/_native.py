@@ -40,6 +40,8 @@ FLEXMF_MAX_K = 256
 
 STOCHASTIC_TRANSFORMS = {None: 0, "softmax": 1, "linear": 2}
 
+FAIR_MAX_N = 1024  # LK_FAIR_MAX_N (lk_fair_max_n()): the list length lk_fair_rerank's LDS holds
+
 ASSOC_METHODS = {"probability": 0, "lift": 1}  # LK_ASSOC_PROBABILITY / LK_ASSOC_LIFT
 ASSOC_REDUCTIONS = {"mean": 0, "max": 1}  # LK_ASSOC_MEAN / LK_ASSOC_MAX
 
@@ -272,6 +274,11 @@ def _declare(lib):
                     vp, ctypes.c_uint32, vp, c_int64, vp]
         ),
         "lk_stochastic_key_of_bits": (c_int, [vp, vp, c_int64, vp, vp]),
+        "lk_fair_max_n": (c_int32, []),
+        "lk_fair_rerank": (
+            c_int, [vp, c_int64, c_int64, c_int64, vp, vp, vp, c_int64, vp, c_int32, c_int32, vp,
+                    vp, vp, vp]
+        ),
         "lk_als_implicit_half_epoch_host": (
             c_int,
             [vp, c_int, vp, vp, c_int64, c_int64, c_int32, vp, vp, vp, c_int32, vp],

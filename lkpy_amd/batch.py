@@ -14,15 +14,39 @@ from .data import ItemList, ItemListCollection, RecQuery
 from .pipeline import Pipeline
 
 
-def recommend(pipe: Pipeline, users, n: int, *, batch_size: int = 16384) -> ItemListCollection:
+def recommend(pipe: Pipeline, users, n: int, *, batch_size: int = 16384,
+              rerank_depth: int | None = None) -> ItemListCollection:
     """Ordered lists of ``n`` recommendations as an ``ItemListCollection`` keyed by ``user_id``
     (what ``BatchResults.output("recommendations")`` is in the reference,
     src/lenskit/batch/_runner.py:157-191): ``out.lookup(user)`` / ``out.lookup(user_id=user)``,
     iteration over ``(key, list)``, ``out.to_df()``.  A pipeline whose ranker is a
     ``StochasticTopNRanker`` gets sampled rankings (``_sample_panels``), any other the scorer's
-    own top-N."""
+    own top-N.
+
+    A pipeline with a ``reranker`` node (``Pipeline.add_reranker``) has the [B x n] arrays of
+    every branch passed through the component's ``rerank_batch`` before the lists are built -- on
+    the device where the scorer's ``recommend_batch`` has ``device_output`` --; a reranker
+    without ``rerank_batch``, or one over another item vocabulary than the scorer's, runs through
+    ``pipe.run`` user by user.  ``rerank_depth`` (>= n):
+    the scorer's lists are taken at that depth and reranked down to ``n``.  That departs from the
+    reference's wiring, where the reranker sees the ranker's ``n`` items and can only reorder
+    them (``pipe.run`` keeps that); it gives a fairness reranker items to promote.  Not with a
+    stochastic ranker."""
     scorer = pipe.node("scorer").component
     lookup = pipe.node("history-lookup").component
+    reranker = _reranker(pipe)
+    batched = _reranks_batches(reranker, scorer)
+    if rerank_depth is not None:
+        if not batched:
+            raise ValueError("rerank_depth needs a pipeline whose reranker has rerank_batch")
+        if _stochastic_ranker(pipe) is not None:
+            raise ValueError("rerank_depth does not apply to a stochastic ranker")
+        if rerank_depth < n:
+            raise ValueError(f"rerank_depth = {rerank_depth} is below n = {n}")
+    if reranker is not None and not batched:
+        return ItemListCollection.from_dict(
+            {u: pipe.run("recommender", query=u, n=n) for u in users}, key=("user_id",))
+    depth = n if rerank_depth is None else int(rerank_depth)
     if _stochastic_ranker(pipe) is not None:
         # a sampled ranking is not the scorer's own top-N: the lists come from the ranker, by
         # panels where the scorer has them, else through the pipeline user by user
@@ -30,17 +54,26 @@ def recommend(pipe: Pipeline, users, n: int, *, batch_size: int = 16384) -> Item
             return ItemListCollection.from_dict(
                 {u: pipe.run("recommender", query=u, n=n) for u in users}, key=("user_id",))
         ids, idx, keys = _sample_panels(pipe, users, n, 1, batch_size)
-        return ItemListCollection.from_arrays(ids, idx[:, 0], keys[:, 0], scorer.items,
-                                              key=("user_id",))
+        i0, k0 = idx[:, 0], keys[:, 0]
+        if batched:
+            i0, k0 = reranker.rerank_batch(i0, k0, _rerank_length(n))
+        return ItemListCollection.from_arrays(ids, i0, k0, scorer.items, key=("user_id",))
     if hasattr(scorer, "recommend_batch") and hasattr(lookup, "batch") and \
             getattr(scorer, "accepts_history_batch", False):
         # the whole batch by user number: the histories are rows of the HBM-resident training
         # matrix, no per-query host work (an id ARRAY stays an array); the lists are built when
         # somebody looks at them
         ids = users if isinstance(users, np.ndarray) else np.asarray(list(users))
+        on_device = batched and _has_device_output(scorer)
         idx, sc = [], []
         for s in range(0, len(ids), batch_size):
-            i, v = scorer.recommend_batch(lookup.batch(ids[s:s + batch_size]), n)
+            if on_device:  # (the lists meet the reranker where they are)
+                i, v = scorer.recommend_batch(lookup.batch(ids[s:s + batch_size]), depth,
+                                              device_output=True)
+            else:
+                i, v = scorer.recommend_batch(lookup.batch(ids[s:s + batch_size]), depth)
+            if batched:
+                i, v = reranker.rerank_batch(i, v, n)
             idx.append(i)
             sc.append(v)
         if not idx:
@@ -55,7 +88,9 @@ def recommend(pipe: Pipeline, users, n: int, *, batch_size: int = 16384) -> Item
         for s in range(0, len(users), batch_size):
             chunk = users[s:s + batch_size]
             queries = [lookup(RecQuery.create(u)) for u in chunk]
-            idx, sc = scorer.recommend_batch(queries, n)
+            idx, sc = scorer.recommend_batch(queries, depth)
+            if batched:
+                idx, sc = reranker.rerank_batch(idx, sc, n)
             for u, i, v in zip(chunk, idx, sc):
                 keep = i >= 0
                 out[u] = ItemList(item_nums=i[keep], vocabulary=scorer.items, scores=v[keep],
@@ -64,6 +99,31 @@ def recommend(pipe: Pipeline, users, n: int, *, batch_size: int = 16384) -> Item
         for u in users:
             out[u] = pipe.run("recommender", query=u, n=n)
     return ItemListCollection.from_dict(out, key=("user_id",))
+
+
+def _reranker(pipe: Pipeline):
+    "the component of the pipeline's ``reranker`` node, or None"
+    node = pipe.nodes.get("reranker")
+    return None if node is None else node.component
+
+
+def _reranks_batches(reranker, scorer) -> bool:
+    "``rerank_batch`` takes the scorer's item NUMBERS: it must exist and mean the same items"
+    if reranker is None or not hasattr(reranker, "rerank_batch"):
+        return False
+    mine, theirs = getattr(reranker, "vocab", None), getattr(scorer, "items", None)
+    return mine is None or mine is theirs or mine == theirs
+
+
+def _rerank_length(n):
+    "a ranker's length as a reranker takes it: None where the ranker's means `every item`"
+    return None if n is None or n < 0 else int(n)
+
+
+def _has_device_output(scorer) -> bool:
+    import inspect
+
+    return "device_output" in inspect.signature(scorer.recommend_batch).parameters
 
 
 # what the score panel and the key panel of one chunk of a stochastic batch may take together
@@ -116,25 +176,43 @@ def recommend_samples(pipe: Pipeline, users, n: int, samples: int, *,
     ``samples`` sampled rankings of ``n`` items per user from a pipeline whose ranker is a
     :class:`lkpy_amd.stochastic.StochasticTopNRanker`, keyed by ``(user_id, sample)``; sample 0 is
     what ``recommend`` draws.  A scorer without ``dense_scores_batch`` is scored through the
-    pipeline user by user and ranked ``samples`` times.
+    pipeline user by user and ranked ``samples`` times.  A pipeline's ``reranker`` is applied to
+    every sampled list, as ``recommend`` applies it.
     """
     ranker = _stochastic_ranker(pipe)
     if ranker is None:
         raise TypeError("recommend_samples needs a pipeline whose ranker is a StochasticTopNRanker")
     samples = int(samples)
     scorer = pipe.node("scorer").component
+    reranker = _reranker(pipe)
+    if reranker is not None and not _reranks_batches(reranker, scorer) and \
+            _has_panels(scorer, pipe.node("history-lookup").component):
+        ids, idx, keys = _sample_panels(pipe, users, n, samples, batch_size)
+        out = {}
+        for b, u in enumerate(ids.tolist()):
+            for s in range(samples):
+                keep = idx[b, s] >= 0
+                il = ItemList(item_nums=idx[b, s][keep], vocabulary=scorer.items,
+                              scores=keys[b, s][keep], ordered=True)
+                out[(u, s)] = reranker(items=il, n=_rerank_length(n))
+        return ItemListCollection.from_dict(out, key=("user_id", "sample"))
     if not _has_panels(scorer, pipe.node("history-lookup").component):
         out = {}
         for u in users:
             got = pipe.run_all("history-lookup", "scorer", query=u)
             lists = ranker.sample(got["scorer"], got["history-lookup"], n, samples=samples)
+            if reranker is not None:
+                lists = [reranker(items=il, n=_rerank_length(n)) for il in lists]
             out.update({(u, s): il for s, il in enumerate(lists)})
         return ItemListCollection.from_dict(out, key=("user_id", "sample"))
     ids, idx, keys = _sample_panels(pipe, users, n, samples, batch_size)
     pairs = [(u, s) for u in ids.tolist() for s in range(samples)]
     flat = idx.shape[0] * idx.shape[1]
-    return ItemListCollection.from_arrays(pairs, idx.reshape(flat, -1), keys.reshape(flat, -1),
-                                          scorer.items, key=("user_id", "sample"))
+    idx, keys = idx.reshape(flat, -1), keys.reshape(flat, -1)
+    if reranker is not None:
+        idx, keys = reranker.rerank_batch(idx, keys, _rerank_length(n))
+    return ItemListCollection.from_arrays(pairs, idx, keys, scorer.items,
+                                          key=("user_id", "sample"))
 
 
 def predict(pipe: Pipeline, pairs, *, batch_size: int = 16384) -> ItemListCollection:

@@ -660,7 +660,9 @@ class Dataset:
         self._cols = np.require(cols, dtype=np.int32)[order]
         self._attrs = {k: np.asarray(v)[order] for k, v in attrs.items()}
         # item x category matrices (dense or scipy.sparse, row i = item number i) by attribute
-        # name: what the diversity metrics read (``items.attribute(name).cat_matrix()``)
+        # name: what the diversity metrics read (``items.attribute(name).cat_matrix()``).  A second
+        # shape, scalar attributes: a 1-D array-like of ``item_count`` values, entry i = item
+        # number i (``items.attribute(name).numpy()``) -- the FA*IR reranker's protected flag
         self.item_attrs: dict[str, Any] = {}
         # repeated (user, item) pairs are kept as separate interactions (as the reference's
         # interaction tables do); consumers that need a MATRIX sum them, as SciPy's COO -> CSR

@@ -140,6 +140,14 @@ class Pipeline:
         node.kind = "component"
         node.wiring.update(wiring)
 
+    def add_reranker(self, comp, config=None):
+        """the ``reranker`` slot of the standard pipelines (``_common.py:149-155``): it takes the
+        ranker's list and ``n``, and ``recommender`` (the default) now names it"""
+        self.add_component("reranker", comp, config, items="ranker", n="n")
+        self.alias("recommender", "reranker")
+        self.default = "recommender"
+        return "reranker"
+
     def use_first_of(self, name, *sources):
         self.nodes[name] = Node(name, kind="first-of", wiring={"sources": list(sources)})
         return name
@@ -207,6 +215,8 @@ class Pipeline:
             config = spec.get("config", None)
             if name in pipe.nodes:
                 pipe.replace_component(name, comp_cls, config, **spec.get("inputs", {}))
+            elif name == "reranker" and "inputs" not in spec and "ranker" in pipe.nodes:
+                pipe.add_reranker(comp_cls, config)
             else:
                 pipe.add_component(name, comp_cls, config, **spec.get("inputs", {}))
         return pipe
@@ -289,15 +299,19 @@ class Pipeline:
 
 
 def topn_pipeline(scorer, *, predicts_ratings: bool = False, n: int | None = None,
-                  name: str | None = None) -> Pipeline:  # fmt: skip
+                  name: str | None = None, reranker=None) -> Pipeline:  # fmt: skip
     p = Pipeline.std_topn_predict(name, {"default_length": n}) if predicts_ratings \
         else Pipeline.std_topn(name, {"default_length": n})
     p.replace_component("scorer", scorer)
+    if reranker is not None:
+        p.add_reranker(reranker)
     return p
 
 
 def predict_pipeline(scorer, *, fallback: bool = True, n: int | None = None,
-                     name: str | None = None) -> Pipeline:  # fmt: skip
+                     name: str | None = None, reranker=None) -> Pipeline:  # fmt: skip
     p = Pipeline.std_topn_predict(name, {"default_length": n, "fallback_predictor": fallback})
     p.replace_component("scorer", scorer)
+    if reranker is not None:
+        p.add_reranker(reranker)
     return p
