@@ -199,6 +199,14 @@ class DeviceCSR:
         )
 
     @classmethod
+    def from_host(cls, indptr, indices, values, shape, dev) -> "DeviceCSR":
+        """
+        A model matrix uploaded as the batch scoring calls take it: ``from_arrays`` with the
+        offsets int64 whatever the host has (SciPy's are int32).  Nothing is sorted or modified.
+        """
+        return cls.from_arrays(np.asarray(indptr, dtype=np.int64), indices, values, shape, dev)
+
+    @classmethod
     def from_scipy(cls, mat, dev) -> "DeviceCSR":
         mat = mat.tocsr()
         mat.sort_indices()

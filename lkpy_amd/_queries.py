@@ -71,6 +71,21 @@ def pack_histories(queries: list[RecQuery], items: Vocabulary, *, unknown: str,
     return ptr, cat(idx, np.int32), None if values is None else cat(val, np.float32)
 
 
+def pack_targets(item_lists: list[ItemList], items: Vocabulary):
+    """
+    The target lists of a batch as ragged rows over ``items``: (offsets int64 [B + 1], item
+    numbers int32), list order kept, repeats kept, -1 for an item ``items`` does not have.  One
+    vocabulary lookup over the concatenated ids; list ``i``'s numbers are
+    ``nums[ptr[i]:ptr[i + 1]]``.
+    """
+    ptr = np.zeros(len(item_lists) + 1, dtype=np.int64)
+    np.cumsum([len(il) for il in item_lists], out=ptr[1:])
+    ids = [il.ids() for il in item_lists if len(il)]
+    if not ids:
+        return ptr, np.zeros(0, np.int32)
+    return ptr, items.numbers(np.concatenate(ids), missing="negative")
+
+
 def user_numbers(queries, users: Vocabulary | None) -> np.ndarray:
     """
     The queries' rows in ``users`` (int64, -1 = unknown user, no user id, or ``users`` is None).

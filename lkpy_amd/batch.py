@@ -44,27 +44,24 @@ def recommend(pipe: Pipeline, users, n: int, *, batch_size: int = 16384,
         if rerank_depth < n:
             raise ValueError(f"rerank_depth = {rerank_depth} is below n = {n}")
     if reranker is not None and not batched:
-        return ItemListCollection.from_dict(
-            {u: pipe.run("recommender", query=u, n=n) for u in users}, key=("user_id",))
+        return _recommend_loop(pipe, users, n)
     depth = n if rerank_depth is None else int(rerank_depth)
     if _stochastic_ranker(pipe) is not None:
         # a sampled ranking is not the scorer's own top-N: the lists come from the ranker, by
         # panels where the scorer has them, else through the pipeline user by user
         if not _has_panels(scorer, lookup):
-            return ItemListCollection.from_dict(
-                {u: pipe.run("recommender", query=u, n=n) for u in users}, key=("user_id",))
+            return _recommend_loop(pipe, users, n)
         ids, idx, keys = _sample_panels(pipe, users, n, 1, batch_size)
         i0, k0 = idx[:, 0], keys[:, 0]
         if batched:
             i0, k0 = reranker.rerank_batch(i0, k0, _rerank_length(n))
         return ItemListCollection.from_arrays(ids, i0, k0, scorer.items, key=("user_id",))
-    if hasattr(scorer, "recommend_batch") and hasattr(lookup, "batch") and \
-            getattr(scorer, "accepts_history_batch", False):
+    if hasattr(scorer, "recommend_batch") and _takes_history_batches(scorer, lookup):
         # the whole batch by user number: the histories are rows of the HBM-resident training
         # matrix, no per-query host work (an id ARRAY stays an array); the lists are built when
         # somebody looks at them
         ids = users if isinstance(users, np.ndarray) else np.asarray(list(users))
-        on_device = batched and _has_device_output(scorer)
+        on_device = batched and getattr(scorer, "returns_device_lists", False)
         idx, sc = [], []
         for s in range(0, len(ids), batch_size):
             if on_device:  # (the lists meet the reranker where they are)
@@ -83,22 +80,31 @@ def recommend(pipe: Pipeline, users, n: int, *, batch_size: int = 16384,
                                               sc[0] if one else np.concatenate(sc),
                                               scorer.items, key=("user_id",))
     users = list(users)
+    if not hasattr(scorer, "recommend_batch"):
+        return _recommend_loop(pipe, users, n)
     out = {}
-    if hasattr(scorer, "recommend_batch"):
-        for s in range(0, len(users), batch_size):
-            chunk = users[s:s + batch_size]
-            queries = [lookup(RecQuery.create(u)) for u in chunk]
-            idx, sc = scorer.recommend_batch(queries, depth)
-            if batched:
-                idx, sc = reranker.rerank_batch(idx, sc, n)
-            for u, i, v in zip(chunk, idx, sc):
-                keep = i >= 0
-                out[u] = ItemList(item_nums=i[keep], vocabulary=scorer.items, scores=v[keep],
-                                  ordered=True)
-    else:
-        for u in users:
-            out[u] = pipe.run("recommender", query=u, n=n)
+    for s in range(0, len(users), batch_size):
+        chunk = users[s:s + batch_size]
+        queries = [lookup(RecQuery.create(u)) for u in chunk]
+        idx, sc = scorer.recommend_batch(queries, depth)
+        if batched:
+            idx, sc = reranker.rerank_batch(idx, sc, n)
+        for u, i, v in zip(chunk, idx, sc):
+            keep = i >= 0
+            out[u] = ItemList(item_nums=i[keep], vocabulary=scorer.items, scores=v[keep],
+                              ordered=True)
     return ItemListCollection.from_dict(out, key=("user_id",))
+
+
+def _recommend_loop(pipe: Pipeline, users, n) -> ItemListCollection:
+    "``recommend`` through ``pipe.run``, one user at a time"
+    return ItemListCollection.from_dict(
+        {u: pipe.run("recommender", query=u, n=n) for u in users}, key=("user_id",))
+
+
+def _takes_history_batches(scorer, lookup) -> bool:
+    "the lookup hands out ``HistoryBatch`` es and the scorer's batch calls take them"
+    return hasattr(lookup, "batch") and getattr(scorer, "accepts_history_batch", False)
 
 
 def _reranker(pipe: Pipeline):
@@ -120,12 +126,6 @@ def _rerank_length(n):
     return None if n is None or n < 0 else int(n)
 
 
-def _has_device_output(scorer) -> bool:
-    import inspect
-
-    return "device_output" in inspect.signature(scorer.recommend_batch).parameters
-
-
 # what the score panel and the key panel of one chunk of a stochastic batch may take together
 STOCHASTIC_PANEL_BYTES = 4 << 30
 
@@ -140,8 +140,7 @@ def _stochastic_ranker(pipe: Pipeline):
 
 
 def _has_panels(scorer, lookup) -> bool:
-    return hasattr(scorer, "dense_scores_batch") and hasattr(lookup, "batch") and \
-        getattr(scorer, "accepts_history_batch", False)
+    return hasattr(scorer, "dense_scores_batch") and _takes_history_batches(scorer, lookup)
 
 
 def _sample_panels(pipe: Pipeline, users, n: int, samples: int, batch_size: int):

@@ -33,7 +33,8 @@ from pydantic import BaseModel, NonNegativeInt, PositiveFloat, PositiveInt, mode
 
 from . import _device as D
 from . import _native
-from ._queries import item_scores, pack_histories, resolve_queries, user_numbers
+from ._queries import (item_scores, pack_histories, pack_targets, resolve_queries,
+                       user_numbers)
 from .als import _DeviceBacked, _scorer_state
 from .basic import HistoryBatch
 from .data import Dataset, ItemList, RecQuery, Vocabulary
@@ -144,6 +145,7 @@ class FlexMFScorerBase(UsesTrainer, Component):
     """
 
     accepts_history_batch = True  # recommend_batch takes a lkpy_amd.basic.HistoryBatch
+    returns_device_lists = True  # ... and has ``device_output``: the lists left on the device
 
     users: Vocabulary
     items: Vocabulary
@@ -320,13 +322,8 @@ class FlexMFExplicitScorer(FlexMFScorerBase):
     def score_batch(self, queries, item_lists) -> list[ItemList]:
         "``__call__`` for many queries: one vocabulary pass, one launch, the same bits."
         qs = [RecQuery.create(q) for q in queries]
-        user_nums = user_numbers(qs, self.users)
-        ptr = np.zeros(len(qs) + 1, np.int64)
-        np.cumsum([len(il) for il in item_lists], out=ptr[1:])
-        ids = [il.ids() for il in item_lists if len(il)]
-        nums = self.items.numbers(np.concatenate(ids), missing="negative") if ids else \
-            np.zeros(0, np.int32)
-        scores = self.score_pairs(user_nums, ptr, nums)
+        ptr, nums = pack_targets(item_lists, self.items)
+        scores = self.score_pairs(user_numbers(qs, self.users), ptr, nums)
         return [ItemList(il, scores=scores[ptr[i]:ptr[i + 1]])
                 for i, il in enumerate(item_lists)]
 

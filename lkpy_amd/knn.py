@@ -14,6 +14,7 @@ scoring run in the HIP kernels.
 from __future__ import annotations
 
 import warnings
+from functools import partial
 from typing import Literal
 
 import numpy as np
@@ -23,7 +24,7 @@ from pydantic import (AliasChoices, BaseModel, Field, NonNegativeFloat, Positive
                       field_validator)
 
 from . import _device as D
-from ._queries import item_scores, pack_histories, resolve_queries
+from ._queries import item_scores, pack_histories, pack_targets, resolve_queries
 from .basic import HistoryBatch
 from .data import Dataset, ItemList, RecQuery, SparseRowArray, Vocabulary
 from .pipeline import Component
@@ -98,13 +99,7 @@ class ItemKNNScorer(Component):
             d = D.device()
             from .matrix import csr_arrays
 
-            so, si, sv, shape = csr_arrays(self.sim_matrix)
-            return {"device": d,
-                    "sims": D.DeviceCSR(
-                        torch.from_numpy(np.array(so, dtype=np.int64)).to(d),
-                        torch.from_numpy(np.array(si, dtype=np.int32)).to(d),
-                        torch.from_numpy(np.array(sv, dtype=np.float32)).to(d),
-                        shape, None)}
+            return {"device": d, "sims": D.DeviceCSR.from_host(*csr_arrays(self.sim_matrix), d)}
 
         return self._device_cache("sims", upload, self.sim_matrix)
 
@@ -181,10 +176,7 @@ class ItemKNNScorer(Component):
         "Score many (query, items) pairs in one kernel launch (item.py:231-295 per pair)."
         hist = self._query_csr([RecQuery.create(q) for q in queries])
         d = hist.indices.device
-        t_idx = [items.numbers(vocabulary=self.items, missing="negative") for items in item_lists]
-        t_ptr = np.zeros(len(t_idx) + 1, np.int64)
-        np.cumsum([len(ti) for ti in t_idx], out=t_ptr[1:])
-        tgt = np.concatenate(t_idx).astype(np.int32) if t_idx else np.zeros(0, np.int32)
+        t_ptr, tgt = pack_targets(item_lists, self.items)
         s, c = self._score(hist, torch.from_numpy(t_ptr).to(d), torch.from_numpy(tgt).to(d))
         s, c = s.cpu().numpy(), c.cpu().numpy()
         out = []
@@ -193,7 +185,7 @@ class ItemKNNScorer(Component):
                 out.append(ItemList(items, scores=np.nan))  # no history: item.py:238-245
                 continue
             sc = s[t_ptr[qi]:t_ptr[qi + 1]].copy()
-            ti = t_idx[qi]
+            ti = tgt[t_ptr[qi]:t_ptr[qi + 1]]
             if self.config.explicit:
                 m = ti >= 0
                 sc[m] += self.item_means[ti[m]]  # item.py:282
@@ -342,15 +334,10 @@ class UserKNNScorer(Component):
             d = D.device()
             uv = self.user_vectors
             uv.sort_indices()
-            ro, ri, rv, shape = csr_arrays(self.user_ratings)
             return {
                 "device": d,
                 "vectors": D.DeviceCSR.from_arrays(uv.indptr, uv.indices, uv.data, uv.shape, d),
-                "ratings": D.DeviceCSR(
-                    torch.from_numpy(np.array(ro, dtype=np.int64)).to(d),
-                    torch.from_numpy(np.array(ri, dtype=np.int32)).to(d),
-                    None if rv is None else torch.from_numpy(np.array(rv, np.float32)).to(d),
-                    shape, None),
+                "ratings": D.DeviceCSR.from_host(*csr_arrays(self.user_ratings), d),
             }
 
         return self._device_cache("model", upload, self.user_vectors, self.user_ratings)
@@ -413,16 +400,11 @@ class UserKNNScorer(Component):
         nbr_ptr[1:] = torch.cumsum(counts, 0)
         nbr_rows = mask.nonzero()[:, 1].to(torch.int32)  # per query, ascending user number
         nbr_sims = sims[mask]
-        t_idx, t_ptr = [], [0]
-        for i in live:
-            ti = item_lists[i].numbers(vocabulary=self.items, missing="negative")
-            t_idx.append(ti)
-            t_ptr.append(t_ptr[-1] + len(ti))
-        tgt = torch.from_numpy(np.concatenate(t_idx).astype(np.int32)).to(d)
+        t_ptr, tgt = pack_targets([item_lists[i] for i in live], self.items)
         s, _c = D.uknn_score_batch(st["ratings"], nbr_ptr, nbr_rows.contiguous(),
-                                   nbr_sims.contiguous(),
-                                   torch.from_numpy(np.asarray(t_ptr, np.int64)).to(d), tgt,
-                                   self.config.max_nbrs, self.config.min_nbrs)
+                                   nbr_sims.contiguous(), torch.from_numpy(t_ptr).to(d),
+                                   torch.from_numpy(tgt).to(d), self.config.max_nbrs,
+                                   self.config.min_nbrs)
         s = s.cpu().numpy()
         has_nbrs = counts.cpu().numpy() > 0
         for b, i in enumerate(live):
@@ -434,6 +416,24 @@ class UserKNNScorer(Component):
 
     def __call__(self, query, items: ItemList) -> ItemList:
         return self.score_batch([query], [items])[0]
+
+
+def _binary_cooccurrence(data: Dataset):
+    """
+    The item-item co-occurrence counts of the training matrix, (user, item) pairs counted once:
+    the similarity-build kernel on unit values.  Returns (device CSR of the counts, the host
+    user-item and item-user matrices it was built from, the device).
+    """
+    ui = data.interactions().matrix().scipy(attribute=None).astype(np.float32)
+    ui = sps.csr_array(ui)
+    ui.sum_duplicates()
+    ui.data[:] = 1.0  # co-occurrences count (user, item) pairs once
+    ui.sort_indices()
+    iu = sps.csr_array(ui.T)
+    iu.sort_indices()
+    d = D.device()
+    cooc = D.iknn_build(D.DeviceCSR.from_scipy(ui, d), D.DeviceCSR.from_scipy(iu, d), 0.5)
+    return cooc, ui, iu, d
 
 
 class EASEConfig(BaseModel, extra="forbid"):
@@ -470,15 +470,7 @@ class EASEScorer(Component):
         if solver == "scipy":
             raise ValueError("LK_EASE_SOLVER=scipy: the device backend has no host solver")
         n_items = data.item_count
-        ui = data.interactions().matrix().scipy(attribute=None).astype(np.float32)
-        ui = sps.csr_array(ui)
-        ui.sum_duplicates()
-        ui.data[:] = 1.0  # co-occurrences count (user, item) pairs once
-        ui.sort_indices()
-        iu = sps.csr_array(ui.T)
-        iu.sort_indices()
-        d = D.device()
-        cooc = D.iknn_build(D.DeviceCSR.from_scipy(ui, d), D.DeviceCSR.from_scipy(iu, d), 0.5)
+        cooc, _ui, iu, d = _binary_cooccurrence(data)
         counts = torch.from_numpy(np.diff(iu.indptr).astype(np.int32)).to(d)
         gram = D.ease_gram(cooc, counts, float(self.config.regularization))
         del cooc
@@ -519,6 +511,103 @@ class EASEScorer(Component):
 
 
 # ---------------------------------------------------------------------------------------
+# Panel scorers: a sparse item-item model, every item scored for a panel of queries at a time
+# ---------------------------------------------------------------------------------------
+
+
+class _PanelScorer:
+    """
+    What ``SLIMScorer`` and ``AssociationScorer`` share, beside :class:`Component`: the model is a
+    sparse item-item matrix in HBM, a kernel call scores every item for a range of queries (a
+    [rows x items] float32 panel), and a batch goes through in panels of at most ``PANEL_BYTES``.
+    A subclass supplies ``items``, :meth:`_device_matrix` and :meth:`_score_panel`.
+    """
+
+    PANEL_BYTES = 1 << 30  # score panel of one recommend / score step
+    accepts_history_batch = True  # recommend_batch takes a lkpy_amd.basic.HistoryBatch
+
+    def _device_matrix(self) -> D.DeviceCSR:
+        "The model matrix in HBM (int64 offsets), uploaded once per model."
+        raise NotImplementedError
+
+    def _score_panel(self, hist: D.DeviceCSR, rows, *, strike_history: bool, nan_empty: bool):
+        "One kernel call: the device panel of the queries ``rows = (lo, hi)`` of ``hist``."
+        raise NotImplementedError
+
+    def _panel_rows(self) -> int:
+        return max(1, self.PANEL_BYTES // (4 * max(len(self.items), 1)))
+
+    def _query_csr(self, queries: list[RecQuery]) -> D.DeviceCSR:
+        "The histories of a list of queries in query order, uploaded: item numbers, -1 = unknown."
+        ptr, idx, _ = pack_histories(queries, self.items, unknown="keep")
+        return D.DeviceCSR.from_arrays(ptr, idx, None, (len(queries), len(self.items)),
+                                       self._device_matrix().indices.device)
+
+    def _batch_csr(self, queries) -> D.DeviceCSR:
+        "The histories of a batch as a device CSR: a HistoryBatch's training rows, or a list's."
+        queries = resolve_queries(queries, self.items)
+        if isinstance(queries, HistoryBatch):
+            return queries.csr(with_values=False)
+        return self._query_csr(queries)
+
+    def _score_lists(self, hist: D.DeviceCSR, item_lists, *, nan_empty: bool, score_panel=None):
+        """
+        The loop of ``score_batch``: each panel of ``hist`` scored (by ``score_panel``, called
+        like :meth:`_score_panel`, which it defaults to) and downloaded, each list's scores read
+        out of its query's row.  ``nan_empty``: the kernel makes the row of a query without a
+        known history item NaN; else an empty row of ``hist`` (a query CSR: the host has its
+        offsets) is told here.
+        """
+        score_panel = score_panel or self._score_panel
+        out = []
+        step = self._panel_rows()
+        for lo in range(0, len(item_lists), step):
+            hi = min(len(item_lists), lo + step)
+            panel = D.to_host(score_panel(hist, (lo, hi), strike_history=False,
+                                          nan_empty=nan_empty))
+            for i in range(lo, hi):
+                items = item_lists[i]
+                if not nan_empty and hist.h_indptr[i] == hist.h_indptr[i + 1]:
+                    out.append(ItemList(items, scores=np.nan))
+                    continue
+                out.append(ItemList(items, scores=item_scores(items, self.items, panel[i - lo])))
+        return out
+
+    def __call__(self, query, items: ItemList) -> ItemList:
+        return self.score_batch([query], [items])[0]
+
+    def recommend_batch(self, queries, n: int | None, *, exclude_history: bool = True):
+        """
+        Top-``n`` lists for many queries at once -- what the ``recommender`` pipeline computes one
+        query at a time: candidates = every training item minus the query's own
+        (src/lenskit/basic/candidates.py:77-94), this scorer over them, ``TopNRanker``
+        (basic/topn.py:45-69).  Items no history item points at score 0.0 and are listed when
+        fewer than ``n`` score above it; a query without a known history item gets an empty list.
+        ``queries``: a list of queries, or a :class:`lkpy_amd.basic.HistoryBatch` (training
+        histories by user number, cut out of the HBM-resident training matrix).  The batch goes
+        through in panels of at most ``PANEL_BYTES``, each selected from by ``lk_argtopn``.
+        ``n`` negative or None: every candidate, ranked.  Returns (item numbers [B x n] with -1
+        padding, scores [B x n] with NaN padding), like ``ItemKNNScorer.recommend_batch``.
+        """
+        hist = self._batch_csr(queries)
+        d = self._device_matrix().indices.device
+        B = hist.shape[0]
+        n = -1 if n is None else int(n)
+        cols = len(self.items) if n < 0 else n
+        oi = torch.full((B, cols), -1, dtype=torch.int32, device=d)
+        osc = torch.full((B, cols), float("nan"), dtype=torch.float32, device=d)
+        step = self._panel_rows()
+        for lo in range(0, B, step):
+            hi = min(B, lo + step)
+            panel = self._score_panel(hist, (lo, hi), strike_history=exclude_history,
+                                      nan_empty=True)
+            idx = D.argtopn(panel, n)
+            oi[lo:hi, :idx.shape[1]] = idx
+            osc[lo:hi, :idx.shape[1]] = D.take_scores(panel, idx)
+        return D.lists_to_host(oi, osc)
+
+
+# ---------------------------------------------------------------------------------------
 # SLIM / fsSLIM
 # ---------------------------------------------------------------------------------------
 
@@ -536,15 +625,15 @@ class SLIMConfig(BaseModel, extra="forbid"):
     "Maximum neighbours (features) per item; a positive integer enables fsSLIM (cosine selection)."
 
 
-class SLIMScorer(Component):
+class SLIMScorer(_PanelScorer, Component):
     """
     Sparse linear methods (``SLIMScorer``, src/lenskit/knn/slim.py:53-152): one elastic-net
     regression per item, learned by coordinate descent with soft thresholding.  Training runs on
     the device, a wave per column, and learns the reference's sparse matrix bit for bit
     (``lk_slim_train_count`` / ``_fill``, csrc/slim.hip); scoring adds the history items' weight
     rows in history order (``lk_slim_score_batch``), whole batches of queries at a time, and
-    ``recommend_batch`` selects the lists from bounded panels with ``lk_argtopn``.  The learned
-    state stays on the host: ``weights`` (SciPy CSR, feature rows) and ``items``.
+    ``recommend_batch`` selects the lists from bounded panels (:class:`_PanelScorer`).  The
+    learned state stays on the host: ``weights`` (SciPy CSR, feature rows) and ``items``.
     """
 
     config: SLIMConfig
@@ -552,8 +641,6 @@ class SLIMScorer(Component):
     weights: sps.csr_array
     "The TRANSPOSED weight matrix: ``weights[i, j]`` is the weight of item i in predicting item j."
     items: Vocabulary
-
-    PANEL_BYTES = 1 << 30  # score panel of one recommend / score step
 
     def is_trained(self) -> bool:
         return hasattr(self, "weights")
@@ -585,78 +672,22 @@ class SLIMScorer(Component):
     def _device_weights(self) -> D.DeviceCSR:
         def upload():
             w = self.weights
-            d = D.device()
-            return D.DeviceCSR(torch.from_numpy(np.array(w.indptr, dtype=np.int64)).to(d),
-                               torch.from_numpy(np.array(w.indices, dtype=np.int32)).to(d),
-                               torch.from_numpy(np.array(w.data, dtype=np.float32)).to(d),
-                               (int(w.shape[0]), int(w.shape[1])), None)
+            return D.DeviceCSR.from_host(w.indptr, w.indices, w.data, w.shape, D.device())
 
         return self._device_cache("weights", upload, self.weights)
 
-    def _panel_rows(self) -> int:
-        return max(1, self.PANEL_BYTES // (4 * max(len(self.items), 1)))
+    def _device_matrix(self) -> D.DeviceCSR:
+        return self._device_weights()
 
-    def _query_csr(self, queries: list[RecQuery]) -> D.DeviceCSR:
-        "The histories of a list of queries in query order, uploaded: item numbers, -1 = unknown."
-        ptr, idx, _ = pack_histories(queries, self.items, unknown="keep")
-        return D.DeviceCSR.from_arrays(ptr, idx, None, (len(queries), len(self.items)),
-                                       self._device_weights().indices.device)
+    def _score_panel(self, hist, rows, *, strike_history, nan_empty):
+        return D.slim_score_batch(hist.indptr, hist.indices, self._device_matrix(), rows=rows,
+                                  strike_history=strike_history, nan_empty=nan_empty)
 
     def score_batch(self, queries, item_lists) -> list[ItemList]:
         "Scores for a batch of (query, items) pairs (slim.py:121-152 per pair)."
-        w = self._device_weights()
         hist = self._query_csr([RecQuery.create(q) for q in queries])
-        out = []
-        step = self._panel_rows()
-        for lo in range(0, len(item_lists), step):
-            hi = min(len(item_lists), lo + step)
-            panel = D.to_host(D.slim_score_batch(hist.indptr, hist.indices, w, rows=(lo, hi)))
-            for i in range(lo, hi):
-                items = item_lists[i]
-                if hist.h_indptr[i] == hist.h_indptr[i + 1]:
-                    out.append(ItemList(items, scores=np.nan))  # no / empty history: 125-130
-                    continue
-                out.append(ItemList(items, scores=item_scores(items, self.items, panel[i - lo])))
-        return out
-
-    def __call__(self, query, items: ItemList) -> ItemList:
-        return self.score_batch([query], [items])[0]
-
-    # -- top-n --------------------------------------------------------------------------------
-    accepts_history_batch = True  # recommend_batch takes a lkpy_amd.basic.HistoryBatch
-
-    def recommend_batch(self, queries, n: int, *, exclude_history: bool = True):
-        """
-        Top-``n`` lists for many queries at once -- what the ``recommender`` pipeline computes one
-        query at a time: candidates = every training item minus the query's own
-        (src/lenskit/basic/candidates.py:77-94), this scorer over them, ``TopNRanker``
-        (basic/topn.py:45-69).  Items no history item points at score 0.0 and are listed when
-        fewer than ``n`` score above it; a query without history gets an empty list.
-        ``queries``: a list of queries, or a :class:`lkpy_amd.basic.HistoryBatch` (training
-        histories by user number, cut out of the HBM-resident training matrix).  The batch goes
-        through in panels of at most ``PANEL_BYTES``.  Returns (item numbers [B x n] with -1
-        padding, scores [B x n] with NaN padding), like ``ItemKNNScorer.recommend_batch``.
-        """
-        queries = resolve_queries(queries, self.items)
-        w = self._device_weights()
-        if isinstance(queries, HistoryBatch):
-            hist = queries.csr(with_values=False)
-        else:
-            hist = self._query_csr(queries)
-        B = hist.shape[0]
-        n = int(n)
-        cols = len(self.items) if n < 0 else n
-        oi = torch.full((B, cols), -1, dtype=torch.int32, device=w.indices.device)
-        osc = torch.full((B, cols), float("nan"), dtype=torch.float32, device=w.indices.device)
-        step = self._panel_rows()
-        for lo in range(0, B, step):
-            hi = min(B, lo + step)
-            panel = D.slim_score_batch(hist.indptr, hist.indices, w, rows=(lo, hi),
-                                       strike_history=exclude_history, nan_empty=True)
-            idx = D.argtopn(panel, n)
-            oi[lo:hi, :idx.shape[1]] = idx
-            osc[lo:hi, :idx.shape[1]] = D.take_scores(panel, idx)
-        return D.lists_to_host(oi, osc)
+        # no / empty history: every score NaN, told by the row's length (slim.py:125-130)
+        return self._score_lists(hist, item_lists, nan_empty=False)
 
 
 # ---------------------------------------------------------------------------------------
@@ -675,7 +706,7 @@ class AssociationConfig(BaseModel, extra="forbid"):
     "``None``: the mean over the reference items; 1: the maximum.  Other values are not offered."
 
 
-class AssociationScorer(Component):
+class AssociationScorer(_PanelScorer, Component):
     """
     Association rules between items (``AssociationScorer``, src/lenskit/knn/association.py:59-163):
     conditional probability ``P[c|r]``, lift, and -- with ``damping`` -- biased lift, from the
@@ -685,7 +716,7 @@ class AssociationScorer(Component):
     the matrix; scoring reduces the reference items' rows by mean or max for whole batches of
     queries (``lk_assoc_score_batch``: a cell's additions in reference-item order, as ``np.mean``
     over the reference's dense rows), and ``recommend_batch`` selects the lists from bounded panels
-    with ``lk_argtopn``.  The learned state stays on the host: ``items``, ``item_freqs`` and
+    (:class:`_PanelScorer`).  The learned state stays on the host: ``items``, ``item_freqs`` and
     ``assoc_scores`` (SciPy CSR, reference items on rows, target items on columns).
     """
 
@@ -695,24 +726,14 @@ class AssociationScorer(Component):
     item_freqs: np.ndarray
     assoc_scores: sps.csr_array
 
-    PANEL_BYTES = 1 << 30  # score panel of one recommend / score step
-
     def is_trained(self) -> bool:
         return hasattr(self, "assoc_scores")
 
     def train(self, data: Dataset, options: TrainingOptions = TrainingOptions()):
         "association.py:91-130"
         n_items = data.item_count
-        ui = data.interactions().matrix().scipy(attribute=None).astype(np.float32)
-        ui = sps.csr_array(ui)
+        cooc, ui, _iu, d = _binary_cooccurrence(data)
         n_groups = ui.shape[0]  # the matrix's rows, not user_count: there might be sessions (99)
-        ui.sum_duplicates()
-        ui.data[:] = 1.0  # co-occurrences count (user, item) pairs once
-        ui.sort_indices()
-        iu = sps.csr_array(ui.T)
-        iu.sort_indices()
-        d = D.device()
-        cooc = D.iknn_build(D.DeviceCSR.from_scipy(ui, d), D.DeviceCSR.from_scipy(iu, d), 0.5)
         # the marginals count interaction RECORDS (item_stats, association.py:113)
         item_counts = np.ascontiguousarray(data.item_stats()["count"].values, dtype=np.int32)
         D.assoc_scale(cooc, torch.from_numpy(item_counts).to(d), n_groups, self.config.method,
@@ -733,13 +754,12 @@ class AssociationScorer(Component):
         def upload():
             s = self.assoc_scores
             s.sort_indices()
-            d = D.device()
-            return D.DeviceCSR(torch.from_numpy(np.array(s.indptr, dtype=np.int64)).to(d),
-                               torch.from_numpy(np.array(s.indices, dtype=np.int32)).to(d),
-                               torch.from_numpy(np.array(s.data, dtype=np.float32)).to(d),
-                               (int(s.shape[0]), int(s.shape[1])), None)
+            return D.DeviceCSR.from_host(s.indptr, s.indices, s.data, s.shape, D.device())
 
         return self._device_cache("assoc_scores", upload, self.assoc_scores)
+
+    def _device_matrix(self) -> D.DeviceCSR:
+        return self._device_scores()
 
     def _reduction(self) -> str:
         if self.config.max_nbrs is None:
@@ -748,77 +768,26 @@ class AssociationScorer(Component):
             return "max"
         raise NotImplementedError("limited reference items not yet implemented")  # 155
 
-    def _panel_rows(self) -> int:
-        return max(1, self.PANEL_BYTES // (4 * max(len(self.items), 1)))
-
-    def _query_csr(self, queries: list[RecQuery]) -> D.DeviceCSR:
-        "The reference items of a list of queries in query order, uploaded: -1 = unknown item."
-        ptr, idx, _ = pack_histories(queries, self.items, unknown="keep")
-        return D.DeviceCSR.from_arrays(ptr, idx, None, (len(queries), len(self.items)),
-                                       self._device_scores().indices.device)
+    def _score_panel(self, hist, rows, *, strike_history, nan_empty, reduce=None):
+        return D.assoc_score_batch(hist.indptr, hist.indices, self._device_matrix(),
+                                   reduce or self._reduction(), rows=rows,
+                                   strike_history=strike_history, nan_empty=nan_empty)
 
     def score_batch(self, queries, item_lists) -> list[ItemList]:
         "Scores for a batch of (query, items) pairs (association.py:132-163 per pair)."
-        s = self._device_scores()
         hist = self._query_csr([RecQuery.create(q) for q in queries])
         if hist.nnz and bool((hist.indices >= 0).any()):
             reduce = self._reduction()  # (the reference raises once it has reference items)
         else:
             reduce = "mean"
-        out = []
-        step = self._panel_rows()
-        for lo in range(0, len(item_lists), step):
-            hi = min(len(item_lists), lo + step)
-            # a query without a known reference item: every score NaN (association.py:144-146)
-            panel = D.to_host(D.assoc_score_batch(hist.indptr, hist.indices, s, reduce,
-                                                  rows=(lo, hi), nan_empty=True))
-            for i in range(lo, hi):
-                items = item_lists[i]
-                out.append(ItemList(items, scores=item_scores(items, self.items, panel[i - lo])))
-        return out
-
-    def __call__(self, query, items: ItemList) -> ItemList:
-        return self.score_batch([query], [items])[0]
-
-    # -- top-n --------------------------------------------------------------------------------
-    accepts_history_batch = True  # recommend_batch takes a lkpy_amd.basic.HistoryBatch
-
-    def _batch_csr(self, queries) -> D.DeviceCSR:
-        "The reference items of a batch as a device CSR: a HistoryBatch's training rows, or a list's"
-        queries = resolve_queries(queries, self.items)
-        if isinstance(queries, HistoryBatch):
-            return queries.csr(with_values=False)
-        return self._query_csr(queries)
+        # a query without a known reference item: every score NaN (association.py:144-146)
+        return self._score_lists(hist, item_lists, nan_empty=True,
+                                 score_panel=partial(self._score_panel, reduce=reduce))
 
     def recommend_batch(self, queries, n: int | None, *, exclude_history: bool = True):
-        """
-        Top-``n`` lists for many queries at once -- what the ``recommender`` pipeline of
-        ``biased-lift.toml`` computes one query at a time: candidates = every training item minus
-        the query's own (src/lenskit/basic/candidates.py:77-94), this scorer over them,
-        ``TopNRanker`` (basic/topn.py:45-69).  Items no reference item is associated with score
-        0.0 and are listed when fewer than ``n`` score above it; a query without a known reference
-        item gets an empty list.  ``queries``: a list of queries, or a
-        :class:`lkpy_amd.basic.HistoryBatch`.  The batch goes through in panels of at most
-        ``PANEL_BYTES``.  ``n = None``: every candidate, ranked.  Returns (item numbers [B x n]
-        with -1 padding, scores [B x n] with NaN padding), like ``SLIMScorer.recommend_batch``.
-        """
-        reduce = self._reduction()
-        hist = self._batch_csr(queries)
-        s = self._device_scores()
-        B = hist.shape[0]
-        n = -1 if n is None else int(n)
-        cols = len(self.items) if n < 0 else n
-        oi = torch.full((B, cols), -1, dtype=torch.int32, device=s.indices.device)
-        osc = torch.full((B, cols), float("nan"), dtype=torch.float32, device=s.indices.device)
-        step = self._panel_rows()
-        for lo in range(0, B, step):
-            hi = min(B, lo + step)
-            panel = D.assoc_score_batch(hist.indptr, hist.indices, s, reduce, rows=(lo, hi),
-                                        strike_history=exclude_history, nan_empty=True)
-            idx = D.argtopn(panel, n)
-            oi[lo:hi, :idx.shape[1]] = idx
-            osc[lo:hi, :idx.shape[1]] = D.take_scores(panel, idx)
-        return D.lists_to_host(oi, osc)
+        "``_PanelScorer.recommend_batch`` (the pipeline of ``biased-lift.toml``) by mean or max."
+        self._reduction()  # (an unsupported max_nbrs is refused before anything is uploaded)
+        return super().recommend_batch(queries, n, exclude_history=exclude_history)
 
     def dense_scores_batch(self, queries):
         """
@@ -827,16 +796,14 @@ class AssociationScorer(Component):
         query without a known reference item is NaN (``valid`` False); the history CSR (known
         items, ascending) is for the caller to exclude.  The caller bounds the batch.
         """
-        reduce = self._reduction()
+        self._reduction()  # (as in recommend_batch)
         queries = resolve_queries(queries, self.items)
-        s = self._device_scores()
         if isinstance(queries, HistoryBatch):
             hist = excl = queries.csr(with_values=False)  # training rows: known items, ascending
             valid = queries.lengths > 0
         else:
             hist = self._query_csr(queries)
             ptr, idx, _ = pack_histories(queries, self.items, unknown="drop", sort=True)
-            excl = D.DeviceCSR.from_arrays(ptr, idx, None, hist.shape, s.indices.device)
+            excl = D.DeviceCSR.from_arrays(ptr, idx, None, hist.shape, hist.indices.device)
             valid = np.diff(ptr) > 0
-        panel = D.assoc_score_batch(hist.indptr, hist.indices, s, reduce, nan_empty=True)
-        return panel, valid, excl
+        return self._score_panel(hist, None, strike_history=False, nan_empty=True), valid, excl

@@ -332,6 +332,50 @@ def test_recommend_through_biased_lift_toml(gpu, oracle, ml_ds, ml_counts):
             assert len(il) == n and len(set(il.ids())) == n and not np.isin(il.ids(), own).any()
 
 
+def test_score_batch_small_panels_equal_one_panel(gpu, monkeypatch, ml_ds, ml_lift20):
+    """``score_batch`` through panels of 7 queries -- 8 of 7 and one of 6, the query without
+    history in the last -- gives one panel's scores bit for bit: 62 queries, 40 targets each, one
+    of them unknown."""
+    from lkpy_amd import _device as D
+    from lkpy_amd.basic import UserTrainingHistoryLookup
+    from lkpy_amd.data import ItemList, RecQuery
+    from lkpy_amd.knn import AssociationScorer
+
+    scorer, _s = ml_lift20
+    lookup = UserTrainingHistoryLookup()
+    lookup.train(ml_ds)
+    users = list(ml_ds.users.ids()[:60]) + [int(ml_ds.users.ids()[-1]), -7]  # the last one unknown
+    queries = [lookup(RecQuery.create(u)) for u in users]
+    ids = ml_ds.items.ids()
+    n_items = len(ids)
+    rng = np.random.default_rng(11)
+    lists, unknown_at = [], []
+    for _ in users:
+        unknown_at.append(int(rng.integers(0, 40)))
+        lists.append(ItemList(item_ids=np.insert(rng.choice(ids, 39, replace=False),
+                                                 unknown_at[-1], 10 ** 9)))
+    assert len(queries) == 62 and scorer._panel_rows() >= 62
+    one = scorer.score_batch(queries, lists)
+    launched, score = [], D.assoc_score_batch
+    with monkeypatch.context() as m:
+        m.setattr(D, "assoc_score_batch",
+                  lambda *a, **k: (launched.append(k.get("rows")), score(*a, **k))[1])
+        m.setattr(AssociationScorer, "PANEL_BYTES", 4 * n_items * 7)  # panels of 7 queries
+        small = scorer.score_batch(queries, lists)
+    assert launched == [(lo, min(62, lo + 7)) for lo in range(0, 62, 7)] and len(launched) == 9
+    assert [hi - lo for lo, hi in launched] == [7] * 8 + [6] and launched[-1] == (56, 62)
+    assert len(one) == len(small) == 62
+    finite = 0
+    for a, b, il, at in zip(one, small, lists, unknown_at):
+        assert np.array_equal(a.ids(), il.ids()) and np.array_equal(b.ids(), il.ids())
+        sa, sb = np.asarray(a.scores(), np.float32), np.asarray(b.scores(), np.float32)
+        assert sa.shape == (40,) and np.array_equal(_bits(sa), _bits(sb))
+        assert np.isnan(sb[at])  # the unknown target
+        finite += int(np.isfinite(sb).sum())
+    assert np.isnan(np.asarray(small[-1].scores())).all()  # no reference items: every score NaN
+    assert finite == 61 * 39  # every known target of a query with reference items has a score
+
+
 def _small_dataset(seed, n_users, n_items):
     from lkpy_amd.data import Dataset
 

@@ -2,7 +2,8 @@
 import numpy as np
 import pytest
 
-from lkpy_amd._queries import item_scores, pack_histories, resolve_queries, user_numbers
+from lkpy_amd._queries import (item_scores, pack_histories, pack_targets, resolve_queries,
+                               user_numbers)
 from lkpy_amd.basic import HistoryBatch
 from lkpy_amd.data import ItemList, RecQuery, Vocabulary
 
@@ -141,6 +142,39 @@ def test_item_scores():
     assert np.array_equal(got, np.array([1.0, np.nan, 0.25, 1.0], np.float32), equal_nan=True)
     got = item_scores(ItemList(np.zeros(0, np.int64)), ITEMS, row)
     assert got.dtype == np.float32 and got.shape == (0,)
+
+
+def test_pack_targets():
+    ptr, nums = pack_targets([], ITEMS)
+    assert ptr.dtype == np.int64 and ptr.tolist() == [0]
+    assert nums.dtype == np.int32 and nums.shape == (0,)
+    empty = ItemList(np.zeros(0, np.int64))
+    ptr, nums = pack_targets([empty, empty], ITEMS)
+    assert ptr.tolist() == [0, 0, 0] and nums.dtype == np.int32 and nums.shape == (0,)
+    # an empty list between two others; an unknown id in its place; a repeat kept; list order kept
+    lists = [ItemList([40, 999, 10]), empty, ItemList([20, 20, 30]),
+             ItemList(item_nums=[3, 0], vocabulary=ITEMS)]
+    ptr, nums = pack_targets(lists, ITEMS)
+    assert ptr.dtype == np.int64 and ptr.tolist() == [0, 3, 3, 6, 8]
+    assert nums.dtype == np.int32 and nums.tolist() == [3, -1, 0, 1, 1, 2, 3, 0]
+    assert nums.flags.c_contiguous and nums.flags.writeable  # (what torch.from_numpy takes)
+
+
+def test_pack_targets_equals_the_per_list_lookup():
+    rng = np.random.default_rng(5)
+    vocab = Vocabulary(rng.permutation(np.arange(100, 130)))  # 30 items, numbered out of id order
+    lists = [ItemList(rng.integers(95, 135, size=rng.integers(0, 12)))  # unknown ids, repeats
+             for _ in range(50)]
+    assert any(len(il) == 0 for il in lists)
+    per_list = [il.numbers(vocabulary=vocab, missing="negative") for il in lists]
+    assert any((p < 0).any() for p in per_list)
+    assert any(len(np.unique(p)) < len(p) for p in per_list)
+    ptr, nums = pack_targets(lists, vocab)
+    assert ptr.dtype == np.int64 and nums.dtype == np.int32
+    assert ptr.tolist() == np.concatenate([[0], np.cumsum([len(p) for p in per_list])]).tolist()
+    assert np.array_equal(nums, np.concatenate(per_list))
+    for i, p in enumerate(per_list):
+        assert np.array_equal(nums[ptr[i]:ptr[i + 1]], p)
 
 
 def test_resolve_queries():
