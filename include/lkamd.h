@@ -238,6 +238,31 @@ int lk_als_implicit_half_epoch(const lk_als_plan *plan, const void *d_indptr,
                                int64_t n_cols, int32_t k, float *d_this, int32_t ld_this,
                                const float *d_other, int32_t ld_other, const float *d_otor,
                                int32_t ld_otor, void *d_ws, float *d_out_frob, void *stream);
+/* One whole implicit epoch -- user half, P^T P + item_reg I, item half, Q^T Q + user_reg I -- in one
+ * call, with the two halves' small kernels scheduled off the critical path:
+ * the Gramian of the new P and the item half's primed copy of it run on the user plan's side
+ * stream under the item half's chunk kernel, and the long rows of each half are solved on that
+ * half's side stream right behind their slab sums.  Results are bit for bit those of
+ *   lk_als_implicit_half_epoch(user) ; lk_gramian(P) ; lk_als_implicit_half_epoch(item) ; lk_gramian(Q).
+ * Serves what the flagship runs and nothing else: two DIFFERENT plans with the same k, padded
+ * k <= 64, the exact solver, LK_ALS_PLAN_HYBRID_ORDER, no task-control block, one device
+ * (LK_E_INVALID otherwise: use the calls above).  P [user rows x lk_padded_dim(k)] and Q are
+ * updated in place; d_qtq holds Q^T Q + user_reg I (ld_qtq >= k) on entry and the new one on
+ * return, d_ptp receives P^T P + item_reg I; d_gram_ws is lk_gramian_workspace_bytes(k) bytes;
+ * d_out_delta[0] = |dP|, d_out_delta[1] = |dQ| (written directly: no copy).  Both status words
+ * are read with lk_als_check_status as before.  When the call returns, everything it enqueued --
+ * on the plans' side streams too -- is ordered before whatever `stream` receives next.
+ * (The half-epoch calls at padded k <= 64 share the launch code: without a task-control block
+ * their long-row solve launch -- hybrid and strict reference-order plans, implicit and explicit
+ * model -- now also runs on the plan's side stream behind the slab sums, joined before the
+ * delta reduction.  Same kernels, same results, same ordering guarantee on `stream`.) */
+int lk_als_implicit_epoch(const lk_als_plan *user_plan, const lk_als_plan *item_plan,
+                          const void *d_u_indptr, const int32_t *d_u_indices,
+                          const float *d_u_values, const void *d_i_indptr,
+                          const int32_t *d_i_indices, const float *d_i_values, int32_t k,
+                          float *d_p, float *d_q, float *d_qtq, int32_t ld_qtq, float user_reg,
+                          float *d_ptp, int32_t ld_ptp, float item_reg, void *d_user_ws,
+                          void *d_item_ws, void *d_gram_ws, float *d_out_delta, void *stream);
 /* Explicit-feedback (biased-MF) half-epoch: replaces `_accel.als.train_explicit_matrix(matrix,
  * this, other, reg)` (src/lenskit/_accel/als.pyi, src/accel/als/explicit.rs:33-119):
  *   A = sum_j q_j q_j^T + reg * n * I,  A x = sum_j r_j q_j   (r = bias-normalised ratings),

@@ -706,6 +706,7 @@ class ImplicitALSEngine:
 
         self._nu, self._ni = nu, ni
         self._qtq = None
+        self._ptp = None  # P^T P + item_reg I of the native epoch call (_train_epoch_native)
         # LK_ALS_Z=sharded: the Woodbury operand Z formed once across the ranks.  Whether a half
         # takes it is decided for ALL ranks together (a rank whose own rows need no Z still owes
         # the others its share of the rows): one small all-reduce at set-up
@@ -820,6 +821,8 @@ class ImplicitALSEngine:
             di = self._delta(ds)
             self.epochs_trained += 1
             return du, di
+        if self._native_epoch():
+            return self._train_epoch_native()
         # user half: previous Q (src/lenskit/als/_common.py:251)
         ds, hs = self._half(self.u_plans, self.u_blocks, self.u_supers, self.P, self.Q, self._qtq)
         ptp, du = self._gramian_and_delta(self.P, self.u_blocks, self.item_reg, ds, hs)
@@ -830,6 +833,31 @@ class ImplicitALSEngine:
         self._qtq, di = self._gramian_and_delta(self.Q, self.i_blocks, self.user_reg, ds, hs)
         self.epochs_trained += 1
         return du, di
+
+    def _native_epoch(self) -> bool:
+        """
+        Does the whole epoch go through ``lk_als_implicit_epoch``?  One device, no collectives,
+        one plan per side, and plans the call serves (hybrid order, exact solver, padded k <= 64,
+        no task-control block); everything else keeps the per-half calls.
+        """
+        D = getattr(self.backend, "D", None)
+        return (D is not None and hasattr(D, "als_implicit_epoch") and not self.collective
+                and not self._zs and len(self.u_plans) == 1 and len(self.i_plans) == 1
+                and isinstance(self._qtq, torch.Tensor) and self._qtq.is_cuda
+                and D.epoch_plans_ok(self.u_plan, self.i_plan))
+
+    def _train_epoch_native(self):
+        b = self.backend
+        # the engine's own Gramian is updated in place (nobody else holds it: otor() copies);
+        # the deltas are a fresh pair per epoch -- a caller may keep those of several epochs
+        qtq = self._qtq
+        if self._ptp is None or self._ptp.shape != qtq.shape:
+            self._ptp = torch.empty_like(qtq)
+        delta = torch.empty(2, dtype=torch.float32, device=qtq.device)
+        b.D.als_implicit_epoch(self.u_plan, self.i_plan, self.P, self.Q, qtq, self.user_reg,
+                               self._ptp, self.item_reg, b._gram, delta)
+        self.epochs_trained += 1
+        return delta[0], delta[1]
 
     def _gramian_and_delta(self, full: torch.Tensor, blocks, reg: float, ds, handles):
         """

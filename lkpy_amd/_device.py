@@ -535,6 +535,41 @@ class ALSPlan:
             pass
 
 
+def epoch_plans_ok(u_plan, i_plan) -> bool:
+    "Can ``lk_als_implicit_epoch`` run these two plans (include/lkamd.h)?  Else: the half-epoch calls."
+    return all(
+        isinstance(p, ALSPlan) and p.order_mode == "auto" and p.kp <= 64
+        and p.solver == _native.SOLVER_CHOLESKY and getattr(p, "_ctl", None) is None
+        for p in (u_plan, i_plan)
+    ) and u_plan is not i_plan and u_plan.k == i_plan.k
+
+
+def als_implicit_epoch(u_plan: "ALSPlan", i_plan: "ALSPlan", P: torch.Tensor, Q: torch.Tensor,
+                       qtq: torch.Tensor, user_reg: float, ptp: torch.Tensor, item_reg: float,
+                       gram: Gramian, out_delta: torch.Tensor):
+    """
+    One implicit epoch on the current stream (lk_als_implicit_epoch): ``P`` and ``Q`` updated in
+    place, ``qtq`` (Q^T Q + user_reg I) in and out, ``ptp`` out, ``out_delta`` = (|dP|, |dQ|).
+    Asynchronous; everything is ordered on the current stream when it returns.
+    """
+    uc, ic = u_plan.csr, i_plan.csr
+    kp = u_plan.kp
+    assert P.shape == (uc.shape[0], kp) and Q.shape == (ic.shape[0], kp)
+    assert uc.shape[1] == ic.shape[0] and ic.shape[1] == uc.shape[0]
+    assert P.is_contiguous() and Q.is_contiguous() and qtq.is_contiguous() and ptp.is_contiguous()
+    assert qtq.shape == (u_plan.k, u_plan.k) == ptp.shape and gram.k == u_plan.k
+    assert out_delta.numel() == 2 and out_delta.dtype == torch.float32
+    check(
+        _native.load().lk_als_implicit_epoch(
+            u_plan._h, i_plan._h, _ptr(uc.indptr), _ptr(uc.indices), _ptr(uc.values),
+            _ptr(ic.indptr), _ptr(ic.indices), _ptr(ic.values), u_plan.k, _ptr(P), _ptr(Q),
+            _ptr(qtq), qtq.stride(0), float(user_reg), _ptr(ptp), ptp.stride(0), float(item_reg),
+            _ptr(u_plan.ws), _ptr(i_plan.ws), _ptr(gram.ws), _ptr(out_delta), _stream()
+        ),
+        "lk_als_implicit_epoch",
+    )  # fmt: skip
+
+
 class ShardedZ:
     """
     Z = other @ OtOr^-1 (the Woodbury kernels' operand at padded k = 128 / 256) formed ONCE ACROSS

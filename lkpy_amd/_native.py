@@ -115,6 +115,11 @@ def _declare(lib):
             [vp, vp, vp, vp, c_int64, c_int64, c_int32, vp, c_int32, vp, c_int32, vp, c_int32, vp,
              vp, vp],
         ),
+        "lk_als_implicit_epoch": (
+            c_int,
+            [vp, vp, vp, vp, vp, vp, vp, vp, c_int32, vp, vp, vp, c_int32, c_float, vp, c_int32,
+             c_float, vp, vp, vp, vp, vp],
+        ),
         "lk_als_explicit_half_epoch": (
             c_int,
             [vp, vp, vp, vp, c_int64, c_int64, c_int32, vp, c_int32, vp, c_int32, c_float, vp, vp,

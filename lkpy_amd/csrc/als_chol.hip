@@ -34,6 +34,7 @@
 
 #include "als_plan.h"
 #include "common.h"
+#include "delta_reduce.h"
 
 #ifndef LK_ALS_RING
 #define LK_ALS_RING 4  // gather ring slots (8 costs 20 more registers: no gain at 3 waves/SIMD)
@@ -1282,38 +1283,20 @@ __global__ void als_prep_otor_kernel(const float *__restrict__ otor, int ld_otor
     otor_p[idx] = v;
 }
 
-// deterministic two-stage sum of row deltas -> sqrt
+// deterministic two-stage sum of row deltas -> sqrt (the loops live in delta_reduce.h: the fused
+// tail kernels of gramian.hip run the same ones)
 __global__ void delta_partial_kernel(const float *__restrict__ row_delta, int64_t n,
                                      float *__restrict__ partial)
 {
     __shared__ float sm[256];
-    const int64_t per = (n + gridDim.x - 1) / gridDim.x;
-    int64_t b = (int64_t)blockIdx.x * per, e = b + per;
-    if (e > n) e = n;
-    float s = 0.f;
-    for (int64_t i = b + threadIdx.x; i < e; i += 256) s += row_delta[i];
-    sm[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = sm[0];
+    delta_partial_body(row_delta, n, (int)gridDim.x, (int)blockIdx.x, sm, partial);
 }
 
 __global__ void delta_final_kernel(const float *__restrict__ partial, int n,
                                    float *__restrict__ out)
 {
     __shared__ float sm[256];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) s += partial[i];
-    sm[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = sqrtf(sm[0]);
+    delta_final_body(partial, n, sm, out);
 }
 
 constexpr int DELTA_BLOCKS = LK_DELTA_BLOCKS;
@@ -1329,43 +1312,88 @@ int launch_delta_reduce(const float *row_delta, int64_t n_rows, float *partial, 
     return LK_OK;
 }
 
-template <int NT, bool IS64, bool EXPL = false>
-static int launch_chol(const lk_als_plan *p, const void *indptr, const int32_t *indices,
-                       const float *values, int64_t n_rows, int k, float *this_, int ld_this,
-                       const float *other, int ld_other, const float *otor, int ld_otor,
-                       char *ws, float *out_frob, hipStream_t st, float reg = 0.f)
+// One half-epoch in the parts its schedule is made of (launch_chol below runs them one after the
+// other; als_chol_epoch interleaves the two halves of an epoch):
+//   prep   status word zeroed, OtOr primed and padded into the workspace (launch stream)
+//   front  reads only `other`: chunk kernel, reference-order chains, ordered slab sums
+//   solve  reads the primed OtOr: the short rows on the launch stream, the long rows (the rows of
+//          the chains) on the side stream right behind their slab sums, then the join
+//   tail   the delta reduction (launch_delta_reduce), or gramian_tail (gramian.hip) in an epoch
+template <int NT, bool IS64, bool EXPL>
+struct CholKind {};  // the kernels' template arguments as a value (chol_dispatch)
+
+struct CholHalf {
+    const lk_als_plan *p;
+    const void *indptr;
+    bool is64;  // width of the CSR offsets at `indptr`
+    const int32_t *indices;
+    const float *values;
+    int64_t n_rows;
+    int k;
+    float *this_;
+    int ld_this;
+    const float *other;
+    int ld_other;
+    char *ws;
+    float reg;
+    hipStream_t st;
+    // set by the front
+    hipStream_t sr = nullptr;  // the stream of the chains (st: no fork)
+    int64_t n_solve = 0, n_y = 0;
+    float *yref = nullptr;
+    bool tm = false;
+    bool forked = false;
+
+    int *status() const { return reinterpret_cast<int *>(ws + p->off_status); }
+    float *otor_p() const { return reinterpret_cast<float *>(ws + p->off_otor); }
+    float *row_delta() const { return reinterpret_cast<float *>(ws + p->off_delta); }
+    float *partial() const { return reinterpret_cast<float *>(ws + p->off_partial); }
+    float *slabs() const { return reinterpret_cast<float *>(ws + p->off_slabs); }
+    // every join happens on every path: whoever leaves between fork and join (an error return)
+    // still makes the launch stream wait for the side stream -- the caller frees the workspaces
+    ~CholHalf()
+    {
+        if (forked) (void)plan_join_rhs(p, st);
+    }
+};
+
+template <int NT, bool IS64, bool EXPL>
+static int chol_prep(CholHalf &h, CholKind<NT, IS64, EXPL>, const float *otor, int ld_otor)
 {
     constexpr int KP = NT * 16;
-    int *status = reinterpret_cast<int *>(ws + p->off_status);
-    float *otor_p = reinterpret_cast<float *>(ws + p->off_otor);
-    float *row_delta = reinterpret_cast<float *>(ws + p->off_delta);
-    float *partial = reinterpret_cast<float *>(ws + p->off_partial);
-    float *slabs = reinterpret_cast<float *>(ws + p->off_slabs);
-
+    const lk_als_plan *p = h.p;
     LK_REQUIRE(!p->ref_order || (p->d_yref && !p->ctl),
                "a reference-order ALS plan needs its rhs workspace (lk_als_plan_set_rhs_workspace) "
                "and no task-control block");
-    LK_HIP_CHECK(hipMemsetAsync(status, 0, 64, st));
+    LK_HIP_CHECK(hipMemsetAsync(h.status(), 0, 64, h.st));
     if (p->ctl) {
         // a cancelled half-epoch leaves the rows not yet started untouched; their deltas
         // must not be garbage in the (discarded) sum
-        LK_HIP_CHECK(hipMemsetAsync(row_delta, 0, (size_t)n_rows * sizeof(float), st));
-        int rc = ctl_begin(p->ctl, n_rows, n_rows, st);
+        LK_HIP_CHECK(hipMemsetAsync(h.row_delta(), 0, (size_t)h.n_rows * sizeof(float), h.st));
+        int rc = ctl_begin(p->ctl, h.n_rows, h.n_rows, h.st);
         if (rc != LK_OK) return rc;
     }
-    hipLaunchKernelGGL(als_prep_otor_kernel<NT>, dim3((KP * KP + 255) / 256), dim3(256), 0, st,
-                       otor, ld_otor, k, otor_p);
-    const bool tm = p->timing && p->timing_n < lk_als_plan::TIMING_RING;
-    if (tm) LK_HIP_CHECK(hipEventRecord(p->ev[p->timing_n][0], st));
+    hipLaunchKernelGGL(als_prep_otor_kernel<NT>, dim3((KP * KP + 255) / 256), dim3(256), 0, h.st,
+                       otor, ld_otor, h.k, h.otor_p());
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
+template <int NT, bool IS64, bool EXPL>
+static int chol_front(CholHalf &h, CholKind<NT, IS64, EXPL>)
+{
+    const lk_als_plan *p = h.p;
+    hipStream_t st = h.st;
+    float *slabs = h.slabs();
+    h.tm = p->timing && p->timing_n < lk_als_plan::TIMING_RING;
+    if (h.tm) LK_HIP_CHECK(hipEventRecord(p->ev[p->timing_n][0], st));
     // (CG hybrid: only the chunked rows, the first dense_limit tasks of the order)
-    const int64_t n_solve = p->dense_limit >= 0 && p->dense_limit < n_rows ? p->dense_limit : n_rows;
+    h.n_solve = p->dense_limit >= 0 && p->dense_limit < h.n_rows ? p->dense_limit : h.n_rows;
     // rows whose right-hand side comes from the reference-order chain (als_rhs.hip): the long
     // rows (the first n_long tasks) of a hybrid plan, every row of a strict reference-order plan
-    float *yref = p->hybrid ? reinterpret_cast<float *>(ws + p->off_yref)
-                            : (p->ctl ? nullptr : p->d_yref);
-    const int64_t n_y = !yref ? 0 : (p->hybrid ? std::min<int64_t>(p->n_long, n_solve) : n_solve);
-    const int ref_chunk = (p->ref_order || p->hybrid) ? p->chunk : 0;
-    using IT = typename IndPtr<IS64>::type;
+    h.yref = p->hybrid ? reinterpret_cast<float *>(h.ws + p->off_yref)
+                       : (p->ctl ? nullptr : p->d_yref);
+    h.n_y = !h.yref ? 0 : (p->hybrid ? std::min<int64_t>(p->n_long, h.n_solve) : h.n_solve);
     // The chains run on the plan's second stream, beside the chunk kernel and the solve of
     // the other rows; only the (small) solve launch of the long rows waits for them.  They are
     // ENQUEUED BEHIND the chunk kernel (the fork point is in front of it): the chain kernel is
@@ -1373,44 +1401,62 @@ static int launch_chol(const lk_als_plan *p, const void *indptr, const int32_t *
     // of workgroups and the MFMA-bound chunk kernel waits (measured: +0.25 ms per cfg2 item
     // half); enqueued second it trickles in as chunk workgroups retire and does most of its
     // work under the solve of the short rows.
-    hipStream_t sr = st;
-    if (n_y > 0) {
-        int rc = plan_fork_rhs(p, st, &sr);
+    h.sr = st;
+    if (h.n_y > 0) {
+        int rc = plan_fork_rhs(p, st, &h.sr);
         if (rc != LK_OK) return rc;
+        h.forked = h.sr != st;
     }
     if (p->n_chunks > 0) {
         hipLaunchKernelGGL((als_chunk_kernel<NT, EXPL>),
-                           dim3((unsigned)((p->n_chunks + 3) / 4)), dim3(256), 0, st, indices,
-                           values, p->d_chunk_beg, p->d_chunk_len, p->n_chunks, other,
-                           ld_other, slabs, p->d_chunk_slab,
+                           dim3((unsigned)((p->n_chunks + 3) / 4)), dim3(256), 0, st,
+                           h.indices, h.values, p->d_chunk_beg, p->d_chunk_len, p->n_chunks,
+                           h.other, h.ld_other, slabs, p->d_chunk_slab,
                            p->unit > p->chunk ? (int)p->chunk : 0);
     }
-    if (n_y > 0) {
-        int rc = launch_rhs_reference(p, indptr, IS64 ? 1 : 0, indices, values, p->d_order, n_y,
-                                      other, EXPL, yref, sr);
+    if (h.n_y > 0) {
+        int rc = launch_rhs_reference(p, h.indptr, IS64 ? 1 : 0, h.indices, h.values, p->d_order,
+                                      h.n_y, h.other, EXPL, h.yref, h.sr);
         if (rc != LK_OK) return rc;
     }
     if (p->n_chunks > 0) {
         // the ordered slab sums of reference-order rows are pure HBM streaming: on the second
         // stream (behind the chains) they run under the solve of the rows that need no slabs
         hipStream_t sg = st;
-        if (n_y > 0 && sr != st) {
+        if (h.forked) {
             int rc = plan_rhs_wait_main(p, st);
             if (rc != LK_OK) return rc;
-            sg = sr;
+            sg = h.sr;
         }
         int rc = launch_slab_group_reduce(p, slabs, slab_floats<NT>(), sg);
         if (rc != LK_OK) return rc;
     }
-    if (tm) LK_HIP_CHECK(hipEventRecord(p->ev[p->timing_n][1], st));
-    const IT *ip = static_cast<const IT *>(indptr);
-#define LK_SOLVE_LAUNCH(CTLV, YREFV, T0, NTASKS, YPTR)                                        \
-    LK_SOLVE_LAUNCH_S(CTLV, YREFV, false, T0, NTASKS, YPTR)
-#define LK_SOLVE_LAUNCH_S(CTLV, YREFV, SEQV, T0, NTASKS, YPTR)                                \
+    if (h.tm) LK_HIP_CHECK(hipEventRecord(p->ev[p->timing_n][1], st));
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
+// `otor_ready` (may be null): an event behind which the primed OtOr and the status word of the
+// workspace are valid; both streams of the solve wait for it
+template <int NT, bool IS64, bool EXPL>
+static int chol_solve(CholHalf &h, CholKind<NT, IS64, EXPL>, hipEvent_t otor_ready)
+{
+    const lk_als_plan *p = h.p;
+    hipStream_t st = h.st;
+    using IT = typename IndPtr<IS64>::type;
+    const IT *ip = static_cast<const IT *>(h.indptr);
+    const int ref_chunk = (p->ref_order || p->hybrid) ? p->chunk : 0;
+    const int64_t n_y = h.n_y, n_solve = h.n_solve;
+    float *yref = h.yref;
+    if (otor_ready) LK_HIP_CHECK(hipStreamWaitEvent(st, otor_ready, 0));
+#define LK_SOLVE_LAUNCH(CTLV, YREFV, T0, NTASKS, YPTR, STREAM)                                \
+    LK_SOLVE_LAUNCH_S(CTLV, YREFV, false, T0, NTASKS, YPTR, STREAM)
+#define LK_SOLVE_LAUNCH_S(CTLV, YREFV, SEQV, T0, NTASKS, YPTR, STREAM)                        \
     hipLaunchKernelGGL((als_solve_kernel<NT, IS64, EXPL, CTLV, YREFV, SEQV>),                  \
-                       dim3((unsigned)(((NTASKS) + 3) / 4)), dim3(256), 0, st, ip, indices,    \
-                       values, p->d_order + (T0), (NTASKS), p->d_row_slab, other, ld_other,    \
-                       this_, ld_this, otor_p, slabs, row_delta, status, k, reg,               \
+                       dim3((unsigned)(((NTASKS) + 3) / 4)), dim3(256), 0, (STREAM), ip,       \
+                       h.indices, h.values, p->d_order + (T0), (NTASKS), p->d_row_slab,        \
+                       h.other, h.ld_other, h.this_, h.ld_this, h.otor_p(), h.slabs(),         \
+                       h.row_delta(), h.status(), h.k, h.reg,                                  \
                        (CTLV) ? p->ctl->dev() : TaskCtlDev{}, (YPTR), ref_chunk)
     // the rows that take their own right-hand side first (longest-first inside the launch) ...
     // (hybrid / reference-order plans: these rows form y in the reference's order inside
@@ -1419,37 +1465,80 @@ static int launch_chol(const lk_als_plan *p, const void *indptr, const int32_t *
     if (n_solve > n_y) {
         if (p->ctl) {
             if (seqy)
-                LK_SOLVE_LAUNCH_S(true, false, true, n_y, n_solve - n_y, nullptr);
+                LK_SOLVE_LAUNCH_S(true, false, true, n_y, n_solve - n_y, nullptr, st);
             else
-                LK_SOLVE_LAUNCH(true, false, n_y, n_solve - n_y, nullptr);
+                LK_SOLVE_LAUNCH(true, false, n_y, n_solve - n_y, nullptr, st);
         } else {
             if (seqy)
-                LK_SOLVE_LAUNCH_S(false, false, true, n_y, n_solve - n_y, nullptr);
+                LK_SOLVE_LAUNCH_S(false, false, true, n_y, n_solve - n_y, nullptr, st);
             else
-                LK_SOLVE_LAUNCH(false, false, n_y, n_solve - n_y, nullptr);
+                LK_SOLVE_LAUNCH(false, false, n_y, n_solve - n_y, nullptr, st);
         }
     }
-    // ... then the rows of the chains (hybrid plans: the long rows -- one slab + one solve each)
+    // ... and the rows of the chains (hybrid plans: the long rows -- one slab + one solve each).
+    // Their launch is less than a round of workgroups and its inputs are complete on the side
+    // stream long before the short rows are through: it goes there, right behind the slab sums,
+    // and the launch stream joins once.  (With a task-control block the launch keeps its place
+    // behind the join: the progress count then still ends with the long rows.)
     if (n_y > 0) {
-        int rc = plan_join_rhs(p, st);
-        if (rc != LK_OK) return rc;
-        if (p->ctl)
-            LK_SOLVE_LAUNCH(true, true, 0, n_y, yref);
-        else
-            LK_SOLVE_LAUNCH(false, true, 0, n_y, yref);
+        if (p->ctl) {
+            h.forked = false;
+            int rc = plan_join_rhs(p, st);
+            if (rc != LK_OK) return rc;
+            LK_SOLVE_LAUNCH(true, true, 0, n_y, yref, st);
+        } else {
+            if (otor_ready && h.sr != st) LK_HIP_CHECK(hipStreamWaitEvent(h.sr, otor_ready, 0));
+            LK_SOLVE_LAUNCH(false, true, 0, n_y, yref, h.sr);
+            h.forked = false;
+            int rc = plan_join_rhs(p, st);
+            if (rc != LK_OK) return rc;
+        }
     }
 #undef LK_SOLVE_LAUNCH
 #undef LK_SOLVE_LAUNCH_S
-    if (tm) {
+    if (h.tm) {
         LK_HIP_CHECK(hipEventRecord(p->ev[p->timing_n][2], st));
         p->timing_n++;
     }
-    hipLaunchKernelGGL(delta_partial_kernel, dim3(DELTA_BLOCKS), dim3(256), 0, st, row_delta,
-                       n_rows, partial);
-    hipLaunchKernelGGL(delta_final_kernel, dim3(1), dim3(256), 0, st, partial, DELTA_BLOCKS,
-                       out_frob);
     LK_HIP_CHECK(hipGetLastError());
     return LK_OK;
+}
+
+// the phase `f` for the half's NT / offset width / model: f(CholKind<NT, IS64, EXPL>{})
+template <class F>
+static int chol_dispatch(const CholHalf &h, bool expl, F &&f)
+{
+    auto by_model = [&](auto nt, auto wide) {
+        constexpr int NT = decltype(nt)::value;
+        constexpr bool IS64 = decltype(wide)::value;
+        return expl ? f(CholKind<NT, IS64, true>{}) : f(CholKind<NT, IS64, false>{});
+    };
+    auto by_width = [&](auto nt) {
+        return h.is64 ? by_model(nt, std::true_type{}) : by_model(nt, std::false_type{});
+    };
+    switch (h.p->NT) {
+        case 1: return by_width(std::integral_constant<int, 1>{});
+        case 2: return by_width(std::integral_constant<int, 2>{});
+        case 4: return by_width(std::integral_constant<int, 4>{});
+    }
+    set_error("%s: no Cholesky kernel for padded k=%d",
+              expl ? "lk_als_explicit_half_epoch" : "lk_als_implicit_half_epoch", h.p->KP);
+    return LK_E_INVALID;
+}
+
+static int half_prep(CholHalf &h, bool expl, const float *otor, int ld_otor)
+{
+    return chol_dispatch(h, expl, [&](auto kind) { return chol_prep(h, kind, otor, ld_otor); });
+}
+
+static int half_front(CholHalf &h, bool expl)
+{
+    return chol_dispatch(h, expl, [&](auto kind) { return chol_front(h, kind); });
+}
+
+static int half_solve(CholHalf &h, bool expl, hipEvent_t otor_ready)
+{
+    return chol_dispatch(h, expl, [&](auto kind) { return chol_solve(h, kind, otor_ready); });
 }
 
 size_t als_chol_slab_floats(int NT) { return (size_t)(als_tiles(NT) * 4 + NT) * 64; }
@@ -1461,24 +1550,57 @@ int als_chol_half_epoch(const lk_als_plan *p, const void *indptr, int is64, cons
                         const float *other, int ld_other, const float *otor, int ld_otor, char *ws,
                         float *out_frob, hipStream_t st, bool expl, float reg)
 {
-#define LK_CHOL_ARGS p, indptr, indices, values, n_rows, k, this_, ld_this, other, ld_other, otor, ld_otor, ws, out_frob, st, reg
-#define LK_CHOL_CASE(NT)                                                                      \
-    do {                                                                                      \
-        if (expl)                                                                             \
-            return is64 ? launch_chol<NT, true, true>(LK_CHOL_ARGS)                           \
-                        : launch_chol<NT, false, true>(LK_CHOL_ARGS);                         \
-        return is64 ? launch_chol<NT, true>(LK_CHOL_ARGS) : launch_chol<NT, false>(LK_CHOL_ARGS); \
-    } while (0)
-    switch (p->NT) {
-        case 1: LK_CHOL_CASE(1);
-        case 2: LK_CHOL_CASE(2);
-        case 4: LK_CHOL_CASE(4);
+    CholHalf h{p, indptr, is64 != 0, indices, values, n_rows, k, this_, ld_this, other, ld_other, ws, reg, st};
+    int rc = half_prep(h, expl, otor, ld_otor);
+    if (rc == LK_OK) rc = half_front(h, expl);
+    if (rc == LK_OK) rc = half_solve(h, expl, nullptr);
+    if (rc != LK_OK) return rc;
+    return launch_delta_reduce(h.row_delta(), n_rows, h.partial(), out_frob, st);
+}
+
+// One implicit epoch, both halves in one schedule (lk_als_implicit_epoch, include/lkamd.h):
+//
+//   st:      prep U, front U (chunk U) -> solve-short U -> join side_U -> front I (chunk I)
+//            -> wait E_tailU -> solve-short I -> join side_I -> tail I
+//   side_U:  chains U -> slab sums U -> solve-long U ... then, behind the join point:
+//            tail U (delta U, Gramian(P), primed OtOr + status word of plan I) -> E_tailU
+//   side_I:  chains I -> slab sums I -> wait E_tailU -> solve-long I
+//
+// Front I reads only P: it does not wait for tail U, which runs under the item half's chunk
+// kernel; only the solve launches of the item half do.  Stream order only: no graph capture,
+// no flags between workgroups.  When the call returns, `st` holds everything.
+int als_chol_epoch(const lk_als_plan *pu, const lk_als_plan *pi, const void *u_indptr,
+                   const int32_t *u_indices, const float *u_values, const void *i_indptr,
+                   const int32_t *i_indices, const float *i_values, float *P, float *Q,
+                   float *qtq, int ld_qtq, float user_reg, float *ptp, int ld_ptp, float item_reg,
+                   char *ws_u, char *ws_i, float *gram_ws, float *out_delta, hipStream_t st)
+{
+    const int k = pu->k, KP = pu->KP;
+    CholHalf hu{pu, u_indptr, pu->is64 != 0, u_indices, u_values, pu->n_rows, k, P, KP, Q, KP, ws_u, 0.f, st};
+    CholHalf hi{pi, i_indptr, pi->is64 != 0, i_indices, i_values, pi->n_rows, k, Q, KP, P, KP, ws_i, 0.f, st};
+    int rc = half_prep(hu, false, qtq, ld_qtq);
+    if (rc == LK_OK) rc = half_front(hu, false);
+    if (rc == LK_OK) rc = half_solve(hu, false, nullptr);
+    if (rc != LK_OK) return rc;
+    // tail U on the user plan's side stream (idle by now), behind everything `st` holds
+    hipStream_t tu = st;
+    rc = plan_fork_rhs(pu, st, &tu);
+    if (rc != LK_OK) return rc;
+    hu.forked = tu != st;  // (joined through E_tailU below; by the destructor on an error)
+    rc = gramian_tail(P, pu->n_rows, k, KP, item_reg, ptp, ld_ptp, gram_ws, hu.row_delta(),
+                      hu.partial(), out_delta, hi.otor_p(), hi.status(), tu);
+    if (rc != LK_OK) return rc;
+    hipEvent_t tail_u = nullptr;
+    if (tu != st) {
+        LK_HIP_CHECK(hipEventRecord(pu->ev_tail_rhs, tu));
+        tail_u = pu->ev_tail_rhs;
     }
-#undef LK_CHOL_ARGS
-#undef LK_CHOL_CASE
-    set_error("%s: no Cholesky kernel for padded k=%d",
-              expl ? "lk_als_explicit_half_epoch" : "lk_als_implicit_half_epoch", p->KP);
-    return LK_E_INVALID;
+    rc = half_front(hi, false);
+    if (rc == LK_OK) rc = half_solve(hi, false, tail_u);
+    if (rc != LK_OK) return rc;
+    hu.forked = false;  // st has waited for E_tailU in half_solve
+    return gramian_tail(Q, pi->n_rows, k, KP, user_reg, qtq, ld_qtq, gram_ws, hi.row_delta(),
+                        hi.partial(), out_delta + 1, nullptr, nullptr, st);
 }
 
 }  // namespace lk

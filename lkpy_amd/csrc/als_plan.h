@@ -132,6 +132,9 @@ struct lk_als_plan {
     // launch of the long rows waits for them (plan_fork_rhs / plan_join_rhs)
     mutable hipStream_t side_rhs = nullptr;
     mutable hipEvent_t ev_fork_rhs = nullptr, ev_join_rhs = nullptr, ev_mid_rhs = nullptr;
+    // lk_als_implicit_epoch: recorded on the side stream behind the tail of the user half (the
+    // Gramian of the new P, primed into the item plan's workspace); the item half's solves wait
+    mutable hipEvent_t ev_tail_rhs = nullptr;
 };
 
 namespace lk {
@@ -202,4 +205,18 @@ int launch_slab_group_reduce(const lk_als_plan *p, float *slabs, size_t slab_flo
 // deterministic two-stage sum of the per-row squared deltas -> sqrt (als_chol.hip)
 int launch_delta_reduce(const float *row_delta, int64_t n_rows, float *partial, float *out_frob,
                         hipStream_t st);
+// The tail of a half-epoch of lk_als_implicit_epoch in two launches (gramian.hip; padded k <= 64):
+// out = m^T m + reg I exactly as lk_gramian forms it, *out_delta = sqrt(sum of row_delta[0 .. n))
+// exactly as launch_delta_reduce does, and -- next_otor_p / next_status not null -- the primed,
+// padded copy of `out` (als_prep_otor_kernel's) and a zeroed 64-byte status block for the half
+// that follows.
+int gramian_tail(const float *m, int64_t n, int k, int KP, float reg, float *out, int ld_out,
+                 float *gram_ws, const float *row_delta, float *partial, float *out_delta,
+                 float *next_otor_p, int *next_status, hipStream_t st);
+// one implicit epoch for two hybrid-order plans of padded k <= 64 (als_chol.hip)
+int als_chol_epoch(const lk_als_plan *pu, const lk_als_plan *pi, const void *u_indptr,
+                   const int32_t *u_indices, const float *u_values, const void *i_indptr,
+                   const int32_t *i_indices, const float *i_values, float *P, float *Q,
+                   float *qtq, int ld_qtq, float user_reg, float *ptp, int ld_ptp, float item_reg,
+                   char *ws_u, char *ws_i, float *gram_ws, float *out_delta, hipStream_t st);
 }  // namespace lk

@@ -11,6 +11,7 @@
 #include <strings.h>
 
 #include <algorithm>
+#include <initializer_list>
 #include <mutex>
 #include <vector>
 
@@ -30,6 +31,7 @@ int plan_fork_rhs(const lk_als_plan *p, hipStream_t st, hipStream_t *side)
         LK_HIP_CHECK(hipEventCreateWithFlags(&p->ev_fork_rhs, hipEventDisableTiming));
         LK_HIP_CHECK(hipEventCreateWithFlags(&p->ev_join_rhs, hipEventDisableTiming));
         LK_HIP_CHECK(hipEventCreateWithFlags(&p->ev_mid_rhs, hipEventDisableTiming));
+        LK_HIP_CHECK(hipEventCreateWithFlags(&p->ev_tail_rhs, hipEventDisableTiming));
     }
     LK_HIP_CHECK(hipEventRecord(p->ev_fork_rhs, st));
     LK_HIP_CHECK(hipStreamWaitEvent(p->side_rhs, p->ev_fork_rhs, 0));
@@ -491,6 +493,7 @@ extern "C" void lk_als_plan_destroy(lk_als_plan *p)
         (void)hipEventDestroy(p->ev_fork_rhs);
         (void)hipEventDestroy(p->ev_join_rhs);
         (void)hipEventDestroy(p->ev_mid_rhs);
+        (void)hipEventDestroy(p->ev_tail_rhs);
     }
     // (d_order ... d_chunk_len point into d_pack.)  Small schedule buffers go back to a per-device
     // pool instead of hipFree: a fold-in plan lives for one call, and hipMalloc + hipFree were a
@@ -629,6 +632,36 @@ extern "C" int lk_als_implicit_half_epoch(const lk_als_plan *plan, const void *d
     return lk::als_chol_half_epoch(plan, d_indptr, plan->is64, d_indices, d_values, n_rows, k,
                                    d_this, ld_this, d_other, ld_other, d_otor, ld_otor, ws,
                                    d_out_frob, st, false, 0.f);
+}
+
+extern "C" int lk_als_implicit_epoch(const lk_als_plan *user_plan, const lk_als_plan *item_plan,
+                                     const void *d_u_indptr, const int32_t *d_u_indices,
+                                     const float *d_u_values, const void *d_i_indptr,
+                                     const int32_t *d_i_indices, const float *d_i_values,
+                                     int32_t k, float *d_p, float *d_q, float *d_qtq,
+                                     int32_t ld_qtq, float user_reg, float *d_ptp, int32_t ld_ptp,
+                                     float item_reg, void *d_user_ws, void *d_item_ws,
+                                     void *d_gram_ws, float *d_out_delta, void *stream)
+{
+    LK_REQUIRE(user_plan && item_plan, "lk_als_implicit_epoch: null plan");
+    for (const lk_als_plan *p : {user_plan, item_plan})
+        LK_REQUIRE(p->k == k && p->KP <= 64 && p->solver == LK_SOLVER_CHOLESKY && p->hybrid &&
+                       !p->ctl && p->dense_limit < 0,
+                   "lk_als_implicit_epoch serves hybrid-order plans of the exact solver at padded "
+                   "k <= 64 without a task-control block (k=%d here); use the half-epoch calls",
+                   k);
+    LK_REQUIRE(user_plan != item_plan, "lk_als_implicit_epoch: one plan given twice");
+    LK_REQUIRE(ld_qtq >= k && ld_ptp >= k, "lk_als_implicit_epoch: Gramian leading dimension < k");
+    LK_REQUIRE(d_u_indptr && d_i_indptr && d_p && d_q && d_qtq && d_ptp && d_user_ws &&
+                   d_item_ws && d_gram_ws && d_out_delta,
+               "lk_als_implicit_epoch: null pointer");
+    LK_REQUIRE(d_user_ws != d_item_ws && d_qtq != d_ptp,
+               "lk_als_implicit_epoch: the two halves need buffers of their own");
+    return lk::als_chol_epoch(user_plan, item_plan, d_u_indptr, d_u_indices, d_u_values,
+                              d_i_indptr, d_i_indices, d_i_values, d_p, d_q, d_qtq, ld_qtq,
+                              user_reg, d_ptp, ld_ptp, item_reg, static_cast<char *>(d_user_ws),
+                              static_cast<char *>(d_item_ws), static_cast<float *>(d_gram_ws),
+                              d_out_delta, lk::as_stream(stream));
 }
 
 extern "C" int lk_als_explicit_half_epoch(const lk_als_plan *plan, const void *d_indptr,

@@ -23,6 +23,7 @@
 
 #include "als_plan.h"
 #include "common.h"
+#include "delta_reduce.h"
 
 namespace lk {
 
@@ -146,13 +147,27 @@ __device__ __forceinline__ void gram_wave(const float *__restrict__ m, int64_t r
     }
 }
 
-template <int NT>
+// TAIL (the half-epoch tail of lk_als_implicit_epoch, gramian_tail below): the first
+// LK_DELTA_BLOCKS workgroups also run delta_partial_kernel's loop over their slice of `row_delta`
+// (n entries, one per row of m) -- the grid then has at least that many workgroups, and those past
+// `gram_blocks` form no slab.
+template <int NT, bool TAIL = false>
 __global__ __launch_bounds__(256) void gramian_partial_kernel(const float *__restrict__ m,
                                                               int64_t n, int ld,
                                                               int64_t rows_per_block,
-                                                              float *__restrict__ ws)
+                                                              float *__restrict__ ws,
+                                                              int gram_blocks = 0,
+                                                              const float *__restrict__ row_delta = nullptr,
+                                                              float *__restrict__ delta_partial = nullptr)
 {
     constexpr int KP = NT * 16;
+    if constexpr (TAIL) {
+        if ((int)blockIdx.x < LK_DELTA_BLOCKS) {
+            __shared__ float sm[256];
+            delta_partial_body(row_delta, n, LK_DELTA_BLOCKS, (int)blockIdx.x, sm, delta_partial);
+        }
+        if ((int)blockIdx.x >= gram_blocks) return;
+    }
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int64_t row_beg = (int64_t)blockIdx.x * rows_per_block;
     int64_t row_end = row_beg + rows_per_block;
@@ -354,12 +369,29 @@ static bool gram_dma_enabled()
 // One workgroup per 64 consecutive primed elements (one coalesced 256-byte segment of
 // every slab); wave w sums slabs w, w+4, ...; the four partial sums are combined in
 // wave order.
-template <int NT>
+//
+// TAIL (gramian_tail below): every element the kernel settles also goes, in primed order and
+// with identity on the pad features, into `next_otor_p` -- what als_prep_otor_kernel would make
+// of `out` -- and ONE more workgroup (the last of the grid) finishes the delta sum
+// (delta_final_kernel's loop) and zeroes the 64-byte status block at `next_status`.
+template <int NT, bool TAIL = false>
 __global__ __launch_bounds__(256) void gramian_finish_kernel(const float *__restrict__ ws,
                                                              int nblocks, int k, float reg,
-                                                             float *__restrict__ out, int ld_out)
+                                                             float *__restrict__ out, int ld_out,
+                                                             const float *__restrict__ delta_partial = nullptr,
+                                                             float *__restrict__ out_delta = nullptr,
+                                                             float *__restrict__ next_otor_p = nullptr,
+                                                             int *__restrict__ next_status = nullptr)
 {
     constexpr int KP = NT * 16;
+    if constexpr (TAIL) {
+        if (blockIdx.x == gridDim.x - 1) {
+            __shared__ float sm[256];
+            delta_final_body(delta_partial, LK_DELTA_BLOCKS, sm, out_delta);
+            if (next_status && threadIdx.x < 16) next_status[threadIdx.x] = 0;
+            return;
+        }
+    }
     __shared__ double part[4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int idx = blockIdx.x * 64 + lane;
@@ -389,11 +421,19 @@ __global__ __launch_bounds__(256) void gramian_finish_kernel(const float *__rest
     if (wave != 0 || ti > tj) return;
     float s = (float)(((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane]);
     const int fr = (pr & 15) * NT + ti, fc = (pc & 15) * NT + tj;
-    if (fr >= k || fc >= k) return;
     // within a diagonal tile both (fr,fc) and (fc,fr) are present and bitwise equal
     // (a*b == b*a, same accumulation order), so taking fr <= fc is enough.
     if (ti == tj && fr > fc) return;
-    if (fr == fc) s += reg;
+    const bool pad = fr >= k || fc >= k;
+    if (!pad && fr == fc) s += reg;
+    if constexpr (TAIL) {
+        if (next_otor_p) {  // primed (pr, pc) <-> feature (fr, fc); its mirror is primed (pc, pr)
+            const float v = pad ? (pr == pc ? 1.0f : 0.0f) : s;
+            next_otor_p[pr * KP + pc] = v;
+            next_otor_p[pc * KP + pr] = v;
+        }
+    }
+    if (pad) return;
     out[fr * ld_out + fc] = s;
     out[fc * ld_out + fr] = s;
 }
@@ -409,16 +449,25 @@ static int gram_blocks(int64_t n, int KP)
     return (int)b;
 }
 
+// the launch geometry of the partial kernel (lk_gramian and gramian_tail share it: the same row
+// blocks give the same bits): number of blocks, and rows per block -- a multiple of 4 * PF
+// groups so that every block's chains break at the same places whatever n is
+static int gram_geometry(int64_t n, int KP, int64_t *rows_per_block)
+{
+    const int nb = gram_blocks(n, KP);
+    int64_t rpb = ((n + nb - 1) / nb + 15) / 16 * 16;
+    if (rpb < 16) rpb = 16;
+    *rows_per_block = rpb;
+    return nb;
+}
+
 template <int NT>
 static int launch_gramian(const float *m, int64_t n, int k, int ld, float reg, float *out,
                           int ld_out, float *ws, hipStream_t st)
 {
     constexpr int KP = NT * 16;
-    int nb = gram_blocks(n, KP);
-    // rows per block: a multiple of 4 * PF groups so that every block's chains break at the
-    // same places whatever n is
-    int64_t rpb = ((n + nb - 1) / nb + 15) / 16 * 16;
-    if (rpb < 16) rpb = 16;
+    int64_t rpb;
+    const int nb = gram_geometry(n, KP, &rpb);
     bool dma = false;
     if constexpr (NT == 16) dma = gram_dma_enabled() && n >= 16;
     if (dma) {
@@ -439,6 +488,40 @@ static int launch_gramian(const float *m, int64_t n, int k, int ld, float reg, f
                        reg, out, ld_out);
     LK_HIP_CHECK(hipGetLastError());
     return LK_OK;
+}
+
+template <int NT>
+static int launch_gramian_tail(const float *m, int64_t n, int k, float reg, float *out, int ld_out,
+                               float *ws, const float *row_delta, float *partial, float *out_delta,
+                               float *next_otor_p, int *next_status, hipStream_t st)
+{
+    constexpr int KP = NT * 16;
+    int64_t rpb;
+    const int nb = gram_geometry(n, KP, &rpb);
+    const int grid = nb > LK_DELTA_BLOCKS ? nb : LK_DELTA_BLOCKS;
+    hipLaunchKernelGGL((gramian_partial_kernel<NT, true>), dim3(grid), dim3(256), 0, st, m, n, KP,
+                       rpb, ws, nb, row_delta, partial);
+    hipLaunchKernelGGL((gramian_finish_kernel<NT, true>), dim3(KP * KP / 64 + 1), dim3(256), 0, st,
+                       ws, nb, k, reg, out, ld_out, partial, out_delta, next_otor_p, next_status);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
+int gramian_tail(const float *m, int64_t n, int k, int KP, float reg, float *out, int ld_out,
+                 float *gram_ws, const float *row_delta, float *partial, float *out_delta,
+                 float *next_otor_p, int *next_status, hipStream_t st)
+{
+#define LK_TAIL(NT)                                                                            \
+    return launch_gramian_tail<NT>(m, n, k, reg, out, ld_out, gram_ws, row_delta, partial,     \
+                                   out_delta, next_otor_p, next_status, st)
+    switch (KP) {
+        case 16: LK_TAIL(1);
+        case 32: LK_TAIL(2);
+        case 64: LK_TAIL(4);
+    }
+#undef LK_TAIL
+    set_error("gramian_tail: padded k=%d is not served (16 / 32 / 64)", KP);
+    return LK_E_INVALID;
 }
 
 }  // namespace lk
