@@ -1091,6 +1091,46 @@ int lk_fair_rerank(const int32_t *d_lists, int64_t n_rows, int64_t row_len, int6
                    int32_t n_table, int32_t n_out, int32_t *d_out_items, float *d_out_scores,
                    int32_t *d_out_pos, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Randomized truncated SVD (csrc/svd.hip): the device steps of `BiasedSVDScorer.train`
+ * (src/lenskit/sklearn/svd.py:74-104), which in the reference is sklearn's
+ * `TruncatedSVD.fit_transform` -> `randomized_svd` -> `randomized_range_finder`.
+ *
+ * lk_csr_spmm replaces the products `A @ Q` / `A.T @ Q` of `randomized_range_finder`, `Q.T @ M` of
+ * `randomized_svd` and `safe_sparse_dot(X, components_.T)` of `fit_transform`:
+ *   d_out[r][c] = sum over the entries e of CSR row r of d_values[e] * d_x[d_indices[e]][c], c < l;
+ *   d_x [n_cols x ld_x] and d_out [n_rows x ld_out] are padded float32 panels (leading dimensions
+ *   multiples of 4 covering l rounded up to 4, ld_out <= 1024, bases 16-byte aligned); the columns
+ *   [l, ld_out) of d_out are written as zero.  An index outside 0..n_cols-1 contributes nothing.
+ *   A row of at most lk_spmm_split() entries is one fused-multiply-add chain per column in entry
+ *   order; a longer one is cut into segments of that length, each such a chain, added in segment
+ *   order.  No atomics: a row has the same bits alone, in any matrix, on any grid.  A^T Y is the
+ *   same call on the transposed CSR (lk_csr_transpose, once per fit).
+ *
+ * lk_chol_upper_inverse replaces the normaliser between the products (sklearn: LU in the power
+ * iterations, QR at the end; here CholeskyQR2 -- the result depends on the sketch's range only):
+ *   d_gram [l x ld_gram] is the symmetric positive definite Gramian of a panel (lk_gramian; the
+ *   lower triangle is read), G = R^T R with R upper triangular.  d_inverse [ld_out x ld_out]
+ *   receives (R^-1)^T and d_lower (may be NULL) R^T, both lower triangular with zeros everywhere
+ *   else -- as they stand the "items" operands of lk_score_dense for Y R^-1 with zero pad columns.
+ *   One workgroup, the matrix in LDS as float32, the sums behind each entry carried in float64
+ *   and rounded once: l <= lk_chol_max_l() = 192 (beyond that the caller uses the
+ *   library's Cholesky and triangular solve).  A pivot that is not above 4 ulp of its diagonal
+ *   entry (not positive to working precision: the panel has lost rank) stores `step` (!= 0) into
+ *   *d_flag if that is still 0 and is replaced by the diagonal entry, so the outputs stay finite;
+ *   the caller reads the flag once, when the whole factorisation is queued (as
+ *   lk_als_check_status does), never between steps.
+ * ---------------------------------------------------------------------- */
+int32_t lk_spmm_split(void);
+int lk_csr_spmm(const void *d_indptr, int indptr_is_64, const int32_t *d_indices,
+                const float *d_values, int64_t n_rows, int64_t n_cols, int64_t nnz,
+                const float *d_x, int32_t ld_x, int32_t l, float *d_out, int32_t ld_out,
+                void *stream);
+int32_t lk_chol_max_l(void);
+int lk_chol_upper_inverse(const float *d_gram, int32_t ld_gram, int32_t l, float *d_lower,
+                          float *d_inverse, int32_t ld_out, int32_t *d_flag, int32_t step,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif

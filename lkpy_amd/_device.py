@@ -2058,3 +2058,205 @@ def mf_score_pairs(users: torch.Tensor, items: torch.Tensor, k: int, user_rows: 
                                 user_rows.numel(), _ptr(tgt_ptr), _ptr(tgt_items),
                                 tgt_items.numel(), _ptr(out), _stream()), "lk_mf_score_pairs")
     return out
+
+
+# ---- randomized truncated SVD (csrc/svd.hip) ------------------------------------------------
+SVD_OVERSAMPLES = 10  # sklearn's ``n_oversamples`` default, which ``TruncatedSVD`` passes on
+
+
+def spmm_split() -> int:
+    "The entries of one chain segment of ``lk_csr_spmm`` (lk_spmm_split): longer rows are cut."
+    return int(_native.load().lk_spmm_split())
+
+
+def chol_max_l() -> int:
+    "The largest Gramian ``lk_chol_upper_inverse`` factors in LDS (lk_chol_max_l)."
+    return int(_native.load().lk_chol_max_l())
+
+
+def csr_spmm(csr: DeviceCSR, x: torch.Tensor, l: int) -> torch.Tensor:
+    """
+    Sparse x tall-skinny (lk_csr_spmm): ``csr`` [rows x cols] times the padded panel ``x``
+    [cols x LD] (``l`` columns in use) -> a padded panel [rows x LD], pad columns zero.
+    """
+    lib = _native.require_gpu()
+    n_rows, n_cols = csr.shape
+    ld = padded_dim(l)
+    assert x.dtype == torch.float32 and x.is_contiguous() and tuple(x.shape) == (n_cols, ld)
+    assert csr.values is not None and csr.values.dtype == torch.float32
+    out = torch.empty((n_rows, ld), dtype=torch.float32, device=x.device)
+    check(
+        lib.lk_csr_spmm(_ptr(csr.indptr), 1 if csr.is64 else 0, _ptr(csr.indices),
+                        _ptr(csr.values), n_rows, n_cols, csr.nnz, _ptr(x), ld, int(l),
+                        _ptr(out), ld, _stream()),
+        "lk_csr_spmm",
+    )
+    return out
+
+
+def chol_upper_inverse(gram: torch.Tensor, flag: torch.Tensor, step: int, *,
+                       want_lower: bool = False):
+    """
+    ``gram`` [l x l] = R^T R -> ((R^-1)^T, R^T | None), each [LD x LD] lower triangular with
+    zeros elsewhere (LD = the padded width of l): ``lk_chol_upper_inverse`` up to
+    :func:`chol_max_l`, the library's ``cholesky_ex`` + ``solve_triangular`` beyond it.  A pivot
+    that is not positive stores ``step`` into ``flag`` (device int32 [1]) if that is still 0;
+    nothing is read back here.
+    """
+    lib = _native.require_gpu()
+    l = int(gram.shape[0])
+    ld = padded_dim(l)
+    dev = gram.device
+    assert gram.dtype == torch.float32 and gram.shape[1] == l and gram.stride(1) == 1
+    assert flag.dtype == torch.int32 and flag.numel() == 1 and int(step) != 0
+    if l <= chol_max_l():
+        inv = torch.empty((ld, ld), dtype=torch.float32, device=dev)
+        lower = torch.empty((ld, ld), dtype=torch.float32, device=dev) if want_lower else None
+        check(lib.lk_chol_upper_inverse(_ptr(gram), gram.stride(0), l, _ptr(lower), _ptr(inv), ld,
+                                        _ptr(flag), int(step), _stream()),
+              "lk_chol_upper_inverse")
+        return inv, lower
+    # float64 inside, as the kernel carries its sums: the float32 factors are rounded once
+    low, info = torch.linalg.cholesky_ex(gram.double())
+    bad = (info != 0) | ~torch.isfinite(low).all()
+    flag.copy_(torch.where((flag == 0) & bad, torch.full_like(flag, int(step)), flag))
+    eye = torch.eye(l, dtype=torch.float64, device=dev)
+    low = torch.where(bad, eye, low).float()
+    inv = torch.zeros((ld, ld), dtype=torch.float32, device=dev)
+    inv[:l, :l] = torch.linalg.solve_triangular(low.double(), eye, upper=False).float()
+    lower = None
+    if want_lower:
+        lower = torch.zeros((ld, ld), dtype=torch.float32, device=dev)
+        lower[:l, :l] = low
+    return inv, lower
+
+
+class CholeskyQR2:
+    """
+    ``orth``: the orthonormal basis of a padded panel's columns by CholeskyQR2 -- Gramian
+    (lk_gramian), the inverse of its Cholesky factor (lk_chol_upper_inverse), the panel times
+    that (lk_score_dense), and the same again on the result, which repairs the first pass's loss
+    of orthogonality.  Everything is queued on the current stream; a Gramian that is not positive
+    definite records its step in ``flag``, which :meth:`failed_step` reads (a synchronisation).
+    """
+
+    def __init__(self, l: int, dev):
+        self.l, self.ld, self.dev = int(l), padded_dim(l), dev
+        self.gramian = Gramian(self.l, dev)
+        self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.steps: list[str] = []
+
+    def __call__(self, y: torch.Tensor, what: str, keep_factor: bool = False):
+        "Q [rows x LD]; with ``keep_factor`` also R^T = L1 L2 ... as (Q, R^T [LD x LD])"
+        lowers = []
+        for p in (1, 2):
+            self.steps.append(f"{what}, CholeskyQR pass {p}")
+            inv, low = chol_upper_inverse(self.gramian(y, 0.0), self.flag, len(self.steps),
+                                          want_lower=keep_factor)
+            y = score_dense(y, inv, self.l)  # Y R^-1: rows of ``inv`` beyond l are zero pads
+            lowers.append(low)
+        if not keep_factor:
+            return y
+        # R = R2 R1, so R^T = L1 L2 with L = R^T: (L1 L2)[i][j] = L1[i] . (L2^T)[j]
+        return y, score_dense(lowers[0], lowers[1].t().contiguous(), self.l)
+
+    def failed_step(self) -> str | None:
+        step = int(self.flag.item())
+        return None if step == 0 else self.steps[step - 1]
+
+
+def randomized_svd(csr: DeviceCSR, csr_t: DeviceCSR, k: int, n_iter: int, omega: np.ndarray, *,
+                   device_output: bool = False, stats: dict | None = None):
+    """
+    Randomized truncated SVD of the sparse matrix ``csr`` (``csr_t``: its transpose,
+    :func:`csr_transpose`), following sklearn's ``randomized_svd`` / ``randomized_range_finder``
+    as ``TruncatedSVD.fit_transform`` calls them, step for step: ``l = k + 10`` sketch columns
+    from the Gaussian start panel ``omega`` [min(shape) x l]; the transpose is operated on when
+    there are fewer rows than columns; ``n_iter`` rounds of ``Q <- orth(M Q); Q <- orth(M^T Q)``
+    and a last ``Q <- orth(M Q)``; ``B^T = M^T Q = Q_b R_b``; the float64 SVD of the l x l
+    ``R_b`` on the host (the only host arithmetic); truncation to ``k``;
+    ``svd_flip(u_based_decision=False)``; ``transformed = A components^T``.  ``orth`` is
+    :class:`CholeskyQR2` where sklearn normalises by LU and QR: the result depends on the range of
+    the sketch only.
+
+    Returns (singular_values float64 [k], components f32 [k x n_cols], transformed f32
+    [n_rows x k]) on the host; with ``device_output`` the last two stay on the device as padded
+    panels: item factors [n_cols x KP] (= components^T) and transformed [n_rows x KP].
+
+    ``ValueError`` unless ``k + 10 <= min(shape)`` and ``k + 10 <= 1024``; ``RuntimeError``
+    naming the step when a sketch is numerically rank-deficient (never NaN factors).
+
+    ``stats`` (a dict, for the timing tool): the stream is synchronised around every step and the
+    dict receives the seconds spent in ``spmm`` and ``orth`` and the number of ``spmm_calls``.
+    """
+    import scipy.linalg as sla
+    from time import perf_counter
+
+    n_rows, n_cols = csr.shape
+    k, n_iter = int(k), int(n_iter)
+    l = k + SVD_OVERSAMPLES
+    if k < 1 or l > min(n_rows, n_cols):
+        raise ValueError(f"randomized_svd: k + {SVD_OVERSAMPLES} = {l} sketch columns need a "
+                         f"matrix of at least that many rows and columns, got {csr.shape}")
+    if l > 1024:
+        raise ValueError(f"randomized_svd: k + {SVD_OVERSAMPLES} = {l} exceeds 1024")
+    if tuple(csr_t.shape) != (n_cols, n_rows) or csr_t.nnz != csr.nnz:
+        raise ValueError("randomized_svd: csr_t is not the transpose of csr")
+    transpose = n_rows < n_cols  # sklearn's transpose="auto"
+    m, mt = (csr_t, csr) if transpose else (csr, csr_t)
+    omega = np.asarray(omega, dtype=np.float32)
+    if omega.shape != (m.shape[1], l):
+        raise ValueError(f"randomized_svd: omega must be {(m.shape[1], l)}, got {omega.shape}")
+    dev = csr.indices.device
+    orth = CholeskyQR2(l, dev)
+    spmm = csr_spmm
+    if stats is not None:
+        stats.update(spmm=0.0, orth=0.0, spmm_calls=0)
+
+        def timed(fn, key):
+            def run(*a, **kw):
+                torch.cuda.synchronize(dev)
+                t0 = perf_counter()
+                out = fn(*a, **kw)
+                torch.cuda.synchronize(dev)
+                stats[key] += perf_counter() - t0
+                stats[key + "_calls"] = stats.get(key + "_calls", 0) + 1
+                return out
+            return run
+
+        spmm, orth_call = timed(csr_spmm, "spmm"), timed(orth.__call__, "orth")
+    else:
+        orth_call = orth.__call__
+
+    def fail(step):
+        raise RuntimeError(f"randomized_svd: the sketch is numerically rank-deficient (its "
+                           f"Gramian has no Cholesky factor) at: {step}")
+
+    q = to_device_padded(omega, dev)
+    for it in range(1, n_iter + 1):
+        q = orth_call(spmm(m, q, l), f"power iteration {it}, M Q")
+        q = orth_call(spmm(mt, q, l), f"power iteration {it}, M^T Q")
+    q = orth_call(spmm(m, q, l), "range basis, M Q")
+    q_b, rbt = orth_call(spmm(mt, q, l), "B^T = M^T Q", keep_factor=True)
+    r_b = rbt[:l, :l].cpu().numpy().T.astype(np.float64)  # the one download inside the fit
+    if not np.isfinite(r_b).all():
+        fail(orth.failed_step() or "B^T = M^T Q")
+    w, s, zt = sla.svd(r_b, lapack_driver="gesdd")
+    # B = Z S (Q_b W)^T: M's left vectors are Q Z, its right vectors Q_b W; A's right vectors
+    # are the left ones of M = A^T
+    basis, rot = (q, zt.T[:, :k]) if transpose else (q_b, w[:, :k])
+    kp = padded_dim(k)
+    rot_t = np.zeros((kp, l), dtype=np.float32)  # the "items" operand: rows beyond k are pads
+    rot_t[:k] = rot.T
+    v = score_dense(basis, to_device_padded(rot_t, dev), l)  # [n_cols x KP]
+    # svd_flip(u_based_decision=False): a component's largest-magnitude entry is made positive
+    top = v.abs().argmax(dim=0, keepdim=True)
+    sign = torch.where(v.gather(0, top) < 0, -1.0, 1.0).to(torch.float32)
+    v = (v * sign).contiguous()
+    transformed = spmm(csr, v, k)
+    step = orth.failed_step()  # the synchronisation at the end
+    if step is not None:
+        fail(step)
+    if device_output:
+        return s[:k], v, transformed
+    return s[:k], np.ascontiguousarray(to_host_unpadded(v, k).T), to_host_unpadded(transformed, k)

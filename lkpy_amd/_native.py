@@ -284,6 +284,15 @@ def _declare(lib):
             c_int, [vp, c_int64, c_int64, c_int64, vp, vp, vp, c_int64, vp, c_int32, c_int32, vp,
                     vp, vp, vp]
         ),
+        "lk_spmm_split": (c_int32, []),
+        "lk_csr_spmm": (
+            c_int, [vp, c_int, vp, vp, c_int64, c_int64, c_int64, vp, c_int32, c_int32, vp,
+                    c_int32, vp]
+        ),
+        "lk_chol_max_l": (c_int32, []),
+        "lk_chol_upper_inverse": (
+            c_int, [vp, c_int32, c_int32, vp, vp, c_int32, vp, c_int32, vp]
+        ),
         "lk_als_implicit_half_epoch_host": (
             c_int,
             [vp, c_int, vp, vp, c_int64, c_int64, c_int32, vp, vp, vp, c_int32, vp],

@@ -33,10 +33,9 @@ from pydantic import BaseModel, NonNegativeInt, PositiveFloat, PositiveInt, mode
 
 from . import _device as D
 from . import _native
-from ._queries import (item_scores, pack_histories, pack_targets, resolve_queries,
-                       user_numbers)
+from ._factor_scoring import BiasedFactorScoring, GlobalBiasPairScoring
+from ._queries import item_scores
 from .als import _DeviceBacked, _scorer_state
-from .basic import HistoryBatch
 from .data import Dataset, ItemList, RecQuery, Vocabulary
 from .pipeline import Component
 from .training import ModelTrainer, TrainingOptions, UsesTrainer
@@ -135,17 +134,15 @@ class FlexMFImplicitConfig(FlexMFConfigBase):
         return self
 
 
-class FlexMFScorerBase(UsesTrainer, Component):
+class FlexMFScorerBase(BiasedFactorScoring, UsesTrainer, Component):
     """
     What the FlexMF scorers share (``FlexMFScorerBase``, _base.py:98-164).  Learned state (host
     arrays, refreshed lazily from the device while a trainer is live): ``user_embeddings``
     [users x k], ``item_embeddings`` [items x k], ``user_bias`` [users] | None, ``item_bias``
     [items] | None, ``users``, ``items``.  On the device the biases are extra columns of the two
-    operand matrices (``_bias_columns``), so that a score is one inner product.
+    operand matrices, so that a score is one inner product: the batched scoring is
+    :class:`lkpy_amd._factor_scoring.BiasedFactorScoring`.
     """
-
-    accepts_history_batch = True  # recommend_batch takes a lkpy_amd.basic.HistoryBatch
-    returns_device_lists = True  # ... and has ``device_output``: the lists left on the device
 
     users: Vocabulary
     items: Vocabulary
@@ -162,83 +159,6 @@ class FlexMFScorerBase(UsesTrainer, Component):
         state.pop("_dev", None)
         state.pop("_pending_sync", None)
         self.__dict__.update(state)
-
-    # -- device state: the biases folded in as extra columns ----------------------------
-    def _bias_columns(self, one_u, bu, one_i, bi):
-        "(user columns, item columns) behind the embeddings: [p_u, 1, b_u] . [q_i, b_i, 1]"
-        return [one_u, bu], [bi, one_i]
-
-    def _device_state(self):
-        def upload():
-            d = D.device()
-            P, Q = self.user_embeddings, self.item_embeddings
-            one_u, one_i = np.ones((len(P), 1), np.float32), np.ones((len(Q), 1), np.float32)
-            bu = np.zeros_like(one_u) if self.user_bias is None else \
-                np.asarray(self.user_bias, np.float32).reshape(-1, 1)
-            bi = np.zeros_like(one_i) if self.item_bias is None else \
-                np.asarray(self.item_bias, np.float32).reshape(-1, 1)
-            ucols, icols = self._bias_columns(one_u, bu, one_i, bi)
-            return {"device": d, "U": D.to_device_padded(np.hstack([P, *ucols]), d),
-                    "Q": D.to_device_padded(np.hstack([Q, *icols]), d)}
-
-        return self._device_cache("model", upload, self.user_embeddings, self.item_embeddings,
-                                  self.user_bias, self.item_bias)
-
-    @property
-    def _score_k(self) -> int:
-        return self.config.embedding_size + 2
-
-    def _user_rows(self, nums: np.ndarray):
-        "device [B x KP] operand rows of the users ``nums`` (-1: unknown -> a zero row) + validity"
-        st = self._device_state()
-        nums = np.asarray(nums, dtype=np.int64)
-        valid = nums >= 0
-        idx = torch.from_numpy(np.where(valid, nums, 0)).to(st["device"])
-        return st["U"][idx].contiguous(), valid
-
-    def recommend_batch(self, queries, n: int, *, exclude_history: bool = True,
-                        device_output: bool = False):
-        """
-        Dense scoring + top-N for many queries at once on ``lk_score_topk``, from the operands
-        ``__call__`` scores with.  ``queries``: a list of queries or a
-        :class:`lkpy_amd.basic.HistoryBatch`.  Returns (item numbers [B x n] with -1 padding,
-        scores [B x n] with NaN padding); an unknown user's row is all padding.
-        """
-        u, valid, hist = self._batch_operands(queries, exclude_history)
-        st = self._device_state()
-        if hist is not None:
-            idx, sc = D.score_topk(u, st["Q"], self._score_k, n, hist.indptr, hist.indices)
-        else:
-            idx, sc = D.score_topk(u, st["Q"], self._score_k, n)
-        D.blank_rows(idx, sc, valid)
-        if device_output:
-            return idx, sc
-        return D.lists_to_host(idx, sc)
-
-    def _batch_operands(self, queries, exclude_history: bool = True):
-        "(device [B x KP] user rows, valid, the CSR of items to strike | None) of a batch"
-        queries = resolve_queries(queries, self.items)
-        st = self._device_state()
-        hist = None
-        if exclude_history and isinstance(queries, HistoryBatch):
-            hist = queries.csr(with_values=False)
-        elif exclude_history:  # the items to strike: known ones, sorted, no values
-            ptr, idx, _ = pack_histories(queries, self.items, unknown="drop", sort=True)
-            hist = D.DeviceCSR.from_arrays(ptr, idx, None, (len(queries), len(self.items)),
-                                           st["device"])
-        u, valid = self._user_rows(user_numbers(queries, self.users))
-        return u, valid, hist
-
-    def dense_scores_batch(self, queries):
-        """
-        Every item's score for many queries at once, left on the device: (panel f32 [B x items],
-        valid, history CSR) -- ``recommend_batch``'s operands scored by ``lk_score_dense``.  An
-        unknown user's row is NaN; the history is for the caller to exclude.
-        """
-        u, valid, hist = self._batch_operands(queries)
-        panel = D.score_dense(u, self._device_state()["Q"], self._score_k)
-        D.blank_panel_rows(panel, valid)
-        return panel, valid, hist
 
 
 class FlexMFImplicitScorer(FlexMFScorerBase):
@@ -266,12 +186,13 @@ class FlexMFImplicitScorer(FlexMFScorerBase):
         return ItemList(items, scores=item_scores(items, self.items, all_scores))
 
 
-class FlexMFExplicitScorer(FlexMFScorerBase):
+class FlexMFExplicitScorer(GlobalBiasPairScoring, FlexMFScorerBase):
     """
     Explicit-feedback FlexMF (_explicit.py:38-55): ``score = g + b_u + b_i + p_u . q_i`` with the
     global bias ``g`` = the float32 mean of the training ratings.  Ratings are predicted for
-    ragged (user, item) lists by ``lk_mf_score_pairs``: ``__call__`` is ``score_batch`` with one
-    query, so the two agree bit for bit.
+    ragged (user, item) lists by ``lk_mf_score_pairs``
+    (:class:`lkpy_amd._factor_scoring.GlobalBiasPairScoring`): ``__call__`` is ``score_batch``
+    with one query, so the two agree bit for bit.
     """
 
     config: FlexMFExplicitConfig
@@ -279,56 +200,6 @@ class FlexMFExplicitScorer(FlexMFScorerBase):
 
     def create_trainer(self, data, options):
         return FlexMFExplicitTrainer(self, data, options)
-
-    def _bias_columns(self, one_u, bu, one_i, bi):
-        # [p_u, 1, b_u, 1] . [q_i, b_i, 1, g]: g is a float32 value (the mean's), carried exactly
-        g = np.full_like(one_i, np.float32(self.global_bias))
-        return [one_u, bu, one_u], [bi, one_i, g]
-
-    @property
-    def _score_k(self) -> int:
-        return self.config.embedding_size + 3
-
-    def score_pairs(self, user_nums, tgt_ptr, item_nums, *, device_output: bool = False):
-        """
-        Scores by number: query q is user ``user_nums[q]`` against the items
-        ``item_nums[tgt_ptr[q]:tgt_ptr[q + 1]]`` (-1: unknown -> NaN).  One upload, one
-        ``lk_mf_score_pairs`` launch, one download (none with ``device_output``).
-        """
-        st = self._device_state()
-        user_nums = np.ascontiguousarray(user_nums, dtype=np.int32).reshape(-1)
-        tgt_ptr = np.ascontiguousarray(tgt_ptr, dtype=np.int64).reshape(-1)
-        item_nums = np.ascontiguousarray(item_nums, dtype=np.int32).reshape(-1)
-        nq, total = len(user_nums), len(item_nums)
-        if len(tgt_ptr) != nq + 1 or tgt_ptr[0] != 0 or tgt_ptr[-1] != total or \
-                (np.diff(tgt_ptr) < 0).any():
-            raise ValueError("tgt_ptr must ascend from 0 to len(item_nums), one entry per query "
-                             "and one more")
-        if total == 0:
-            empty = np.zeros(0, np.float32)
-            return torch.from_numpy(empty).to(st["device"]) if device_output else empty
-        # one upload: offsets (int64) | user rows | item numbers (int32)
-        packed = np.empty(2 * (nq + 1) + nq + total, np.int32)
-        packed[:2 * (nq + 1)] = tgt_ptr.view(np.int32)
-        packed[2 * (nq + 1):2 * (nq + 1) + nq] = user_nums
-        packed[2 * (nq + 1) + nq:] = item_nums
-        d_packed = torch.from_numpy(packed).to(st["device"])
-        out = D.mf_score_pairs(st["U"], st["Q"], self._score_k,
-                               d_packed[2 * (nq + 1):2 * (nq + 1) + nq],
-                               d_packed[:2 * (nq + 1)].view(torch.int64),
-                               d_packed[2 * (nq + 1) + nq:])
-        return out if device_output else out.cpu().numpy()
-
-    def score_batch(self, queries, item_lists) -> list[ItemList]:
-        "``__call__`` for many queries: one vocabulary pass, one launch, the same bits."
-        qs = [RecQuery.create(q) for q in queries]
-        ptr, nums = pack_targets(item_lists, self.items)
-        scores = self.score_pairs(user_numbers(qs, self.users), ptr, nums)
-        return [ItemList(il, scores=scores[ptr[i]:ptr[i + 1]])
-                for i, il in enumerate(item_lists)]
-
-    def __call__(self, query, items: ItemList) -> ItemList:
-        return self.score_batch([query], [items])[0]
 
 
 def initial_tables(n_users: int, n_items: int, k: int, gen: torch.Generator, *, user_bias: bool,
