@@ -1131,6 +1131,58 @@ int lk_chol_upper_inverse(const float *d_gram, int32_t ld_gram, int32_t l, float
                           float *d_inverse, int32_t ld_out, int32_t *d_flag, int32_t step,
                           void *stream);
 
+/* ------------------------------------------------------------------------
+ * LightGCN (csrc/lightgcn.hip): the training step of `lenskit.graphs.lightgcn.LightGCNScorer`
+ * (src/lenskit/graphs/lightgcn.py:108-324), whose arithmetic the reference tree states in
+ * `FlexMFModel.update_convolution` / `forward` (src/lenskit/flexmf/_model.py:122-198) and
+ * `FlexMFImplicitTrainer.prepare_data` / `train_batch` (_implicit.py:179-274).  n = items + users
+ * nodes, items first; M is the symmetric n x n adjacency in CSR (int64 offsets, int32 columns, no
+ * values), d_scale [n] = degree^-1/2 (0 for a node without entries), Mhat = diag(d) M diag(d).
+ * Panels are float32 [n x ld], ld a multiple of 4 covering k <= LK_FLEXMF_MAX_K, bases 16-byte
+ * aligned, pad columns zero.  Every call is asynchronous on `stream`; nothing is atomic on floats
+ * and every sum has a fixed order.
+ *
+ * lk_lgcn_propagate replaces one `torch.mm(ui_mat, imat)` / `torch.mm(iu_mat, umat)` pair of
+ * `update_convolution` (_model.py:134-140) together with the layer blend of `forward`
+ * (_model.py:174-186), and the same products of autograd's backward pass:
+ *   d_out[r] = a d_x[r] + (b d_scale[r]) sum over the entries e of row r of d_scale[col_e] d_t[col_e];
+ *   d_x = NULL: no a d_x term.  A row of at most lk_spmm_split() entries is one
+ *   fused-multiply-add chain per column in entry order from zero; a longer one is cut into
+ *   segments of that length, each such a chain, added in segment order from zero; the row's scale
+ *   is applied to the sum once and the a d_x term joins by one fused multiply-add.  A row has the
+ *   same bits alone, in any matrix, on any grid.  An index outside 0..n-1 contributes nothing; a
+ *   row without entries gives a d_x[r] (0 without d_x).  d_out must not alias d_x or d_t.
+ *
+ * lk_lgcn_pair_grad replaces `model(edges, mb_edges)`'s inner products, `batch_loss` and the
+ * part of `loss.backward()` up to the propagated embeddings (lightgcn.py:289-292; the losses as
+ * _implicit.py:399-409 states them, one negative per positive):
+ *   s+ = xbar[u] . xbar[i+], s- = xbar[u] . xbar[i-] per sample (d_users, d_pos, d_neg: node
+ *   numbers, duplicates allowed; a sample naming a node outside 0..n-1 takes no part);
+ *   LK_FLEXMF_PAIRWISE  mean -log sigmoid(s+ - s-);
+ *   LK_FLEXMF_LOGISTIC  (sum -log sigmoid(s+) + sum -log sigmoid(-s-)) / (2 batch);
+ *   *d_loss receives the loss, *d_loss_sum (may be NULL) has it added; d_grad [n x ld] receives
+ *   dloss/dxbar as a dense panel: zero, plus per node the sum of its samples' contributions in
+ *   sample order (stable radix sort by node, then one wave per touched node, float64 sums
+ *   rounded once), as lk_flexmf_step sums its rows.
+ *
+ * lk_adamw_dense replaces `optimizer.step()` of torch.optim.AdamW on one dense parameter
+ * (lightgcn.py:239-249,293): every element of the k columns of d_param, d_exp_avg, d_exp_avg_sq
+ * is updated from d_grad with the moments and the rounding of lk_flexmf_step's AdamW pass;
+ * weight_decay = 0 is torch.optim.Adam.  bias_corr = 1 - beta^t of the step about to be taken.
+ * Pad columns are left as they are.
+ * ---------------------------------------------------------------------- */
+int lk_lgcn_propagate(const int64_t *d_indptr, const int32_t *d_indices, const float *d_scale,
+                      int64_t n, int64_t nnz, float a, const float *d_x, float b,
+                      const float *d_t, int32_t k, int32_t ld, float *d_out, void *stream);
+size_t lk_lgcn_pair_grad_workspace_bytes(int64_t batch);
+int lk_lgcn_pair_grad(const float *d_xbar, int64_t n, int32_t k, int32_t ld, int32_t loss,
+                      const int32_t *d_users, const int32_t *d_pos, const int32_t *d_neg,
+                      int64_t batch, void *d_ws, float *d_grad, float *d_loss, float *d_loss_sum,
+                      void *stream);
+int lk_adamw_dense(float *d_param, float *d_exp_avg, float *d_exp_avg_sq, const float *d_grad,
+                   int64_t n, int32_t k, int32_t ld, double lr, double weight_decay, double beta1,
+                   double beta2, double eps, double bias_corr1, double bias_corr2, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2260,3 +2260,171 @@ def randomized_svd(csr: DeviceCSR, csr_t: DeviceCSR, k: int, n_iter: int, omega:
     if device_output:
         return s[:k], v, transformed
     return s[:k], np.ascontiguousarray(to_host_unpadded(v, k).T), to_host_unpadded(transformed, k)
+
+
+# ---- LightGCN (csrc/lightgcn.hip) --------------------------------------------------------------
+def lgcn_ld(k: int) -> int:
+    "The leading dimension of a LightGCN panel: ``k`` rounded up to whole float4 chunks."
+    return (int(k) + 3) // 4 * 4
+
+
+def lgcn_panel(mat: np.ndarray, dev) -> torch.Tensor:
+    "Host [n x k] float32 -> device [n x lgcn_ld(k)] with zero pad columns."
+    mat = np.ascontiguousarray(mat, dtype=np.float32)
+    n, k = mat.shape
+    out = torch.zeros((n, lgcn_ld(k)), dtype=torch.float32, device=dev)
+    out[:, :k] = torch.from_numpy(mat).to(dev)
+    return out
+
+
+def lgcn_propagate(indptr: torch.Tensor, indices: torch.Tensor, scale: torch.Tensor, a: float,
+                   x: torch.Tensor | None, b: float, t: torch.Tensor, k: int,
+                   out: torch.Tensor | None = None) -> torch.Tensor:
+    """
+    ``out[r] = a x[r] + b scale[r] sum_e scale[col_e] t[col_e]`` over the entries of CSR row r
+    (lk_lgcn_propagate): ``indptr`` int64 [n + 1], ``indices`` int32, ``scale`` float32 [n],
+    ``x`` (or None: no ``a x`` term) and ``t`` padded panels [n x lgcn_ld(k)].
+    """
+    lib = _native.require_gpu()
+    n, ld = t.shape
+    assert indptr.dtype == torch.int64 and indptr.numel() == n + 1 and indptr.is_contiguous()
+    assert indices.dtype == torch.int32 and indices.is_contiguous()
+    assert scale.dtype == torch.float32 and scale.numel() == n and scale.is_contiguous()
+    for p in (x, t, out):
+        assert p is None or (p.dtype == torch.float32 and p.is_contiguous()
+                             and tuple(p.shape) == (n, ld))
+    if out is None:
+        out = torch.empty_like(t)
+    check(lib.lk_lgcn_propagate(_ptr(indptr), _ptr(indices), _ptr(scale), n, indices.numel(),
+                                float(a), _ptr(x), float(b), _ptr(t), int(k), ld, _ptr(out),
+                                _stream()), "lk_lgcn_propagate")
+    return out
+
+
+def adamw_dense(param: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor,
+                grad: torch.Tensor, k: int, *, step: int, learning_rate: float,
+                weight_decay: float, beta1: float = 0.9, beta2: float = 0.999,
+                eps: float = 1e-8) -> None:
+    "Step ``step`` (from 1) of ``torch.optim.AdamW`` on one padded panel, in place (lk_adamw_dense)."
+    lib = _native.require_gpu()
+    n, ld = param.shape
+    for p in (param, exp_avg, exp_avg_sq, grad):
+        assert p.dtype == torch.float32 and p.is_contiguous() and tuple(p.shape) == (n, ld)
+    check(lib.lk_adamw_dense(_ptr(param), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(grad), n, int(k),
+                             ld, float(learning_rate), float(weight_decay), float(beta1),
+                             float(beta2), float(eps), 1.0 - beta1 ** step, 1.0 - beta2 ** step,
+                             _stream()), "lk_adamw_dense")
+
+
+class LightGCNState:
+    """
+    The LightGCN model and its optimiser state in HBM: the embedding panel ``X`` [n x LD] of the
+    n = items + users nodes (items first), AdamW's two moment panels, the adjacency ``M`` (CSR:
+    ``indptr`` int64, ``indices`` int32) with ``scale`` = degree^-1/2, three work panels and the
+    pair gradient's scratch.  ``blend``: the L + 1 layer weights alpha_0 .. alpha_L.
+
+    ``step`` is one batch: forward by L ``lk_lgcn_propagate`` launches (Horner form:
+    ``t_L = alpha_L x``, ``t_j = alpha_j x + Mhat t_{j+1}``), ``lk_lgcn_pair_grad``, backward by
+    the same L launches on the gradient panel, ``lk_adamw_dense``.
+    """
+
+    def __init__(self, embeddings, indptr, indices, scale, blend, *, loss: str = "pairwise",
+                 regularization: float | None = 0.01, learning_rate: float = 0.01, dev=None):
+        self.dev = dev = device(dev)
+        self.n, self.k = np.shape(embeddings)
+        if not 1 <= self.k <= _native.FLEXMF_MAX_K:
+            raise ValueError(f"unsupported embedding size {self.k} "
+                             f"(supported: 1..{_native.FLEXMF_MAX_K})")
+        if loss not in ("pairwise", "logistic"):
+            raise ValueError(f"unknown loss {loss}")
+        self.blend = [float(a) for a in blend]
+        if len(self.blend) < 2:
+            raise ValueError("LightGCN needs at least one layer (two blend weights)")
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        scale = np.ascontiguousarray(scale, dtype=np.float32)
+        if len(indptr) != self.n + 1 or len(scale) != self.n or indptr[0] != 0 or \
+                indptr[-1] != len(indices) or (np.diff(indptr) < 0).any():
+            raise ValueError("the adjacency does not describe the embedding table's nodes")
+        if len(indices) and (indices.min() < 0 or indices.max() >= self.n):
+            raise ValueError(f"adjacency columns outside [0, {self.n})")
+        self.indptr = torch.from_numpy(indptr).to(dev)
+        self.indices = torch.from_numpy(indices).to(dev)
+        self.scale = torch.from_numpy(scale).to(dev)
+        self.X = lgcn_panel(embeddings, dev)
+        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.X), torch.zeros_like(self.X)
+        self._work = [torch.empty_like(self.X) for _ in range(3)]  # two running panels, g
+        self.loss = loss
+        self.weight_decay = 0.0 if regularization is None else float(regularization)
+        self.learning_rate = float(learning_rate)
+        self.steps = 0
+        self._ws = None
+        self._ws_batch = 0
+
+    @property
+    def layers(self) -> int:
+        return len(self.blend) - 1
+
+    def propagate(self, x: torch.Tensor) -> torch.Tensor:
+        "sum_l alpha_l Mhat^l x in Horner form; the result is one of the two running panels"
+        al = self.blend
+        L = self.layers
+        out, other = self._work[0], self._work[1]
+        lgcn_propagate(self.indptr, self.indices, self.scale, al[L - 1], x, al[L], x, self.k, out)
+        for j in range(L - 2, -1, -1):
+            lgcn_propagate(self.indptr, self.indices, self.scale, al[j], x, 1.0, out, self.k,
+                           other)
+            out, other = other, out
+        return out
+
+    def pair_grad(self, xbar: torch.Tensor, users, positives, negatives, *, loss_sum=None,
+                  check_indices: bool = True, out: torch.Tensor | None = None):
+        "(dloss/dxbar as a dense panel, the batch loss) of one batch of node numbers"
+        lib = _native.require_gpu()
+        dev = self.dev
+        users, positives = _i32_dev(users, dev).reshape(-1), _i32_dev(positives, dev).reshape(-1)
+        negatives = _i32_dev(negatives, dev).reshape(-1)
+        B = users.numel()
+        if positives.numel() != B or negatives.numel() != B or B < 1:
+            raise ValueError("batch arrays disagree in length")
+        if check_indices:
+            for name, t in (("users", users), ("positives", positives), ("negatives", negatives)):
+                if int(t.min()) < 0 or int(t.max()) >= self.n:
+                    raise ValueError(f"{name} outside [0, {self.n})")
+        if self._ws is None or self._ws_batch < B:
+            self._ws = torch.empty(lib.lk_lgcn_pair_grad_workspace_bytes(B), dtype=torch.uint8,
+                                   device=dev)
+            self._ws_batch = B
+        g = self._work[2] if out is None else out
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        check(lib.lk_lgcn_pair_grad(_ptr(xbar), self.n, self.k, self.X.shape[1],
+                                    _native.FLEXMF_LOSSES[self.loss], _ptr(users),
+                                    _ptr(positives), _ptr(negatives), B, _ptr(self._ws), _ptr(g),
+                                    _ptr(loss), _ptr(loss_sum), _stream()), "lk_lgcn_pair_grad")
+        return g, loss
+
+    def step(self, users, positives, negatives, *, loss_sum=None,
+             check_indices: bool = True) -> torch.Tensor:
+        "One training step; returns the batch loss (device, 1 element), nothing synchronised."
+        xbar = self.propagate(self.X)
+        g, loss = self.pair_grad(xbar, users, positives, negatives, loss_sum=loss_sum,
+                                 check_indices=check_indices)
+        grad = self.propagate(g)
+        self.steps += 1
+        adamw_dense(self.X, self.exp_avg, self.exp_avg_sq, grad, self.k, step=self.steps,
+                    learning_rate=self.learning_rate, weight_decay=self.weight_decay)
+        return loss
+
+    def final_embeddings(self) -> np.ndarray:
+        "The propagated, blended embeddings xbar [n x k] on the host: one forward pass."
+        return self.propagate(self.X)[:, :self.k].cpu().numpy()
+
+    def host_table(self) -> np.ndarray:
+        "The embedding table X [n x k] on the host."
+        return self.X[:, :self.k].cpu().numpy()
+
+    def load_table(self, table) -> None:
+        table = np.asarray(table, dtype=np.float32)
+        if table.shape != (self.n, self.k):
+            raise ValueError(f"the embedding table is {(self.n, self.k)}, got {table.shape}")
+        self.X[:, :self.k] = torch.from_numpy(np.ascontiguousarray(table)).to(self.dev)

@@ -293,6 +293,17 @@ def _declare(lib):
         "lk_chol_upper_inverse": (
             c_int, [vp, c_int32, c_int32, vp, vp, c_int32, vp, c_int32, vp]
         ),
+        "lk_lgcn_propagate": (
+            c_int, [vp, vp, vp, c_int64, c_int64, ctypes.c_float, vp, ctypes.c_float, vp, c_int32,
+                    c_int32, vp, vp]
+        ),
+        "lk_lgcn_pair_grad_workspace_bytes": (c_size_t, [c_int64]),
+        "lk_lgcn_pair_grad": (
+            c_int, [vp, c_int64, c_int32, c_int32, c_int32, vp, vp, vp, c_int64, vp, vp, vp, vp, vp]
+        ),
+        "lk_adamw_dense": (
+            c_int, [vp, vp, vp, vp, c_int64, c_int32, c_int32] + [ctypes.c_double] * 7 + [vp]
+        ),
         "lk_als_implicit_half_epoch_host": (
             c_int,
             [vp, c_int, vp, vp, c_int64, c_int64, c_int32, vp, vp, vp, c_int32, vp],

@@ -19,8 +19,8 @@ FlexMF explicit -- ``FlexMFExplicitScorer`` / ``FlexMFExplicitConfig`` / ``FlexM
 (``lk_flexmf_step_explicit``); it predicts the ratings of ragged (user, item) lists through
 ``lk_mf_score_pairs`` instead of forming a row of scores per user.
 
-Not here: LightGCN (``convolution_layers > 0`` validates, and ``create_trainer`` raises
-``NotImplementedError``).
+Not here: the ``lightgcn`` preset (``convolution_layers > 0`` validates, and ``create_trainer``
+raises ``NotImplementedError``); the model itself is :class:`lkpy_amd.graphs.lightgcn.LightGCNScorer`.
 """
 
 from __future__ import annotations
@@ -234,7 +234,7 @@ class FlexMFTrainerBase(ModelTrainer):
 
     def __init__(self, scorer, data: Dataset, options: TrainingOptions):
         self.scorer = scorer
-        self.config = cfg = scorer.config
+        self.config = scorer.config
         self.check_data(data)
         # the NumPy generator first, then Torch's (_training.py:102-103): with a Generator as the
         # seed the Torch seed is that generator's next draw
@@ -248,12 +248,7 @@ class FlexMFTrainerBase(ModelTrainer):
         ds = self.matrix._ds
         self.n_users, self.n_items = data.user_count, data.item_count
         self.n_samples = ds.interaction_count  # repeated pairs stay separate samples
-        user_bias, item_bias = self.model_biases()
-        tabs = initial_tables(
-            self.n_users, self.n_items, cfg.embedding_size, self.torch_rng,
-            user_bias=user_bias, item_bias=item_bias,
-            user_counts=np.diff(ds._indptr), item_counts=np.bincount(ds._cols,
-                                                                     minlength=self.n_items))
+        tabs = self.initial_parameters(ds)
         self.state = self.create_state(tabs)
         self.d_users = torch.from_numpy(ds._rows).to(dev)
         self.d_items = torch.from_numpy(ds._cols).to(dev)
@@ -263,6 +258,15 @@ class FlexMFTrainerBase(ModelTrainer):
 
     def check_data(self, data: Dataset) -> None:
         "what the model needs of the data, said before any device work"
+
+    def initial_parameters(self, ds):
+        "the model's parameters as drawn from ``torch_rng``: what ``create_state`` uploads"
+        user_bias, item_bias = self.model_biases()
+        return initial_tables(
+            self.n_users, self.n_items, self.config.embedding_size, self.torch_rng,
+            user_bias=user_bias, item_bias=item_bias,
+            user_counts=np.diff(ds._indptr), item_counts=np.bincount(ds._cols,
+                                                                     minlength=self.n_items))
 
     def _set_host(self, tabs: dict):
         s = self.scorer
