@@ -582,6 +582,55 @@ int lk_csr_rows_dot(const void *d_indptr, int indptr_is_64, const int32_t *d_ind
                     const float *d_values, int64_t n_rows, const float *d_x, int64_t ld_x,
                     int64_t n_queries, float *d_out, int64_t ld_out, void *stream);
 
+/* ------------------------------------------------------------------------
+ * User-kNN for whole PANELS of queries, every item scored (csrc/uknn_recommend.hip): what
+ * `UserKNNScorer.__call__` (src/lenskit/knn/user.py:171-255) computes per query, as three
+ * asynchronous calls on `stream`.
+ * lk_uknn_query_panel: the dense query vectors of the histories d_hist_items[d_hist_ptr[q] ..
+ *   d_hist_ptr[q + 1]) (int64 offsets; items outside [0, n_items) are skipped), item-major:
+ *   x[item][q] (ld_x >= n_queries) = d_hist_ratings[e] - d_centre[q] (one f32 subtraction), or
+ *   1.0 when d_hist_ratings is NULL (implicit feedback; d_centre is not read); absent items 0.
+ *   A repeated item takes the value of its LAST occurrence (user.py:296-304's NumPy assignment).
+ * lk_uknn_sims_panel: lk_csr_rows_dot with the output USER-major, out[user][q] (ld_out >=
+ *   n_queries): the same fmaf chain over the stored row, the same bits.  d_self_user (may be
+ *   NULL) [n_queries]: the query's own user, -1 = none; that entry is written as +0.0
+ *   (user.py:192-194).
+ * lk_uknn_score_panel: out[q][item] (ld_out >= n_items), ready for lk_argtopn.  The ratings come
+ *   TRANSPOSED (lk_csr_transpose of the users x items matrix: items x users, int64 offsets, users
+ *   ascending in a row; d_t_values NULL = implicit feedback).  A cell walks its item's row in
+ *   stored order; every rater u with d_sims[u][q] >= thr (a NaN fails) offers (similarity,
+ *   rating) to the cell's own ScoreAccumulator (accum.rs:16-239, step for step: a vector while it
+ *   holds fewer than max_nbrs, then std's BinaryHeap, an entry displacing the minimum only when
+ *   strictly greater).  Cell = sum(w * v) / sum(w) + d_offset[q] (explicit; d_offset NULL = 0)
+ *   or sum(w) (implicit), sequential f32 sums in the accumulator's final array order, the product
+ *   rounded before it is added; fewer than min_nbrs entries (or none): NaN.  max_col_len: the
+ *   longest row of the transposed matrix (an accumulator is never given more slots than that;
+ *   a smaller value than the truth gives wrong scores, never a stray store).  d_item_order (may
+ *   be NULL) [n_items]: a permutation of the items, the order in which their tasks start
+ *   (heaviest first).  mark_history as lk_slim_score_batch, on the histories d_hist_ptr /
+ *   d_hist_items (may be NULL when 0): bit 0 turns the query's own items into NaN, bit 1 the
+ *   whole row of a query without a known history item.  Workspace:
+ *   lk_uknn_score_panel_workspace_bytes(max_nbrs, max_col_len) -- 0 (d_ws may be NULL) while
+ *   min(max_nbrs, max_col_len) <= lk_uknn_score_panel_lds_max_nbrs(), the accumulators then live
+ *   in LDS; above, in per-wave slabs of the workspace.  Every max_nbrs >= 1 is taken.
+ * ---------------------------------------------------------------------- */
+int lk_uknn_query_panel(const int64_t *d_hist_ptr, const int32_t *d_hist_items,
+                        const float *d_hist_ratings, const float *d_centre, int64_t n_queries,
+                        int64_t n_items, float *d_x, int64_t ld_x, void *stream);
+int lk_uknn_sims_panel(const void *d_indptr, int indptr_is_64, const int32_t *d_indices,
+                       const float *d_values, int64_t n_users, const float *d_x, int64_t ld_x,
+                       int64_t n_queries, const int32_t *d_self_user, float *d_out,
+                       int64_t ld_out, void *stream);
+int32_t lk_uknn_score_panel_lds_max_nbrs(void);
+size_t lk_uknn_score_panel_workspace_bytes(int32_t max_nbrs, int64_t max_col_len);
+int lk_uknn_score_panel(const int64_t *d_t_indptr, const int32_t *d_t_users,
+                        const float *d_t_values, int64_t n_items, int64_t n_users,
+                        int64_t max_col_len, const int32_t *d_item_order, const float *d_sims,
+                        int64_t ld_sims, int64_t n_queries, float thr, int32_t max_nbrs,
+                        int32_t min_nbrs, const float *d_offset, const int64_t *d_hist_ptr,
+                        const int32_t *d_hist_items, int mark_history, void *d_ws, float *d_out,
+                        int64_t ld_out, void *stream);
+
 /* Device -> pageable host memory at PCIe speed: chunks through a ring of pinned staging slots,
  * a team of `n_threads` host threads (<= 14; 0 = 8) copies the landed chunks to `h_dst` in
  * parallel (first-touching its pages on many cores).  Used for results the reference hands

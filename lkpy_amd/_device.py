@@ -1010,6 +1010,140 @@ def csr_rows_dot(csr: DeviceCSR, x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def uknn_query_panel(hist: DeviceCSR, centre: torch.Tensor | None, *, ld: int | None = None,
+                     rows: tuple[int, int] | None = None) -> torch.Tensor:
+    """
+    The dense query vectors of the histories ``hist`` (queries x items, int64 offsets, -1 =
+    unknown item) built on the device (lk_uknn_query_panel): X [items x ld] f32, item-major as
+    ``csr_rows_dot`` reads it.  With values: ``rating - centre[q]`` (``centre`` device f32 per
+    query of ``hist``); without: 1.0.  A repeated item keeps its last occurrence.
+    ``rows = (lo, hi)``: those queries only (column 0 is query ``lo``).
+    """
+    lib = _native.require_gpu()
+    n_items = int(hist.shape[1])
+    lo, hi = (0, int(hist.indptr.shape[0]) - 1) if rows is None else (int(rows[0]), int(rows[1]))
+    assert 0 <= lo <= hi < int(hist.indptr.shape[0])
+    P = hi - lo
+    ld = P if ld is None else int(ld)
+    assert ld >= P
+    assert hist.indptr.dtype == torch.int64 and hist.indptr.is_contiguous()
+    assert hist.indices.dtype == torch.int32 and hist.indices.is_contiguous()
+    if hist.values is not None:
+        assert hist.values.dtype == torch.float32 and hist.values.is_contiguous()
+        assert centre is not None and centre.dtype == torch.float32 and centre.is_contiguous()
+        assert centre.numel() == int(hist.indptr.shape[0]) - 1
+        assert centre.device == hist.indices.device
+    x = torch.empty((n_items, ld), dtype=torch.float32, device=hist.indices.device)
+    if ld > P:
+        x[:, P:] = 0.0
+    check(
+        lib.lk_uknn_query_panel(_ptr(hist.indptr[lo:]), _ptr(hist.indices), _ptr(hist.values),
+                                _ptr(centre[lo:]) if hist.values is not None else None, P,
+                                n_items, _ptr(x), ld, _stream()),
+        "lk_uknn_query_panel",
+    )
+    return x
+
+
+def uknn_sims_panel(vectors: DeviceCSR, x: torch.Tensor, self_user: torch.Tensor | None = None,
+                    *, queries: int | None = None, ld: int | None = None) -> torch.Tensor:
+    """
+    ``sims[u][q] = <row u of vectors, x[:, q]>`` for the first ``queries`` columns of ``x``
+    ([items x ld_x] f32), USER-major [users x ld] (lk_uknn_sims_panel): ``csr_rows_dot``'s bits,
+    transposed.  ``self_user`` (device int32 per query, -1 = none): that entry is +0.0.
+    """
+    lib = _native.require_gpu()
+    n_users, n_items = vectors.shape
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 2
+    assert x.shape[0] == n_items and x.device == vectors.indices.device
+    P = int(x.shape[1]) if queries is None else int(queries)
+    assert 0 <= P <= int(x.shape[1])
+    ld = P if ld is None else int(ld)
+    assert ld >= P
+    assert vectors.values is not None and vectors.values.dtype == torch.float32
+    assert vectors.indices.dtype == torch.int32
+    if self_user is not None:
+        assert self_user.dtype == torch.int32 and self_user.is_contiguous()
+        assert self_user.numel() == P and self_user.device == x.device
+    out = torch.empty((n_users, ld), dtype=torch.float32, device=x.device)
+    check(
+        lib.lk_uknn_sims_panel(_ptr(vectors.indptr), 1 if vectors.is64 else 0,
+                               _ptr(vectors.indices), _ptr(vectors.values), n_users, _ptr(x),
+                               int(x.shape[1]), P, _ptr(self_user), _ptr(out), ld, _stream()),
+        "lk_uknn_sims_panel",
+    )
+    return out
+
+
+def uknn_lds_max_nbrs() -> int:
+    "The largest ``max_nbrs`` whose accumulators ``lk_uknn_score_panel`` keeps in LDS."
+    return int(_native.load().lk_uknn_score_panel_lds_max_nbrs())
+
+
+def uknn_score_panel(ratings_t: DeviceCSR, sims: torch.Tensor, queries: int, thr: float,
+                     max_nbrs: int, min_nbrs: int, offset: torch.Tensor | None = None, *,
+                     hist: DeviceCSR | None = None, rows: tuple[int, int] | None = None,
+                     strike_history: bool = False, nan_empty: bool = False,
+                     item_order: torch.Tensor | None = None, max_col: int | None = None,
+                     out: torch.Tensor | None = None) -> torch.Tensor:
+    """
+    The user-kNN score panel [queries x n_items] of ``lk_uknn_score_panel``, as ``argtopn`` wants
+    it.  ``ratings_t``: the transposed centred ratings (items x users, int64 offsets, users
+    ascending; ``values`` None = implicit feedback); ``sims``: the user-major panel of
+    :func:`uknn_sims_panel` (its first ``queries`` columns); ``thr``: the float32 ``min_sim``;
+    ``offset``: device f32 per query, added to explicit scores.  ``hist`` / ``rows = (lo, hi)``:
+    the histories of the panel's queries are rows ``lo .. hi`` of ``hist``; ``strike_history``
+    makes their items NaN, ``nan_empty`` the row of a query without a known item.
+    ``item_order``: device int32 permutation of the items (heaviest column first);
+    ``max_col``: the longest column (read from the device when not given).  ``out``: write into
+    the first ``n_items`` columns of this [queries x ld] f32 device matrix (ld >= n_items) instead
+    of a fresh panel; the other columns are left alone.
+    """
+    lib = _native.require_gpu()
+    n_items, n_users = ratings_t.shape
+    dev = sims.device
+    P = int(queries)
+    assert ratings_t.indptr.dtype == torch.int64 and ratings_t.indptr.is_contiguous()
+    assert ratings_t.indices.dtype == torch.int32 and ratings_t.indices.device == dev
+    assert ratings_t.values is None or (ratings_t.values.dtype == torch.float32 and
+                                        ratings_t.values.is_contiguous())
+    assert sims.dtype == torch.float32 and sims.is_contiguous() and sims.dim() == 2
+    assert sims.shape[0] == n_users and 0 <= P <= int(sims.shape[1])
+    if offset is not None:
+        assert offset.dtype == torch.float32 and offset.is_contiguous() and offset.numel() == P
+        assert offset.device == dev
+    if item_order is not None:
+        assert item_order.dtype == torch.int32 and item_order.is_contiguous()
+        assert item_order.numel() == n_items and item_order.device == dev
+    mark = (1 if strike_history else 0) | (2 if nan_empty else 0)
+    h_ptr = h_idx = None
+    if mark:
+        assert hist is not None and hist.indptr.dtype == torch.int64
+        assert hist.indices.dtype == torch.int32 and hist.indices.device == dev
+        lo, hi = (0, int(hist.indptr.shape[0]) - 1) if rows is None else \
+            (int(rows[0]), int(rows[1]))
+        assert 0 <= lo <= hi < int(hist.indptr.shape[0]) and hi - lo == P
+        h_ptr, h_idx = hist.indptr[lo:], hist.indices
+    if max_col is None:
+        max_col = int(torch.diff(ratings_t.indptr).max()) if n_items else 0
+    if out is None:
+        out = torch.empty((P, n_items), dtype=torch.float32, device=dev)
+    assert out.dtype == torch.float32 and out.dim() == 2 and out.is_contiguous()
+    assert out.shape[0] == P and out.shape[1] >= n_items and out.device == dev
+    wb = lib.lk_uknn_score_panel_workspace_bytes(int(max_nbrs), int(max_col))
+    ws = torch.empty(wb, dtype=torch.uint8, device=dev) if wb else None
+    check(
+        lib.lk_uknn_score_panel(_ptr(ratings_t.indptr), _ptr(ratings_t.indices),
+                                _ptr(ratings_t.values), n_items, n_users, int(max_col),
+                                _ptr(item_order), _ptr(sims), int(sims.shape[1]), P, float(thr),
+                                int(max_nbrs), int(min_nbrs), _ptr(offset), _ptr(h_ptr),
+                                _ptr(h_idx), mark, _ptr(ws), _ptr(out), int(out.shape[1]),
+                                _stream()),
+        "lk_uknn_score_panel",
+    )
+    return out
+
+
 def ease_gram(cooc: DeviceCSR, item_counts: torch.Tensor, reg: float) -> torch.Tensor:
     """
     ``X^T X + reg I`` as a dense [n x n] f32 device matrix (lk_ease_gram) from the off-diagonal

@@ -178,6 +178,17 @@ def _declare(lib):
         "lk_csr_rows_dot": (
             c_int, [vp, c_int, vp, vp, c_int64, vp, c_int64, c_int64, vp, c_int64, vp]
         ),
+        "lk_uknn_query_panel": (c_int, [vp, vp, vp, vp, c_int64, c_int64, vp, c_int64, vp]),
+        "lk_uknn_sims_panel": (
+            c_int, [vp, c_int, vp, vp, c_int64, vp, c_int64, c_int64, vp, vp, c_int64, vp]
+        ),
+        "lk_uknn_score_panel_lds_max_nbrs": (c_int32, []),
+        "lk_uknn_score_panel_workspace_bytes": (c_size_t, [c_int32, c_int64]),
+        "lk_uknn_score_panel": (
+            c_int,
+            [vp, vp, vp, c_int64, c_int64, c_int64, vp, vp, c_int64, c_int64, c_float, c_int32,
+             c_int32, vp, vp, vp, c_int, vp, vp, c_int64, vp],
+        ),
         "lk_download": (c_int, [vp, vp, c_size_t, c_int32, vp]),
         "lk_download_warmup": (c_int, []),
         "lk_download_i32_narrow": (c_int, [vp, vp, c_int64, vp, c_int32, vp]),

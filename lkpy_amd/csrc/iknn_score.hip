@@ -35,6 +35,7 @@
 // rounded separately) give the reference's bits.  Queries with long histories are started first
 // and split into parts by target (see the kernel).  1.3 ms for the cfg3 batch.
 #include "common.h"
+#include "knn_accum.h"  // KfHeap, kf_offer: the reference's accumulator for one lane
 
 // The reference's sums are plain f32 multiplies and adds (Rust never contracts a * b + c): no
 // FMA contraction anywhere in this file, so that `weight * value` is rounded before it is added.
@@ -53,52 +54,6 @@ __host__ __device__ inline size_t ks_slab_bytes(int64_t n_items, int max_nbrs)
                  (size_t)n_items * ((size_t)max_nbrs + 1) * 2 * sizeof(float);
     return (per + 255) / 256 * 256;
 }
-
-// ---- the reference's accumulator, restated for ONE lane (arrays in LDS or in the slab) ---------
-// `Full(BinaryHeap<AccEntry>)` with the REVERSED ordering of accum.rs:170-184: a min-heap on
-// the weight.  std's BinaryHeap::push = sift_up(0, old_len); pop = swap the last element into
-// the root, sift_down_to_bottom(0), sift_up.  Followed step for step so that WHICH of several
-// equal weights is evicted, and the array order the sums run over, are the reference's.
-struct KfHeap {
-    float *w, *v;
-    int len;
-    __device__ __forceinline__ void sift_up(int pos, float ew, float ev)
-    {
-        while (pos > 0) {
-            const int parent = (pos - 1) >> 1;
-            if (ew >= w[parent]) break;  // hole.element() <= hole.get(parent) in reversed order
-            w[pos] = w[parent];
-            v[pos] = v[parent];
-            pos = parent;
-        }
-        w[pos] = ew;
-        v[pos] = ev;
-    }
-    __device__ __forceinline__ void push(float ew, float ev) { sift_up(len++, ew, ev); }
-    __device__ __forceinline__ void pop()
-    {
-        const float ew = w[len - 1], ev = v[len - 1];
-        --len;
-        if (len == 0) return;
-        const int end = len;
-        int pos = 0, child = 1;
-        const int limit = end >= 2 ? end - 2 : 0;
-        while (child <= limit && end >= 2) {
-            if (w[child] >= w[child + 1]) child += 1;  // hole.get(child) <= hole.get(child + 1)
-            w[pos] = w[child];
-            v[pos] = v[child];
-            pos = child;
-            child = 2 * pos + 1;
-        }
-        if (child == end - 1) {
-            w[pos] = w[child];
-            v[pos] = v[child];
-            pos = child;
-        }
-        sift_up(pos, ew, ev);
-    }
-};
-
 
 // SWAP = false: item-kNN (matrix = similarities, entry value = weight, the reference row's
 // rating = value).  SWAP = true: user-kNN (`user_score_items_*`,
@@ -157,32 +112,11 @@ __global__ __launch_bounds__(KS_THREADS) void iknn_score_kernel(
                 }
                 float *ss = slot_s + (size_t)t * stride;
                 float *sv = slot_v + (size_t)t * stride;
-                const bool heap = is_heap[t] != 0;
-                if (!heap && c < max_nbrs) {  // Partial(vec): push (accum.rs:103-104)
-                    ss[c] = s;
-                    sv[c] = rv;
-                    cnt[t] = c + 1;
-                } else {  // Full(heap): the reference's BinaryHeap, step for step
-                    KfHeap h{ss, sv, c};
-                    if (!heap) {
-                        // Partial -> Full (heap_mut, accum.rs:76-83): the vector is popped from the
-                        // back and every element pushed onto an empty heap = reverse it in place,
-                        // then sift element k up into the heap formed by the k before it
-                        for (int i = 0, j = c - 1; i < j; ++i, --j) {
-                            const float a = ss[i], b = sv[i];
-                            ss[i] = ss[j];
-                            sv[i] = sv[j];
-                            ss[j] = a;
-                            sv[j] = b;
-                        }
-                        for (int kk = 1; kk < c; ++kk) h.sift_up(kk, ss[kk], sv[kk]);
-                        is_heap[t] = 1;
-                    }
-                    if (s > ss[0]) {  // accum.rs:108: strictly greater than the minimum
-                        h.push(s, rv);
-                        while (h.len > max_nbrs) h.pop();
-                    }
-                }
+                int cn = c;
+                bool heap = is_heap[t] != 0;
+                kf_offer(ss, sv, cn, heap, max_nbrs, s, rv);  // (accum.rs:99-117)
+                cnt[t] = cn;
+                is_heap[t] = heap ? 1 : 0;
             }
             __syncthreads();
         }
@@ -528,7 +462,7 @@ __global__ __launch_bounds__(KF_THREADS) void iknn_score_fast_kernel(
                             __builtin_amdgcn_wave_barrier();
                         }
                         if (lane == 0) {
-                            KfHeap h{hw[wave], hv[wave], len};
+                            KfHeap<> h{hw[wave], hv[wave], len};
                             if (!full) {
                                 h.len = 0;
                                 for (int i = len - 1; i >= 0; --i) h.push(tw_[wave][i], tv_[wave][i]);

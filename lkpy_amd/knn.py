@@ -9,6 +9,13 @@ Item-based k-NN: mirror of ``lenskit.knn.ItemKNNScorer`` /
 ``ItemKNNConfig`` (src/lenskit/knn/item.py:41-295).  Matrix preparation is the reference's
 own SciPy code path (item-mean centring, L2 normalisation); the similarity build and the
 scoring run in the HIP kernels.
+
+User-based k-NN scores candidate lists through ``lk_csr_rows_dot`` + ``lk_uknn_score_batch``
+(``score_batch``) and EVERY item for panels of queries through csrc/uknn_recommend.hip
+(``recommend_batch`` / ``dense_scores_batch``, the loops of :class:`_PanelScorer`): the query
+vectors built on the device, the neighbour similarities user-major, and each (query, item) cell a
+gather from the transposed ratings into the reference's accumulator.
+``batch.recommend`` takes that path, as it takes item-kNN's, SLIM's and the association rules'.
 """
 
 from __future__ import annotations
@@ -260,6 +267,104 @@ class ItemKNNScorer(Component):
 
 
 # ---------------------------------------------------------------------------------------
+# Panel scorers: a sparse model in HBM, every item scored for a panel of queries at a time
+# ---------------------------------------------------------------------------------------
+
+
+class _PanelScorer:
+    """
+    What ``SLIMScorer``, ``AssociationScorer`` and ``UserKNNScorer`` share, beside
+    :class:`Component`: the model is a sparse matrix in HBM (item-item; user-kNN: the transposed
+    ratings), a kernel call scores every item for a range of queries (a [rows x items] float32
+    panel), and a batch goes through in panels of at most ``PANEL_BYTES``.
+    A subclass supplies ``items``, :meth:`_device_matrix` and :meth:`_score_panel`.
+    """
+
+    PANEL_BYTES = 1 << 30  # score panel of one recommend / score step
+    accepts_history_batch = True  # recommend_batch takes a lkpy_amd.basic.HistoryBatch
+
+    def _device_matrix(self) -> D.DeviceCSR:
+        "The model matrix in HBM (int64 offsets), uploaded once per model."
+        raise NotImplementedError
+
+    def _score_panel(self, hist: D.DeviceCSR, rows, *, strike_history: bool, nan_empty: bool):
+        "One kernel call: the device panel of the queries ``rows = (lo, hi)`` of ``hist``."
+        raise NotImplementedError
+
+    def _panel_rows(self) -> int:
+        return max(1, self.PANEL_BYTES // (4 * max(len(self.items), 1)))
+
+    def _query_csr(self, queries: list[RecQuery]) -> D.DeviceCSR:
+        "The histories of a list of queries in query order, uploaded: item numbers, -1 = unknown."
+        ptr, idx, _ = pack_histories(queries, self.items, unknown="keep")
+        return D.DeviceCSR.from_arrays(ptr, idx, None, (len(queries), len(self.items)),
+                                       self._device_matrix().indices.device)
+
+    def _batch_csr(self, queries) -> D.DeviceCSR:
+        "The histories of a batch as a device CSR: a HistoryBatch's training rows, or a list's."
+        queries = resolve_queries(queries, self.items)
+        if isinstance(queries, HistoryBatch):
+            return queries.csr(with_values=False)
+        return self._query_csr(queries)
+
+    def _score_lists(self, hist: D.DeviceCSR, item_lists, *, nan_empty: bool, score_panel=None):
+        """
+        The loop of ``score_batch``: each panel of ``hist`` scored (by ``score_panel``, called
+        like :meth:`_score_panel`, which it defaults to) and downloaded, each list's scores read
+        out of its query's row.  ``nan_empty``: the kernel makes the row of a query without a
+        known history item NaN; else an empty row of ``hist`` (a query CSR: the host has its
+        offsets) is told here.
+        """
+        score_panel = score_panel or self._score_panel
+        out = []
+        step = self._panel_rows()
+        for lo in range(0, len(item_lists), step):
+            hi = min(len(item_lists), lo + step)
+            panel = D.to_host(score_panel(hist, (lo, hi), strike_history=False,
+                                          nan_empty=nan_empty))
+            for i in range(lo, hi):
+                items = item_lists[i]
+                if not nan_empty and hist.h_indptr[i] == hist.h_indptr[i + 1]:
+                    out.append(ItemList(items, scores=np.nan))
+                    continue
+                out.append(ItemList(items, scores=item_scores(items, self.items, panel[i - lo])))
+        return out
+
+    def __call__(self, query, items: ItemList) -> ItemList:
+        return self.score_batch([query], [items])[0]
+
+    def recommend_batch(self, queries, n: int | None, *, exclude_history: bool = True):
+        """
+        Top-``n`` lists for many queries at once -- what the ``recommender`` pipeline computes one
+        query at a time: candidates = every training item minus the query's own
+        (src/lenskit/basic/candidates.py:77-94), this scorer over them, ``TopNRanker``
+        (basic/topn.py:45-69).  Items no history item points at score 0.0 and are listed when
+        fewer than ``n`` score above it; a query without a known history item gets an empty list.
+        ``queries``: a list of queries, or a :class:`lkpy_amd.basic.HistoryBatch` (training
+        histories by user number, cut out of the HBM-resident training matrix).  The batch goes
+        through in panels of at most ``PANEL_BYTES``, each selected from by ``lk_argtopn``.
+        ``n`` negative or None: every candidate, ranked.  Returns (item numbers [B x n] with -1
+        padding, scores [B x n] with NaN padding), like ``ItemKNNScorer.recommend_batch``.
+        """
+        hist = self._batch_csr(queries)
+        d = self._device_matrix().indices.device
+        B = hist.shape[0]
+        n = -1 if n is None else int(n)
+        cols = len(self.items) if n < 0 else n
+        oi = torch.full((B, cols), -1, dtype=torch.int32, device=d)
+        osc = torch.full((B, cols), float("nan"), dtype=torch.float32, device=d)
+        step = self._panel_rows()
+        for lo in range(0, B, step):
+            hi = min(B, lo + step)
+            panel = self._score_panel(hist, (lo, hi), strike_history=exclude_history,
+                                      nan_empty=True)
+            idx = D.argtopn(panel, n)
+            oi[lo:hi, :idx.shape[1]] = idx
+            osc[lo:hi, :idx.shape[1]] = D.take_scores(panel, idx)
+        return D.lists_to_host(oi, osc)
+
+
+# ---------------------------------------------------------------------------------------
 # User-based k-NN (SURVEY.md section 8f, rank 4)
 # ---------------------------------------------------------------------------------------
 
@@ -282,7 +387,7 @@ class UserKNNConfig(BaseModel, extra="forbid"):
         return self.feedback == "explicit"
 
 
-class UserKNNScorer(Component):
+class UserKNNScorer(_PanelScorer, Component):
     """
     User-user nearest-neighbour collaborative filtering (``UserKNNScorer``,
     src/lenskit/knn/user.py:74-316).  "Training" memorises the mean-centred and the
@@ -290,7 +395,15 @@ class UserKNNScorer(Component):
     device for whole batches of queries: neighbour similarities = normalised matrix x query
     vector (``lk_csr_rows_dot``), neighbours with sim >= min_sim in ascending user order,
     per-item accumulation of the ``max_nbrs`` most similar raters (``lk_uknn_score_batch``).
+
+    ``recommend_batch`` / ``dense_scores_batch`` score EVERY item for panels of queries
+    (:class:`_PanelScorer`; csrc/uknn_recommend.hip): the query vectors are built on the device
+    (``lk_uknn_query_panel``), the similarities come user-major (``lk_uknn_sims_panel``), and
+    each (query, item) cell gathers the item's raters from the transposed ratings into its own
+    accumulator (``lk_uknn_score_panel``) -- the bits ``score_batch`` gives the same query.
     """
+
+    PANEL_BYTES = 1 << 30  # the query, similarity and score panels of one step, together
 
     config: UserKNNConfig
 
@@ -417,6 +530,155 @@ class UserKNNScorer(Component):
     def __call__(self, query, items: ItemList) -> ItemList:
         return self.score_batch([query], [items])[0]
 
+    # -- every item for panels of queries (csrc/uknn_recommend.hip) ---------------------------
+    def _panel_rows(self) -> int:
+        "Queries per panel: X [items x P], sims [users x P] and scores [P x items] live at once."
+        per = 4 * (2 * len(self.items) + len(self.users))
+        return max(64, self.PANEL_BYTES // max(per, 1) // 64 * 64)
+
+    def _device_transposed(self):
+        """
+        The centred ratings transposed in HBM (items x users, users ascending: ``lk_csr_transpose``
+        is stable), once per model, with the items ordered by falling rater count (the order in
+        which ``lk_uknn_score_panel`` starts its columns) and the longest column.
+        """
+        def build():
+            from .matrix import csr_arrays
+
+            rt = D.csr_transpose(self._device_state()["ratings"], with_values=self.config.explicit)
+            rt.perm = None  # (the permutation is as large as the values: not kept)
+            counts = np.bincount(csr_arrays(self.user_ratings)[1], minlength=len(self.items))
+            order = np.argsort(-counts, kind="stable").astype(np.int32)
+            return {"ratings_t": rt, "order": torch.from_numpy(order).to(rt.indices.device),
+                    "max_col": int(counts.max()) if len(counts) else 0}
+
+        return self._device_cache("ratings_t", build, self.user_ratings)
+
+    def _device_matrix(self) -> D.DeviceCSR:
+        return self._device_transposed()["ratings_t"]
+
+    def _history_centres(self, lookup) -> np.ndarray:
+        """
+        What the reference centres a PROVIDED history by (user.py:281-304): ``urv.mean()`` of the
+        history's float32 ratings -- NumPy's pairwise float32 sum, not the training mean -- for
+        every training row of ``lookup``, by the same NumPy call.  Host float32 per user, computed
+        once per (lookup matrix, scorer); a user without ratings gets 0.
+        """
+        def build():
+            ds = lookup.interactions._ds
+            rat, hp = ds._attrs["rating"], ds._indptr
+            out = np.zeros(len(hp) - 1, dtype=np.float32)
+            for u in range(len(out)):
+                if hp[u + 1] > hp[u]:
+                    out[u] = np.require(rat[hp[u]:hp[u + 1]], dtype=np.float32).mean()
+            return out
+
+        return self._device_cache("centres", build, lookup.interactions, self.user_ratings)
+
+    def _device_centres(self, lookup) -> torch.Tensor:
+        "``_history_centres`` in HBM, one upload per (lookup matrix, scorer)."
+        return self._device_cache(
+            "centres_dev", lambda: torch.from_numpy(self._history_centres(lookup)).to(
+                self._device_state()["device"]), lookup.interactions, self.user_ratings)
+
+    def _batch_csr(self, queries) -> D.DeviceCSR:
+        """
+        The queries of a batch as :meth:`_score_panel` takes them: the device CSR of their
+        histories (item numbers, -1 = unknown: what is struck) carrying ``self_user`` (device
+        int32, this scorer's number of the query's user or -1), ``centre`` (device f32, the mean
+        the history is centred by = the offset of the scores; None if implicit), ``valid`` (host
+        bool: the query has data to score from) and ``x_rows``.  A :class:`HistoryBatch` is cut
+        out of the HBM-resident training matrix with its ratings (``x_rows`` None: the query
+        vectors are built on the device); a list of queries goes through :meth:`_user_data` per
+        query, stored-vector branch included, and ``x_rows`` holds the dense host rows.
+        """
+        from ._queries import user_numbers
+
+        queries = resolve_queries(queries, self.items)
+        d = self._device_state()["device"]
+        explicit = self.config.explicit
+        if isinstance(queries, HistoryBatch):
+            if explicit and not queries.has_ratings:
+                raise RuntimeError("explicit-feedback scorer must have ratings")
+            hist = queries.csr(use_ratings=explicit, with_values=explicit)
+            hist = D.DeviceCSR(hist.indptr, hist.indices, hist.values, hist.shape, hist.h_indptr)
+            hist.x_rows = None
+            hist.valid = queries.lengths > 0
+            hist.centre = None
+            if explicit:
+                nums = torch.from_numpy(np.maximum(queries.user_nums, 0).astype(np.int64)).to(d)
+                hist.centre = self._device_centres(queries.lookup)[nums].contiguous()
+            selves = user_numbers(queries, self.users)
+        else:
+            data = [self._user_data(q) for q in queries]
+            ptr, idx, _ = pack_histories(queries, self.items, unknown="keep")
+            hist = D.DeviceCSR.from_arrays(ptr, idx, None, (len(queries), len(self.items)), d)
+            hist.x_rows = [None if u is None else u[1] for u in data]
+            hist.valid = np.array([u is not None for u in data], dtype=bool)
+            hist.centre = None
+            if explicit:
+                hist.centre = torch.from_numpy(np.array(
+                    [0.0 if u is None else u[2] for u in data], dtype=np.float32)).to(d)
+            selves = [-1 if u is None or u[0] is None else u[0] for u in data]
+        hist.self_user = torch.from_numpy(np.asarray(selves, dtype=np.int32)).to(d)
+        return hist
+
+    def _score_panel(self, hist, rows, *, strike_history: bool, nan_empty: bool = False):
+        """
+        The device panel of the queries ``rows = (lo, hi)`` of ``hist`` (:meth:`_batch_csr`): query
+        panel -> similarities -> scores.  ``nan_empty`` is not passed on: a known user without a
+        history is scored from the stored vector, and the row of a query without neighbours --
+        an unknown user, an empty history -- is NaN cell by cell (fewer than ``min_nbrs``).
+        """
+        st, tr = self._device_state(), self._device_transposed()
+        lo, hi = (0, hist.shape[0]) if rows is None else (int(rows[0]), int(rows[1]))
+        if hist.x_rows is None:
+            x = D.uknn_query_panel(hist, hist.centre, rows=(lo, hi))
+        else:
+            X = np.zeros((len(self.items), hi - lo), dtype=np.float32)
+            for j, row in enumerate(hist.x_rows[lo:hi]):
+                if row is not None:
+                    X[:, j] = row
+            x = torch.from_numpy(X).to(st["device"])
+        sims = D.uknn_sims_panel(st["vectors"], x, hist.self_user[lo:hi])
+        del x
+        return D.uknn_score_panel(
+            tr["ratings_t"], sims, hi - lo, float(np.float32(self.config.min_sim)),
+            self.config.max_nbrs, self.config.min_nbrs,
+            None if hist.centre is None else hist.centre[lo:hi], hist=hist, rows=(lo, hi),
+            strike_history=strike_history, item_order=tr["order"], max_col=tr["max_col"])
+
+    def recommend_batch(self, queries, n: int | None, *, exclude_history: bool = True):
+        """
+        Top-``n`` lists for many queries at once -- what the ``recommender`` pipeline computes one
+        query at a time: candidates = every training item minus the query's own
+        (src/lenskit/basic/candidates.py:77-94), this scorer over them (user.py:171-262, the
+        query's mean added back), ``TopNRanker`` (basic/topn.py:45-69).  Items with fewer than
+        ``min_nbrs`` passing raters are never listed; an unknown user without history, an empty
+        history and a query without neighbours get an empty list.  ``queries``: a list of queries,
+        or a :class:`lkpy_amd.basic.HistoryBatch` (training histories by user number, nothing done
+        per query on the host).  The batch goes through in panels (:meth:`_panel_rows`), each
+        selected from by ``lk_argtopn``.  ``n`` negative or None: every scorable candidate,
+        ranked.  Returns (item numbers [B x n] with -1 padding, scores [B x n] with NaN padding).
+        """
+        return super().recommend_batch(queries, n, exclude_history=exclude_history)
+
+    def dense_scores_batch(self, queries):
+        """
+        Every item's score for many queries at once, left on the device: (panel f32 [B x items],
+        valid, history CSR), the contract of ``AssociationScorer.dense_scores_batch``.  The row of
+        a query that cannot be scored is NaN (``valid`` False: no data to score from); the history
+        CSR (known items, ascending) is for the caller to exclude.  The caller bounds the batch.
+        """
+        queries = resolve_queries(queries, self.items)
+        hist = self._batch_csr(queries)
+        if isinstance(queries, HistoryBatch):
+            excl = queries.csr(with_values=False)  # training rows: known items, ascending
+        else:
+            ptr, idx, _ = pack_histories(queries, self.items, unknown="drop", sort=True)
+            excl = D.DeviceCSR.from_arrays(ptr, idx, None, hist.shape, hist.indices.device)
+        return self._score_panel(hist, None, strike_history=False), hist.valid, excl
+
 
 def _binary_cooccurrence(data: Dataset):
     """
@@ -508,103 +770,6 @@ class EASEScorer(Component):
 
     def __call__(self, query, items: ItemList) -> ItemList:
         return self.score_batch([query], [items])[0]
-
-
-# ---------------------------------------------------------------------------------------
-# Panel scorers: a sparse item-item model, every item scored for a panel of queries at a time
-# ---------------------------------------------------------------------------------------
-
-
-class _PanelScorer:
-    """
-    What ``SLIMScorer`` and ``AssociationScorer`` share, beside :class:`Component`: the model is a
-    sparse item-item matrix in HBM, a kernel call scores every item for a range of queries (a
-    [rows x items] float32 panel), and a batch goes through in panels of at most ``PANEL_BYTES``.
-    A subclass supplies ``items``, :meth:`_device_matrix` and :meth:`_score_panel`.
-    """
-
-    PANEL_BYTES = 1 << 30  # score panel of one recommend / score step
-    accepts_history_batch = True  # recommend_batch takes a lkpy_amd.basic.HistoryBatch
-
-    def _device_matrix(self) -> D.DeviceCSR:
-        "The model matrix in HBM (int64 offsets), uploaded once per model."
-        raise NotImplementedError
-
-    def _score_panel(self, hist: D.DeviceCSR, rows, *, strike_history: bool, nan_empty: bool):
-        "One kernel call: the device panel of the queries ``rows = (lo, hi)`` of ``hist``."
-        raise NotImplementedError
-
-    def _panel_rows(self) -> int:
-        return max(1, self.PANEL_BYTES // (4 * max(len(self.items), 1)))
-
-    def _query_csr(self, queries: list[RecQuery]) -> D.DeviceCSR:
-        "The histories of a list of queries in query order, uploaded: item numbers, -1 = unknown."
-        ptr, idx, _ = pack_histories(queries, self.items, unknown="keep")
-        return D.DeviceCSR.from_arrays(ptr, idx, None, (len(queries), len(self.items)),
-                                       self._device_matrix().indices.device)
-
-    def _batch_csr(self, queries) -> D.DeviceCSR:
-        "The histories of a batch as a device CSR: a HistoryBatch's training rows, or a list's."
-        queries = resolve_queries(queries, self.items)
-        if isinstance(queries, HistoryBatch):
-            return queries.csr(with_values=False)
-        return self._query_csr(queries)
-
-    def _score_lists(self, hist: D.DeviceCSR, item_lists, *, nan_empty: bool, score_panel=None):
-        """
-        The loop of ``score_batch``: each panel of ``hist`` scored (by ``score_panel``, called
-        like :meth:`_score_panel`, which it defaults to) and downloaded, each list's scores read
-        out of its query's row.  ``nan_empty``: the kernel makes the row of a query without a
-        known history item NaN; else an empty row of ``hist`` (a query CSR: the host has its
-        offsets) is told here.
-        """
-        score_panel = score_panel or self._score_panel
-        out = []
-        step = self._panel_rows()
-        for lo in range(0, len(item_lists), step):
-            hi = min(len(item_lists), lo + step)
-            panel = D.to_host(score_panel(hist, (lo, hi), strike_history=False,
-                                          nan_empty=nan_empty))
-            for i in range(lo, hi):
-                items = item_lists[i]
-                if not nan_empty and hist.h_indptr[i] == hist.h_indptr[i + 1]:
-                    out.append(ItemList(items, scores=np.nan))
-                    continue
-                out.append(ItemList(items, scores=item_scores(items, self.items, panel[i - lo])))
-        return out
-
-    def __call__(self, query, items: ItemList) -> ItemList:
-        return self.score_batch([query], [items])[0]
-
-    def recommend_batch(self, queries, n: int | None, *, exclude_history: bool = True):
-        """
-        Top-``n`` lists for many queries at once -- what the ``recommender`` pipeline computes one
-        query at a time: candidates = every training item minus the query's own
-        (src/lenskit/basic/candidates.py:77-94), this scorer over them, ``TopNRanker``
-        (basic/topn.py:45-69).  Items no history item points at score 0.0 and are listed when
-        fewer than ``n`` score above it; a query without a known history item gets an empty list.
-        ``queries``: a list of queries, or a :class:`lkpy_amd.basic.HistoryBatch` (training
-        histories by user number, cut out of the HBM-resident training matrix).  The batch goes
-        through in panels of at most ``PANEL_BYTES``, each selected from by ``lk_argtopn``.
-        ``n`` negative or None: every candidate, ranked.  Returns (item numbers [B x n] with -1
-        padding, scores [B x n] with NaN padding), like ``ItemKNNScorer.recommend_batch``.
-        """
-        hist = self._batch_csr(queries)
-        d = self._device_matrix().indices.device
-        B = hist.shape[0]
-        n = -1 if n is None else int(n)
-        cols = len(self.items) if n < 0 else n
-        oi = torch.full((B, cols), -1, dtype=torch.int32, device=d)
-        osc = torch.full((B, cols), float("nan"), dtype=torch.float32, device=d)
-        step = self._panel_rows()
-        for lo in range(0, B, step):
-            hi = min(B, lo + step)
-            panel = self._score_panel(hist, (lo, hi), strike_history=exclude_history,
-                                      nan_empty=True)
-            idx = D.argtopn(panel, n)
-            oi[lo:hi, :idx.shape[1]] = idx
-            osc[lo:hi, :idx.shape[1]] = D.take_scores(panel, idx)
-        return D.lists_to_host(oi, osc)
 
 
 # ---------------------------------------------------------------------------------------
