@@ -664,6 +664,61 @@ int lk_ease_gram(const int64_t *d_cooc_indptr, const int32_t *d_cooc_indices,
 int lk_ease_score_batch(const int64_t *d_hist_ptr, const int32_t *d_hist_items,
                         int64_t n_queries, const float *d_weights, int64_t n_items, int64_t ld_w,
                         float *d_out, int64_t ld_out, void *stream);
+/* lk_ease_score_panel: the same sums as a panel for lk_argtopn, any number of queries: out[q][c] =
+ *   the plain float32 sum, from zero and in history order, of weights[i][c] over the history
+ *   items i of query q (items outside [0, n_items) -- -1 = unknown -- add nothing): the bits of
+ *   lk_ease_score_batch.  The rows of d_weights need 4-byte alignment only (ld_w = n_items is odd
+ *   in general).  mark_history as lk_slim_score_batch: bit 0 turns the query's own items into
+ *   NaN, bit 1 the whole row of a query without a known item (0 otherwise). */
+int lk_ease_score_panel(const int64_t *d_hist_ptr, const int32_t *d_hist_items,
+                        int64_t n_queries, const float *d_weights, int64_t n_items, int64_t ld_w,
+                        float *d_out, int64_t ld_out, int mark_history, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Dense float32 GEMM and the blocked SPD inverse of EASE's training (csrc/spd_blocked.hip;
+ * `_chol_invert_torch`, src/lenskit/knn/ease.py:190-208).
+ * lk_gemm_f32: C <- beta C + alpha op(A) op(B) on row-major float32 matrices: C [m x n], op(A)
+ *   [m x k], op(B) [k x n]; trans_a / trans_b != 0: the operand is stored transposed (A as
+ *   [k x m], B as [n x k]).  Leading dimensions are in elements, at least the stored row length;
+ *   pointers and rows need 4-byte alignment only; any m, n, k >= 0 (k = 0: C <- beta C).  A cell
+ *   is the k-ordered fmaf chain of v_mfma_f32_32x32x2_f32 from zero, then fmaf(alpha, sum, beta c)
+ *   -- alpha * sum when beta == 0, C is then not read.  No atomics, no split-k: a result's bits
+ *   depend on its operands alone.  C must not overlap A or B.  tile_mask, in tiles of
+ *   lk_gemm_tile() = 128 rows / columns counted from C's origin:
+ *     LK_GEMM_LOWER       only the tiles on or below C's diagonal are computed, the others are
+ *                         left untouched;
+ *     LK_GEMM_K_FROM_COL  a tile's k starts at its first column (op(B) is lower triangular: zero
+ *                         for k < the tile's columns);
+ *     LK_GEMM_K_FROM_ROW  a tile's k starts at its first row (op(A) is upper triangular).
+ * lk_spd_inverse_blocked: d_a [n x n, leading dimension ld] <- its inverse, in place, for a
+ *   symmetric positive definite matrix (the lower triangle is read); the full result is written
+ *   and is exactly symmetric.  Blocked Cholesky with block size 128: (a) right-looking
+ *   factorisation, the diagonal blocks through lk_chol_upper_inverse (step = block + 1), panels
+ *   and trailing updates through lk_gemm_f32; (b) the blocked inverse of the factor; (c) X^T X on
+ *   the lower tiles, mirrored.  Every step is queued on `stream`; nothing waits for the host.
+ *   d_work: lk_spd_inverse_blocked_workspace_bytes(n) bytes (a second n x n matrix, the diagonal
+ *   blocks' inverses and a 128-row panel; 0 for an n that is not served).  n <=
+ *   lk_spd_inverse_blocked_max_n() = 2^20, ld < 2^31.
+ *   *d_flag (device) <- 0, or 1 + the number of the first block whose factorisation met a pivot
+ *   that is not positive to working precision; every value stays finite on that path and the
+ *   result is then all zeros.  The caller reads the flag once, after the call.
+ * lk_spd_inverse_blocked_phases: the same with `phases` naming the steps to queue (bit 0 = (a),
+ *   which also clears the flag, bit 1 = (b), bit 2 = (c); 7 = lk_spd_inverse_blocked): a timing
+ *   hook -- three calls in that order on the same matrix and workspace are one inversion.
+ * ---------------------------------------------------------------------- */
+#define LK_GEMM_LOWER 1
+#define LK_GEMM_K_FROM_COL 2
+#define LK_GEMM_K_FROM_ROW 4
+int32_t lk_gemm_tile(void);
+int lk_gemm_f32(int trans_a, int trans_b, int64_t m, int64_t n, int64_t k, float alpha,
+                const float *d_a, int64_t lda, const float *d_b, int64_t ldb, float beta,
+                float *d_c, int64_t ldc, int tile_mask, void *stream);
+int64_t lk_spd_inverse_blocked_max_n(void);
+size_t lk_spd_inverse_blocked_workspace_bytes(int64_t n);
+int lk_spd_inverse_blocked(float *d_a, int64_t n, int64_t ld, void *d_work, size_t work_bytes,
+                           int32_t *d_flag, void *stream);
+int lk_spd_inverse_blocked_phases(float *d_a, int64_t n, int64_t ld, void *d_work,
+                                  size_t work_bytes, int32_t *d_flag, int phases, void *stream);
 
 /* ------------------------------------------------------------------------
  * SLIM / fsSLIM (`SLIMScorer`, src/lenskit/knn/slim.py:53-152; csrc/slim.hip).

@@ -1180,6 +1180,97 @@ def ease_score_batch(hist_ptr: torch.Tensor, hist_items: torch.Tensor,
     return out
 
 
+def ease_score_panel(hist_ptr: torch.Tensor, hist_items: torch.Tensor, weights: torch.Tensor,
+                     rows: tuple[int, int] | None = None, strike_history: bool = False,
+                     nan_empty: bool = False) -> torch.Tensor:
+    """
+    ``ease_score_batch`` as a panel for ``argtopn`` (lk_ease_score_panel): the sum of the history
+    items' rows of the dense ``weights`` in history order, -1 (unknown) adding nothing, [B x
+    n_items] f32 with the bits ``ease_score_batch`` gives; any number of queries.  ``rows = (lo,
+    hi)``: those queries only.  ``strike_history`` makes the query's own items NaN, ``nan_empty``
+    the whole row of a query without a known item.
+    """
+    lib = _native.require_gpu()
+    n = int(weights.shape[0])
+    lo, hi = (0, int(hist_ptr.shape[0]) - 1) if rows is None else (int(rows[0]), int(rows[1]))
+    assert 0 <= lo <= hi < int(hist_ptr.shape[0])
+    assert hist_ptr.dtype == torch.int64 and hist_items.dtype == torch.int32
+    assert weights.dtype == torch.float32 and weights.is_contiguous()
+    out = torch.empty((hi - lo, n), dtype=torch.float32, device=weights.device)
+    check(
+        lib.lk_ease_score_panel(_ptr(hist_ptr[lo:]), _ptr(hist_items), hi - lo, _ptr(weights), n,
+                                n, _ptr(out), n, (1 if strike_history else 0) |
+                                (2 if nan_empty else 0), _stream()),
+        "lk_ease_score_panel",
+    )
+    return out
+
+
+def gemm_tile() -> int:
+    "The tile ``gemm_f32``'s masks count in (lk_gemm_tile)."
+    return int(_native.load().lk_gemm_tile())
+
+
+def gemm_f32(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, *, trans_a: bool = False,
+             trans_b: bool = False, alpha: float = 1.0, beta: float = 0.0,
+             mask: int = 0) -> torch.Tensor:
+    """
+    ``c <- beta c + alpha op(a) op(b)`` in place (lk_gemm_f32): 2-D float32 device tensors whose
+    rows are contiguous (any row stride: views of larger matrices are fine), ``op`` the transpose
+    where ``trans_*``.  ``mask``: ``_native.GEMM_LOWER`` / ``GEMM_K_FROM_COL`` / ``GEMM_K_FROM_ROW``
+    in tiles of :func:`gemm_tile`.  Returns ``c``.
+    """
+    lib = _native.require_gpu()
+    for t in (a, b, c):
+        assert t.dtype == torch.float32 and t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1)
+    m, n = int(c.shape[0]), int(c.shape[1])
+    k = int(a.shape[0] if trans_a else a.shape[1])
+    assert tuple(a.shape) == ((k, m) if trans_a else (m, k))
+    assert tuple(b.shape) == ((n, k) if trans_b else (k, n))
+
+    def ld(t):  # (the stride of a one-row view is arbitrary: give the row length)
+        return max(int(t.stride(0)), int(t.shape[1])) if t.shape[0] > 1 else int(t.shape[1])
+
+    check(
+        lib.lk_gemm_f32(int(trans_a), int(trans_b), m, n, k, float(alpha), _ptr(a), ld(a),
+                        _ptr(b), ld(b), float(beta), _ptr(c), ld(c), int(mask), _stream()),
+        "lk_gemm_f32",
+    )
+    return c
+
+
+def spd_inverse_blocked_max_n() -> int:
+    "The largest matrix ``spd_inverse_blocked`` accepts (lk_spd_inverse_blocked_max_n)."
+    return int(_native.load().lk_spd_inverse_blocked_max_n())
+
+
+def spd_inverse_blocked(a: torch.Tensor, flag: torch.Tensor | None = None):
+    """
+    The inverse of the SPD matrix ``a`` IN PLACE (lk_spd_inverse_blocked: blocked Cholesky, f32
+    MFMA GEMMs, float64 diagonal blocks): a square float32 device matrix, or a square view with
+    contiguous rows of a wider one.  Everything is queued on the current stream; the workspace
+    (a second matrix and panels) is released on return, stream-ordered.  Returns (``a``, the int32
+    device flag: 0, or 1 + the first block that is not positive definite -- ``a`` is then zeros).
+    The caller reads the flag.
+    """
+    lib = _native.require_gpu()
+    assert a.dtype == torch.float32 and a.dim() == 2 and a.shape[0] == a.shape[1]
+    n = int(a.shape[0])
+    assert n <= 1 or a.stride(1) == 1
+    if n > spd_inverse_blocked_max_n():
+        raise ValueError(f"spd_inverse_blocked: n = {n} above {spd_inverse_blocked_max_n()}")
+    if flag is None:
+        flag = torch.zeros(1, dtype=torch.int32, device=a.device)
+    nbytes = int(lib.lk_spd_inverse_blocked_workspace_bytes(n))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=a.device)
+    check(
+        lib.lk_spd_inverse_blocked(_ptr(a), n, max(int(a.stride(0)), n) if n > 1 else n, _ptr(ws),
+                                   nbytes, _ptr(flag), _stream()),
+        "lk_spd_inverse_blocked",
+    )
+    return a, flag
+
+
 SLIM_STAGE_BYTES = 2 << 30  # staging area of one lk_slim_train_count call (column batches)
 
 

@@ -44,6 +44,10 @@ FAIR_MAX_N = 1024  # LK_FAIR_MAX_N (lk_fair_max_n()): the list length lk_fair_re
 
 ASSOC_METHODS = {"probability": 0, "lift": 1}  # LK_ASSOC_PROBABILITY / LK_ASSOC_LIFT
 ASSOC_REDUCTIONS = {"mean": 0, "max": 1}  # LK_ASSOC_MEAN / LK_ASSOC_MAX
+# lk_gemm_f32's tile mask: LK_GEMM_LOWER / LK_GEMM_K_FROM_COL / LK_GEMM_K_FROM_ROW
+GEMM_LOWER = 1
+GEMM_K_FROM_COL = 2
+GEMM_K_FROM_ROW = 4
 
 
 class FlexMFTables(ctypes.Structure):
@@ -195,6 +199,20 @@ def _declare(lib):
         "lk_ease_gram": (c_int, [vp, vp, vp, vp, c_int64, c_float, vp, c_int64, vp]),
         "lk_ease_score_batch": (
             c_int, [vp, vp, c_int64, vp, c_int64, c_int64, vp, c_int64, vp]
+        ),
+        "lk_ease_score_panel": (
+            c_int, [vp, vp, c_int64, vp, c_int64, c_int64, vp, c_int64, c_int, vp]
+        ),
+        "lk_gemm_tile": (c_int32, []),
+        "lk_gemm_f32": (
+            c_int, [c_int, c_int, c_int64, c_int64, c_int64, c_float, vp, c_int64, vp, c_int64,
+                    c_float, vp, c_int64, c_int, vp]
+        ),
+        "lk_spd_inverse_blocked_max_n": (c_int64, []),
+        "lk_spd_inverse_blocked_workspace_bytes": (c_size_t, [c_int64]),
+        "lk_spd_inverse_blocked": (c_int, [vp, c_int64, c_int64, vp, c_size_t, vp, vp]),
+        "lk_spd_inverse_blocked_phases": (
+            c_int, [vp, c_int64, c_int64, vp, c_size_t, vp, c_int, vp]
         ),
         "lk_slim_train_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
         "lk_slim_train_count": (

@@ -808,6 +808,80 @@ __global__ __launch_bounds__(256) void ease_score_kernel(
     }
     out[q * ld_out + c] = acc;
 }
+
+// four floats at a 4-byte aligned address (a row of W starts anywhere: ld = n_items is odd in
+// general); gfx950 serves the one wide instruction this compiles to at any dword address
+typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+
+constexpr int EASE_PANEL_COLS = 1024;  // columns per workgroup: four per thread
+
+// The panel form of ease_score_kernel: workgroup = (query, 1024-column strip) from a 1-D grid (no
+// limit on the queries), a thread owns four neighbouring columns and reads them with one load per
+// history item.  A cell is the same chain -- from zero, plain adds, history order -- so it has
+// the bits ease_score_kernel gives it.  Four history items at a time: their rows are requested
+// before the first is added.
+__global__ __launch_bounds__(256) void ease_score_panel_kernel(
+    const int64_t *__restrict__ hist_ptr, const int32_t *__restrict__ hist_items,
+    const float *__restrict__ w, int64_t n_items, int64_t ld_w, float *__restrict__ out,
+    int64_t ld_out, int mark, int64_t n_strips)
+{
+    const int64_t q = (int64_t)blockIdx.x / n_strips;
+    const int64_t c = ((int64_t)blockIdx.x % n_strips) * EASE_PANEL_COLS + 4 * threadIdx.x;
+    if (c >= n_items) return;
+    const bool whole = c + 4 <= n_items;
+    const int64_t b = hist_ptr[q], e = hist_ptr[q + 1];
+    auto load = [&](int32_t it) {
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (it < 0 || it >= n_items) return v;
+        const float *p = w + (int64_t)it * ld_w + c;
+        if (whole) {
+            const f32x4_a4 u = *reinterpret_cast<const f32x4_a4 *>(p);
+            v = f32x4{u[0], u[1], u[2], u[3]};
+        } else {
+            for (int t = 0; t < 4; ++t)
+                if (c + t < n_items) v[t] = p[t];
+        }
+        return v;
+    };
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    bool known = false;
+    unsigned own = 0u;  // bit t: column c + t is an item of the history
+    auto add = [&](int32_t it, const f32x4 &v) {
+        if (it < 0 || it >= n_items) return;  // unknown item: contributes nothing
+        known = true;
+        acc += v;
+        if (it >= c && it < c + 4) own |= 1u << (int)(it - c);
+    };
+    int64_t i = b;
+    for (; i + 4 <= e; i += 4) {
+        int32_t it[4];
+        f32x4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) it[u] = hist_items[i + u];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = load(it[u]);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) add(it[u], v[u]);
+    }
+    for (; i < e; ++i) {
+        const int32_t it = hist_items[i];
+        add(it, load(it));
+    }
+    const float nan = __builtin_nanf("");
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+        if (((mark & 2) && !known) || ((mark & 1) && (own >> t & 1u))) acc[t] = nan;
+    float *o = out + q * ld_out + c;
+    if (whole) {
+        f32x4_a4 u;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) u[t] = acc[t];
+        *reinterpret_cast<f32x4_a4 *>(o) = u;
+    } else {
+        for (int t = 0; t < 4; ++t)
+            if (c + t < n_items) o[t] = acc[t];
+    }
+}
 }  // namespace lk
 
 extern "C" int lk_ease_gram(const int64_t *d_cooc_indptr, const int32_t *d_cooc_indices,
@@ -840,6 +914,24 @@ extern "C" int lk_ease_score_batch(const int64_t *d_hist_ptr, const int32_t *d_h
                        dim3((unsigned)((n_items + 255) / 256), (unsigned)n_queries), dim3(256), 0,
                        lk::as_stream(stream), d_hist_ptr, d_hist_items, d_weights, n_items, ld_w,
                        d_out, ld_out);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
+extern "C" int lk_ease_score_panel(const int64_t *d_hist_ptr, const int32_t *d_hist_items,
+                                   int64_t n_queries, const float *d_weights, int64_t n_items,
+                                   int64_t ld_w, float *d_out, int64_t ld_out, int mark_history,
+                                   void *stream)
+{
+    LK_REQUIRE(n_queries >= 0 && n_items >= 0 && ld_w >= n_items && ld_out >= n_items,
+               "lk_ease_score_panel: bad shape");
+    if (n_queries == 0 || n_items == 0) return LK_OK;
+    LK_REQUIRE(d_hist_ptr && d_weights && d_out, "lk_ease_score_panel: null pointer");
+    const int64_t strips = (n_items + lk::EASE_PANEL_COLS - 1) / lk::EASE_PANEL_COLS;
+    LK_REQUIRE(n_queries < ((int64_t)1 << 31) / strips, "lk_ease_score_panel: too many queries");
+    hipLaunchKernelGGL(lk::ease_score_panel_kernel, dim3((unsigned)(n_queries * strips)),
+                       dim3(256), 0, lk::as_stream(stream), d_hist_ptr, d_hist_items, d_weights,
+                       n_items, ld_w, d_out, ld_out, mark_history, strips);
     LK_HIP_CHECK(hipGetLastError());
     return LK_OK;
 }

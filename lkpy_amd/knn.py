@@ -15,7 +15,9 @@ User-based k-NN scores candidate lists through ``lk_csr_rows_dot`` + ``lk_uknn_s
 (``recommend_batch`` / ``dense_scores_batch``, the loops of :class:`_PanelScorer`): the query
 vectors built on the device, the neighbour similarities user-major, and each (query, item) cell a
 gather from the transposed ratings into the reference's accumulator.
-``batch.recommend`` takes that path, as it takes item-kNN's, SLIM's and the association rules'.
+``batch.recommend`` takes that path, as it takes item-kNN's, SLIM's, the association rules' and
+EASE's (``lk_ease_score_panel``; EASE's training can invert its Gramian with this package's blocked
+Cholesky, ``lk_spd_inverse_blocked``: DESIGN.md section 4.25).
 """
 
 from __future__ import annotations
@@ -273,11 +275,12 @@ class ItemKNNScorer(Component):
 
 class _PanelScorer:
     """
-    What ``SLIMScorer``, ``AssociationScorer`` and ``UserKNNScorer`` share, beside
-    :class:`Component`: the model is a sparse matrix in HBM (item-item; user-kNN: the transposed
-    ratings), a kernel call scores every item for a range of queries (a [rows x items] float32
-    panel), and a batch goes through in panels of at most ``PANEL_BYTES``.
-    A subclass supplies ``items``, :meth:`_device_matrix` and :meth:`_score_panel`.
+    What ``SLIMScorer``, ``AssociationScorer``, ``UserKNNScorer`` and ``EASEScorer`` share, beside
+    :class:`Component`: the model is a matrix in HBM (a sparse item-item one; user-kNN: the
+    transposed ratings; EASE: the dense weights), a kernel call scores every item for a range of
+    queries (a [rows x items] float32 panel), and a batch goes through in panels of at most
+    ``PANEL_BYTES``.  A subclass supplies ``items``, :meth:`_device_matrix` and
+    :meth:`_score_panel` (and :meth:`_panel_device` if its matrix is no ``DeviceCSR``).
     """
 
     PANEL_BYTES = 1 << 30  # score panel of one recommend / score step
@@ -291,6 +294,10 @@ class _PanelScorer:
         "One kernel call: the device panel of the queries ``rows = (lo, hi)`` of ``hist``."
         raise NotImplementedError
 
+    def _panel_device(self):
+        "The device the model lives on (a subclass whose matrix is no CSR overrides this)."
+        return self._device_matrix().indices.device
+
     def _panel_rows(self) -> int:
         return max(1, self.PANEL_BYTES // (4 * max(len(self.items), 1)))
 
@@ -298,7 +305,7 @@ class _PanelScorer:
         "The histories of a list of queries in query order, uploaded: item numbers, -1 = unknown."
         ptr, idx, _ = pack_histories(queries, self.items, unknown="keep")
         return D.DeviceCSR.from_arrays(ptr, idx, None, (len(queries), len(self.items)),
-                                       self._device_matrix().indices.device)
+                                       self._panel_device())
 
     def _batch_csr(self, queries) -> D.DeviceCSR:
         "The histories of a batch as a device CSR: a HistoryBatch's training rows, or a list's."
@@ -347,7 +354,7 @@ class _PanelScorer:
         padding, scores [B x n] with NaN padding), like ``ItemKNNScorer.recommend_batch``.
         """
         hist = self._batch_csr(queries)
-        d = self._device_matrix().indices.device
+        d = self._panel_device()
         B = hist.shape[0]
         n = -1 if n is None else int(n)
         cols = len(self.items) if n < 0 else n
@@ -705,16 +712,23 @@ class EASEConfig(BaseModel, extra="forbid"):
     "Regularization term for EASE."
 
 
-class EASEScorer(Component):
+class EASEScorer(_PanelScorer, Component):
     """
     Embarrassingly shallow autoencoder (``EASEScorer``, src/lenskit/knn/ease.py:47-170;
     SURVEY.md section 8f rank 4).  Training: the dense item-item co-occurrence Gramian
     ``X^T X + reg I`` is built on the device (the similarity-build kernel on unit values +
-    ``lk_ease_gram``), inverted there with the very PyTorch calls of the reference's
-    ``_chol_invert_torch`` (``torch.linalg.cholesky_ex`` + ``torch.cholesky_inverse``,
-    ease.py:190-208 -- a library factorisation, as in the reference), and turned into the
-    weight matrix ``B = inv / -diag(inv)`` with a zero diagonal.  Scoring = sum of the history
-    items' weight rows (``lk_ease_score_batch``), whole batches of queries at a time.
+    ``lk_ease_gram``), inverted there, and turned into the weight matrix ``B = inv / -diag(inv)``
+    with a zero diagonal.  The inverse is, by ``LK_EASE_SOLVER``: unset or ``torch``, the very
+    PyTorch calls of the reference's ``_chol_invert_torch`` (``torch.linalg.cholesky_ex`` +
+    ``torch.cholesky_inverse``, ease.py:190-208 -- a library factorisation, as in the reference);
+    ``native``, this package's blocked Cholesky inverse (``lk_spd_inverse_blocked``,
+    csrc/spd_blocked.hip: f32 MFMA GEMMs, float64 diagonal blocks).
+    Scoring = sum of the history items' weight rows, whole batches of queries at a time:
+    ``score_batch`` through ``lk_ease_score_batch``; ``recommend_batch`` / ``dense_scores_batch``
+    from bounded device panels (:class:`_PanelScorer`, ``lk_ease_score_panel``: the same bits).
+    A repeated history item counts once (``q_vec[q_good] = 1.0``): a list of queries is packed
+    that way; the rows of a :class:`lkpy_amd.basic.HistoryBatch` are training rows, whose items
+    are distinct.
     """
 
     config: EASEConfig
@@ -727,7 +741,7 @@ class EASEScorer(Component):
 
     def train(self, data: Dataset, options: TrainingOptions = TrainingOptions()):
         solver = options.env_var("LK_EASE_SOLVER", None)
-        if solver and solver not in ("torch", "scipy"):
+        if solver and solver not in ("torch", "scipy", "native"):
             raise ValueError(f"unsupported option: LK_EASE_SOLVER={solver}")  # ease.py:96-97
         if solver == "scipy":
             raise ValueError("LK_EASE_SOLVER=scipy: the device backend has no host solver")
@@ -737,12 +751,17 @@ class EASEScorer(Component):
         gram = D.ease_gram(cooc, counts, float(self.config.regularization))
         del cooc
         with torch.inference_mode():
-            decomp, info = torch.linalg.cholesky_ex(gram)
-            if info.item():
-                # ease.py:202-203
-                raise RuntimeError(f"matrix minor {info.item()} is not positive-definite.")
-            inv = torch.cholesky_inverse(decomp, out=gram)
-            del decomp
+            if solver == "native":
+                inv, flag = D.spd_inverse_blocked(gram)
+                if flag.item():  # the one read of the flag: everything above was only queued
+                    raise RuntimeError(f"matrix block {flag.item()} is not positive-definite.")
+            else:
+                decomp, info = torch.linalg.cholesky_ex(gram)
+                if info.item():
+                    # ease.py:202-203
+                    raise RuntimeError(f"matrix minor {info.item()} is not positive-definite.")
+                inv = torch.cholesky_inverse(decomp, out=gram)
+                del decomp
             # divide cells by the column's diagonal entry, zero the diagonal (ease.py:140-142)
             inv /= -torch.diagonal(inv).reshape(1, -1).clone()
             inv.fill_diagonal_(0.0)
@@ -750,6 +769,8 @@ class EASEScorer(Component):
         self.items = data.items
         self.weights = mat
         assert self.weights.shape == (n_items, n_items)
+        # the matrix in HBM IS the device copy of the new weights: not uploaded again
+        self._device_cache("weights", lambda: inv, self.weights)
 
     def _device_weights(self):
         return self._device_cache(
@@ -770,6 +791,40 @@ class EASEScorer(Component):
 
     def __call__(self, query, items: ItemList) -> ItemList:
         return self.score_batch([query], [items])[0]
+
+    # -- every item for panels of queries (lk_ease_score_panel) -------------------------------
+    def _device_matrix(self) -> torch.Tensor:
+        "The dense weight matrix in HBM (f32 [items x items]), uploaded once per model."
+        return self._device_weights()
+
+    def _panel_device(self):
+        return self._device_weights().device
+
+    def _query_csr(self, queries: list[RecQuery]) -> D.DeviceCSR:
+        "The histories of a list of queries as ``score_batch`` packs them: known, ascending, once."
+        ptr, idx, _ = pack_histories(queries, self.items, unknown="drop", unique=True)
+        return D.DeviceCSR.from_arrays(ptr, idx, None, (len(queries), len(self.items)),
+                                       self._panel_device())
+
+    def _score_panel(self, hist, rows, *, strike_history, nan_empty):
+        return D.ease_score_panel(hist.indptr, hist.indices, self._device_weights(), rows=rows,
+                                  strike_history=strike_history, nan_empty=nan_empty)
+
+    def dense_scores_batch(self, queries):
+        """
+        Every item's score for many queries at once, left on the device: (panel f32 [B x items],
+        valid, history CSR), the contract of ``AssociationScorer.dense_scores_batch``.  The row of a
+        query without a known history item is NaN (``valid`` False; ease.py:150-158); the history
+        CSR (known items, ascending) is for the caller to exclude.  The caller bounds the batch.
+        """
+        queries = resolve_queries(queries, self.items)
+        if isinstance(queries, HistoryBatch):
+            hist = queries.csr(with_values=False)  # training rows: known items, ascending
+            valid = queries.lengths > 0
+        else:
+            hist = self._query_csr(queries)  # (known items, ascending: the exclusion CSR as well)
+            valid = np.diff(hist.h_indptr) > 0
+        return self._score_panel(hist, None, strike_history=False, nan_empty=True), valid, hist
 
 
 # ---------------------------------------------------------------------------------------
