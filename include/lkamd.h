@@ -555,6 +555,52 @@ int lk_predict_merge(int64_t n_queries, const int64_t *d_tgt_ptr, const int32_t 
                      const uint8_t *d_user_add, uint8_t *d_out_is_fallback, void *stream);
 
 /* ------------------------------------------------------------------------
+ * `BiasedMFScorer.__call__` for a BATCH of queries (csrc/bmf_batch.hip): the host arithmetic of
+ * the explicit-feedback ALS scorer around its row solve and its lk_score_dense row
+ * (src/lenskit/als/_common.py:133-175, _explicit.py:55-91, basic/bias.py:166-241), so that a
+ * batched list holds float32(the per-query score) bit for bit.  A query's MODE says which branch
+ * the per-query path takes, and with it the precision it adds in:
+ *   LK_BMF_FOLD    a fold-in row: ub is the float64 user bias derived from the history, and
+ *                  score = (float)((double)dot + ((double)((float)mu + b_i) + ub));
+ *   LK_BMF_STORED  the stored embedding: ub holds the model's float32 user bias (exactly), and
+ *                  score = dot + (((float)mu + b_i) + (float)ub) in float32;
+ *   LK_BMF_INVALID neither: the score is NaN.
+ * `dot` is the lk_score_dense entry; d_item_biases [n_items] f32 is required.
+ *
+ * lk_bmf_residual_rows: query q's history is row d_user_nums[q] of the training matrix (as
+ *   lk_bias_user_offsets takes it; -1 or out of range: no row, ub = 0, nothing written).
+ *   d_out_ub[q] = the ub of lk_bias_user_offsets BEFORE its rounding to float32 (same sum, same
+ *   order); the row's entries go to d_out_indices / d_out_values from d_out_ptr[q] on (int64
+ *   [n_queries + 1], the caller's prefix sums of the row lengths; entries past d_out_ptr[q + 1]
+ *   are not written), item numbers copied, values r_j - (((float)mu + b_i[j]) + (float)ub) in
+ *   float32: the CSR `new_user_embedding` hands to the explicit row solve.  One wave per query.
+ * lk_bmf_finish_panel: the finish in place on d_panel [n_rows x n_items], rows `ld` floats apart,
+ *   16-byte aligned; d_mode uint8 [n_rows], d_ub float64 [n_rows].  With d_strike_ptr (int64
+ *   [n_rows + 1] offsets into d_strike_items, int32) each row's listed items are then set to NaN.
+ * lk_bmf_finish_pairs: entries first_entry .. first_entry + n_entries - 1 of the ragged lists
+ *   d_tgt_ptr [n_rows + 1] / d_tgt_items (d_tgt_ptr[0] = first_entry; negative or >= n_items: an
+ *   unknown item, NaN): d_out[e] = the finish of d_panel[row of e][d_tgt_items[e]].
+ * ---------------------------------------------------------------------- */
+#define LK_BMF_INVALID 0
+#define LK_BMF_FOLD 1
+#define LK_BMF_STORED 2
+int lk_bmf_residual_rows(const void *d_indptr, int indptr_is_64, const int32_t *d_indices,
+                         const float *d_values, int64_t n_users, int64_t n_items,
+                         int64_t n_queries, const int32_t *d_user_nums, const int64_t *d_out_ptr,
+                         double global_bias, const float *d_item_biases, double damping_user,
+                         double *d_out_ub, int32_t *d_out_indices, float *d_out_values,
+                         void *stream);
+int lk_bmf_finish_panel(float *d_panel, int64_t n_rows, int64_t n_items, int64_t ld,
+                        const uint8_t *d_mode, const double *d_ub, double global_bias,
+                        const float *d_item_biases, const int64_t *d_strike_ptr,
+                        const int32_t *d_strike_items, void *stream);
+int lk_bmf_finish_pairs(const float *d_panel, int64_t n_rows, int64_t n_items, int64_t ld,
+                        const uint8_t *d_mode, const double *d_ub, double global_bias,
+                        const float *d_item_biases, const int64_t *d_tgt_ptr,
+                        const int32_t *d_tgt_items, int64_t first_entry, int64_t n_entries,
+                        float *d_out, void *stream);
+
+/* ------------------------------------------------------------------------
  * User-kNN scoring for a BATCH of queries.
  * Replaces `_accel.knn.user_score_items_explicit / _implicit(tgt_items, nbr_rows, nbr_sims,
  * ratings, max_nbrs, min_nbrs)` (src/accel/knn/user_score.rs:21-98): query q has neighbours

@@ -915,6 +915,103 @@ def predict_merge(tgt_ptr: torch.Tensor, tgt_items: torch.Tensor, n_items: int,
     return scores
 
 
+def bmf_residual_rows(mat: DeviceCSR, rows: np.ndarray, global_bias: float,
+                      item_biases: torch.Tensor, damping_user: float):
+    """
+    The fold-in input of ``BiasedMFScorer`` for a batch of training histories
+    (lk_bmf_residual_rows): the rows ``rows`` (HOST int32, -1 = an empty row) of the training
+    matrix ``mat`` (users x items, f32 ratings, item-sorted rows) with the bias model taken out --
+    what ``new_user_embedding`` builds per query from ``BiasModel.compute_for_items``, bit for
+    bit.  Returns (the residual CSR [B x items], int64 offsets from the host prefix sums as
+    :func:`gather_rows` makes them, and the float64 user biases, device [B], 0 without a row).
+    """
+    lib = _native.require_gpu()
+    hp = mat.h_indptr
+    assert hp is not None and mat.values is not None and item_biases is not None
+    assert item_biases.dtype == torch.float32 and int(item_biases.shape[0]) == mat.shape[1]
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    B = int(rows.shape[0])
+    ok = (rows >= 0) & (rows < mat.shape[0])
+    safe = np.where(ok, rows, 0)
+    lens = np.where(ok, hp[safe + 1] - hp[safe], 0).astype(np.int64)
+    ptr = np.zeros(B + 1, dtype=np.int64)
+    np.cumsum(lens, out=ptr[1:])
+    dev = mat.indices.device
+    nnz = int(ptr[-1])
+    packed = np.empty(2 * (B + 1) + B + (B & 1), dtype=np.int32)  # (one upload, as gather_rows)
+    packed[:2 * (B + 1)] = ptr.view(np.int32)
+    packed[2 * (B + 1):2 * (B + 1) + B] = rows
+    d_packed = torch.from_numpy(packed).to(dev)
+    d_ptr = d_packed[:2 * (B + 1)].view(torch.int64)
+    d_rows = d_packed[2 * (B + 1):2 * (B + 1) + B]
+    out_idx = torch.empty(nnz, dtype=torch.int32, device=dev)
+    out_val = torch.empty(nnz, dtype=torch.float32, device=dev)
+    ub = torch.zeros(B, dtype=torch.float64, device=dev)
+    if B and nnz:  # (rows without an entry: nothing to write, and their bias is 0)
+        check(
+            lib.lk_bmf_residual_rows(
+                _ptr(mat.indptr), 1 if mat.is64 else 0, _ptr(mat.indices), _ptr(mat.values),
+                mat.shape[0], mat.shape[1], B, _ptr(d_rows), _ptr(d_ptr), float(global_bias),
+                _ptr(item_biases), float(damping_user), _ptr(ub), _ptr(out_idx), _ptr(out_val),
+                _stream()
+            ),
+            "lk_bmf_residual_rows",
+        )  # fmt: skip
+    return DeviceCSR(d_ptr, out_idx, out_val, (B, mat.shape[1]), ptr), ub
+
+
+def _bmf_rows(panel: torch.Tensor, mode: torch.Tensor, ub: torch.Tensor, item_biases):
+    rows, n_items = panel.shape
+    assert panel.dtype == torch.float32 and panel.dim() == 2 and panel.is_contiguous()
+    assert mode.dtype == torch.uint8 and mode.shape == (rows,) and mode.is_contiguous()
+    assert ub.dtype == torch.float64 and ub.shape == (rows,) and ub.is_contiguous()
+    assert item_biases.dtype == torch.float32 and item_biases.shape == (n_items,)
+    return rows, n_items
+
+
+def bmf_finish_panel(panel: torch.Tensor, mode: torch.Tensor, ub: torch.Tensor,
+                     global_bias: float, item_biases: torch.Tensor,
+                     strike_ptr: torch.Tensor | None = None,
+                     strike_items: torch.Tensor | None = None) -> torch.Tensor:
+    """
+    ``BiasedMFScorer.finalize_scores`` in place on a [rows x items] f32 panel of
+    :func:`score_dense` (lk_bmf_finish_panel): per row a mode (uint8, ``_native.BMF_*``) and a
+    float64 user bias, the item biases f32 [items].  ``strike_ptr`` (int64 [rows + 1], offsets
+    into ``strike_items``, int32): the row's listed items become NaN.  Returns ``panel``.
+    """
+    lib = _native.require_gpu()
+    rows, n_items = _bmf_rows(panel, mode, ub, item_biases)
+    if strike_ptr is not None:
+        assert strike_ptr.dtype == torch.int64 and strike_ptr.shape == (rows + 1,)
+        assert strike_items.dtype == torch.int32
+    check(lib.lk_bmf_finish_panel(_ptr(panel), rows, n_items, n_items, _ptr(mode), _ptr(ub),
+                                  float(global_bias), _ptr(item_biases), _ptr(strike_ptr),
+                                  _ptr(strike_items), _stream()), "lk_bmf_finish_panel")
+    return panel
+
+
+def bmf_finish_pairs(panel: torch.Tensor, mode: torch.Tensor, ub: torch.Tensor,
+                     global_bias: float, item_biases: torch.Tensor, tgt_ptr: torch.Tensor,
+                     tgt_items: torch.Tensor, first: int, count: int,
+                     out: torch.Tensor) -> torch.Tensor:
+    """
+    The same finish for ragged target lists (lk_bmf_finish_pairs): ``panel`` is the UNFINISHED
+    :func:`score_dense` panel of the rows whose lists are ``tgt_ptr`` (int64 [rows + 1], absolute
+    offsets into ``tgt_items`` int32 and ``out`` f32, ``tgt_ptr[0] == first``); the ``count``
+    entries from ``first`` on are written to ``out`` (an unknown item, -1: NaN).
+    """
+    lib = _native.require_gpu()
+    rows, n_items = _bmf_rows(panel, mode, ub, item_biases)
+    assert tgt_ptr.dtype == torch.int64 and tgt_ptr.shape == (rows + 1,)
+    assert tgt_items.dtype == torch.int32 and out.dtype == torch.float32
+    assert 0 <= first and first + count <= min(int(tgt_items.shape[0]), int(out.shape[0]))
+    check(lib.lk_bmf_finish_pairs(_ptr(panel), rows, n_items, n_items, _ptr(mode), _ptr(ub),
+                                  float(global_bias), _ptr(item_biases), _ptr(tgt_ptr),
+                                  _ptr(tgt_items), int(first), int(count), _ptr(out), _stream()),
+          "lk_bmf_finish_pairs")
+    return out
+
+
 def iknn_recommend(sims: DeviceCSR, ref_ptr, ref_items, ref_rates, item_bias, max_nbrs: int,
                    min_nbrs: int, n: int, query_hits: np.ndarray, exclude_refs: bool = True):
     """
@@ -1589,16 +1686,22 @@ def fold_in(hist: DeviceCSR, items: torch.Tensor, otor: torch.Tensor, k: int,
     return out
 
 
-def fold_in_explicit(hist: DeviceCSR, items: torch.Tensor, reg: float, k: int) -> torch.Tensor:
+def fold_in_explicit(hist: DeviceCSR, items: torch.Tensor, reg: float, k: int,
+                     pending: list | None = None) -> torch.Tensor:
     """
     Batched new-user embeddings of the biased-MF model (``_train_bias_row_cholesky``,
     src/lenskit/als/_explicit.py:121-149): one explicit row solve per history row of ``hist``
-    (queries x items CSR, values = bias-normalised ratings).  Returns [n_queries x KP].
+    (queries x items CSR, values = bias-normalised ratings).  Returns [n_queries x KP]; empty
+    histories give zeros.  ``pending``: as :func:`fold_in` -- the launch is left unchecked and its
+    plan appended there, for the caller to check once its own launches are queued behind it.
     """
     plan = ALSPlan(hist, k, _native.SOLVER_CHOLESKY, reference_order="accurate")  # (as fold_in)
     out = torch.zeros((hist.shape[0], plan.kp), dtype=torch.float32, device=items.device)
     plan.half_epoch_explicit(out, items, reg)
-    plan.check_status()
+    if pending is None:
+        plan.check_status()
+    else:
+        pending.append(plan)
     return out
 
 

@@ -42,6 +42,8 @@ STOCHASTIC_TRANSFORMS = {None: 0, "softmax": 1, "linear": 2}
 
 FAIR_MAX_N = 1024  # LK_FAIR_MAX_N (lk_fair_max_n()): the list length lk_fair_rerank's LDS holds
 
+BMF_INVALID, BMF_FOLD, BMF_STORED = 0, 1, 2  # LK_BMF_*: a query's branch of BiasedMFScorer.__call__
+
 ASSOC_METHODS = {"probability": 0, "lift": 1}  # LK_ASSOC_PROBABILITY / LK_ASSOC_LIFT
 ASSOC_REDUCTIONS = {"mean": 0, "max": 1}  # LK_ASSOC_MEAN / LK_ASSOC_MAX
 # lk_gemm_f32's tile mask: LK_GEMM_LOWER / LK_GEMM_K_FROM_COL / LK_GEMM_K_FROM_ROW
@@ -173,6 +175,19 @@ def _declare(lib):
             c_int,
             [c_int64, vp, vp, c_int64, c_int64, vp, vp, c_int, ctypes.c_double, vp, vp, vp, vp,
              vp],
+        ),
+        "lk_bmf_residual_rows": (
+            c_int,
+            [vp, c_int, vp, vp, c_int64, c_int64, c_int64, vp, vp, ctypes.c_double, vp,
+             ctypes.c_double, vp, vp, vp, vp],
+        ),
+        "lk_bmf_finish_panel": (
+            c_int, [vp, c_int64, c_int64, c_int64, vp, vp, ctypes.c_double, vp, vp, vp, vp]
+        ),
+        "lk_bmf_finish_pairs": (
+            c_int,
+            [vp, c_int64, c_int64, c_int64, vp, vp, ctypes.c_double, vp, vp, vp, c_int64, c_int64,
+             vp, vp],
         ),
         "lk_uknn_score_batch": (
             c_int,

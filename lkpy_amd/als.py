@@ -22,8 +22,9 @@ from pydantic import AliasChoices, BaseModel, Field, PositiveFloat, PositiveInt
 from . import _device as D
 from . import _native
 from ._als_engine import HipBackend, ImplicitALSEngine
-from ._queries import item_scores, pack_histories, resolve_queries, user_numbers
-from .basic import BiasModel, HistoryBatch
+from ._queries import (item_scores, pack_histories, pack_targets, resolve_queries,
+                       user_numbers)
+from .basic import BiasModel, HistoryBatch, _damping
 from .data import Dataset, ItemList, RecQuery, Vocabulary
 from .pipeline import Component
 from .training import ModelTrainer, TrainingOptions, UsesTrainer
@@ -441,10 +442,15 @@ class BiasedMFScorer(UsesTrainer, Component):
     (``BiasedMFScorer``, src/lenskit/als/_explicit.py:32-90): the bias model stays on the
     host, the row solves (training and fold-in) run in the explicit mode of the HIP kernel.
     Scoring follows ``ALSBase.__call__`` (src/lenskit/als/_common.py:133-175) +
-    ``finalize_scores`` (adds b_g + b_i + b_u back).
+    ``finalize_scores`` (adds b_g + b_i + b_u back).  Whole batches -- ``recommend_batch``,
+    ``dense_scores_batch``, ``score_batch``, ``predict_history_batch`` -- do the same arithmetic on
+    the device (csrc/bmf_batch.hip) and hold float32(the per-query score) bit for bit.
     """
 
     config: BiasedMFConfig
+    accepts_history_batch = True  # recommend_batch takes a lkpy_amd.basic.HistoryBatch
+    returns_device_lists = True  # ... and has ``device_output``: the lists left on the device
+    PANEL_BYTES = 1 << 30  # score panel of one recommend / score step
 
     users: Vocabulary | None = None
     items: Vocabulary
@@ -464,12 +470,28 @@ class BiasedMFScorer(UsesTrainer, Component):
     def _device_state(self):
         def upload():
             d = D.device()
-            return {"device": d, "Q": D.to_device_padded(self.item_embeddings, d)}
+            f32 = lambda a: None if a is None else torch.from_numpy(  # noqa: E731
+                np.ascontiguousarray(a, dtype=np.float32)).to(d)
+            kept = self.user_embeddings is not None
+            return {"device": d, "Q": D.to_device_padded(self.item_embeddings, d),
+                    "item_biases": f32(self.bias.item_biases),
+                    "user_biases": f32(self.bias.user_biases) if kept else None}
 
-        return self._device_cache("model", upload, self.item_embeddings)
+        return self._device_cache("model", upload, self.item_embeddings, self.bias,
+                                  self.bias.item_biases, self.bias.user_biases)
 
-    def new_user_embedding(self, user_num, user_items: ItemList):
-        "_explicit.py:56-74: normalise the ratings with the bias model, one explicit row solve."
+    def _device_users(self) -> torch.Tensor:
+        "The stored user embeddings in HBM ([users x KP]), uploaded when a batch first takes one."
+        return self._device_cache(
+            "users", lambda: D.to_device_padded(self.user_embeddings, D.device()),
+            self.user_embeddings)
+
+    def _residual_row(self, user_items: ItemList):
+        """
+        The host part of a fold-in (_explicit.py:56-70): the history's known items with a finite
+        rating in ascending item number, their ratings minus the bias model (float32), and the
+        user bias ``BiasModel.compute_for_items`` derives from the history.
+        """
         inums = user_items.numbers(vocabulary=self.items, missing="negative")
         ratings = user_items.field("rating")
         assert ratings is not None
@@ -478,10 +500,15 @@ class BiasedMFScorer(UsesTrainer, Component):
         biases, u_bias = self.bias.compute_for_items(user_items, None, user_items)
         resid = (ratings - biases)[mask]
         order = np.argsort(inums[mask], kind="stable")
+        return inums[mask][order].astype(np.int32), resid[order].astype(np.float32), u_bias
+
+    def new_user_embedding(self, user_num, user_items: ItemList):
+        "_explicit.py:56-74: normalise the ratings with the bias model, one explicit row solve."
+        nums, resid, u_bias = self._residual_row(user_items)
         st = self._device_state()
         hist = D.DeviceCSR.from_arrays(
-            np.array([0, int(mask.sum())], dtype=np.int64), inums[mask][order].astype(np.int32),
-            resid[order].astype(np.float32), (1, len(self.items)), st["device"])
+            np.array([0, len(nums)], dtype=np.int64), nums, resid, (1, len(self.items)),
+            st["device"])
         u = D.fold_in_explicit(hist, st["Q"], self.config.user_reg, self.config.embedding_size)
         return D.to_host_unpadded(u, self.config.embedding_size)[0], u_bias
 
@@ -516,6 +543,227 @@ class BiasedMFScorer(UsesTrainer, Component):
         all_scores = D.score_dense(u, st["Q"], k)[0].cpu().numpy()
         scores = item_scores(items, self.items, all_scores)
         return self.finalize_scores(user_num, ItemList(items, scores=scores), u_off)
+
+    # -- whole batches of queries ---------------------------------------------------------------
+    # ``__call__`` adds in float64 on a fold-in row (the user bias derived from the history is a
+    # NumPy float64 scalar: NEP 50) and in float32 on a stored row; a batched list holds
+    # float32(the per-query score), formed in the branch's own precision by lk_bmf_finish_*.
+
+    def _batch_ready(self) -> bool:
+        "the bias model has both terms (``BiasedMFTrainer`` always learns both): the kernels' case"
+        return self.bias.item_biases is not None and self.bias.user_biases is not None
+
+    def _panel_rows(self) -> int:
+        return max(1, self.PANEL_BYTES // (4 * max(len(self.items), 1)))
+
+    def _batch_operands(self, queries):
+        """
+        What scoring a batch starts from, with the precedence of ``__call__``: history present
+        and user_embeddings != "prefer" -> fold-in; else the stored row of a known user; else
+        invalid.  Returns (device [B x KP] embeddings, host modes uint8 [B] (``_native.BMF_*``),
+        the same on the device, device float64 [B] user biases -- the history's on a fold-in row,
+        the model's on a stored one --, the histories' CSR (structure: the items to strike), the
+        fold-in plans whose status is read once the scoring is queued behind them).
+
+        A :class:`HistoryBatch` over a float32 training matrix of finite ratings does no
+        per-query host work: ``lk_bmf_residual_rows`` reads the rows by user number, one explicit
+        half-epoch solves every fold-in row, stored rows are gathered by number.  Any other batch
+        computes the residuals per query on the host (``_residual_row``) and uploads one CSR.
+        """
+        queries = resolve_queries(queries, self.items)
+        if isinstance(queries, HistoryBatch) and not queries.lookup.ratings_finite():
+            queries = queries.queries()
+        st = self._device_state()
+        d, cfg = st["device"], self.config
+        B = len(queries)
+        pending: list = []
+        prefer = cfg.user_embeddings == "prefer"
+        if isinstance(queries, HistoryBatch):
+            fold = (queries.lengths > 0) & (not prefer)
+            resid, ub = D.bmf_residual_rows(
+                queries.lookup._device_matrix()["csr"], np.where(fold, queries.user_nums, -1),
+                self.bias.global_bias, st["item_biases"], _damping(self.bias.damping, "user"))
+            # the fold-in rows ARE the histories unless stored rows are preferred
+            hist = queries.csr(with_values=False) if prefer else resid
+        else:
+            fold = np.zeros(B, dtype=bool)
+            ptr = np.zeros(B + 1, dtype=np.int64)
+            idx, val, h_ub = [], [], np.zeros(B, dtype=np.float64)
+            for i, q in enumerate(queries):
+                h = q.query_items
+                if h is not None and len(h) > 0 and not prefer:
+                    nums, res, u_bias = self._residual_row(h)
+                    fold[i] = True
+                    ptr[i + 1] = len(nums)
+                    idx.append(nums)
+                    val.append(res)
+                    h_ub[i] = u_bias  # (a NaN bias came back as 0: the same sum in either type)
+            np.cumsum(ptr, out=ptr)
+            cat = lambda xs, dt: np.concatenate(xs) if xs else np.zeros(0, dt)  # noqa: E731
+            resid = D.DeviceCSR.from_arrays(ptr, cat(idx, np.int32), cat(val, np.float32),
+                                            (B, len(self.items)), d)
+            ub = torch.from_numpy(h_ub).to(d)
+            hp, hi, _ = pack_histories(queries, self.items, unknown="drop", sort=True)
+            hist = D.DeviceCSR.from_arrays(hp, hi, None, (B, len(self.items)), d)
+        if fold.any():
+            u = D.fold_in_explicit(resid, st["Q"], cfg.user_reg, cfg.embedding_size, pending)
+        else:
+            u = torch.zeros((B, D.padded_dim(cfg.embedding_size)), dtype=torch.float32, device=d)
+        stored = self._stored_rows(queries)
+        take = ~fold & (stored >= 0)
+        if take.any():
+            at = torch.from_numpy(np.flatnonzero(take)).to(d)
+            rows = torch.from_numpy(stored[take]).to(d)
+            u[at] = self._device_users()[rows]
+            ub[at] = st["user_biases"][rows].to(torch.float64)
+        mode = np.where(fold, _native.BMF_FOLD,
+                        np.where(take, _native.BMF_STORED, _native.BMF_INVALID)).astype(np.uint8)
+        return u, mode, torch.from_numpy(mode).to(d), ub, hist, pending
+
+    def _stored_rows(self, queries) -> np.ndarray:
+        "per query: the user's row of ``user_embeddings``, -1 = none"
+        return user_numbers(queries, None if self.user_embeddings is None else self.users)
+
+    def _query_list(self, queries) -> list[RecQuery]:
+        if isinstance(queries, HistoryBatch):
+            return queries.queries()
+        return [RecQuery.create(q) for q in queries]
+
+    def recommend_batch(self, queries, n: int | None, *, exclude_history: bool = True,
+                        device_output: bool = False):
+        """
+        Top-``n`` lists for many queries at once -- what the ``recommender`` pipeline computes one
+        query at a time: fold-in or stored row, every item scored, the query's own items struck,
+        ``TopNRanker``.  ``queries``: a list of queries, or a :class:`lkpy_amd.basic.HistoryBatch`
+        (training histories by user number: no per-query host work).  The batch goes through in
+        panels of at most ``PANEL_BYTES``: ``lk_score_dense``, ``lk_bmf_finish_panel`` (biases
+        added as ``__call__`` adds them, history struck), ``lk_argtopn``, ``lk_take_scores``.
+        ``n`` negative or None: every candidate, ranked.  Returns (item numbers [B x n] with -1
+        padding, scores [B x n] float32 with NaN padding) as host arrays (``device_output``:
+        device tensors); a query with nothing to score is all padding.
+        """
+        n = -1 if n is None else int(n)
+        if not self._batch_ready():
+            return self._recommend_per_query(queries, n, exclude_history, device_output)
+        u, _mode, d_mode, ub, hist, pending = self._batch_operands(queries)
+        st = self._device_state()
+        B = u.shape[0]
+        cols = len(self.items) if n < 0 else n
+        oi = torch.full((B, cols), -1, dtype=torch.int32, device=st["device"])
+        osc = torch.full((B, cols), float("nan"), dtype=torch.float32, device=st["device"])
+        step = self._panel_rows()
+        for lo in range(0, B, step):
+            hi = min(B, lo + step)
+            panel = D.score_dense(u[lo:hi], st["Q"], self.config.embedding_size)
+            D.bmf_finish_panel(panel, d_mode[lo:hi], ub[lo:hi], self.bias.global_bias,
+                               st["item_biases"],
+                               hist.indptr[lo:hi + 1] if exclude_history else None,
+                               hist.indices if exclude_history else None)
+            idx = D.argtopn(panel, n)
+            oi[lo:hi, :idx.shape[1]] = idx
+            osc[lo:hi, :idx.shape[1]] = D.take_scores(panel, idx)
+        for plan in pending:
+            plan.check_status()  # RuntimeError("ALS solve error: ...") like the fold-in alone
+        if device_output:
+            return oi, osc
+        return D.lists_to_host(oi, osc)
+
+    def _recommend_per_query(self, queries, n: int, exclude_history: bool, device_output: bool):
+        "``recommend_batch`` through ``__call__``: a bias model set by hand without both terms"
+        qs = self._query_list(queries)
+        cols = len(self.items) if n < 0 else n
+        oi = np.full((len(qs), cols), -1, dtype=np.int32)
+        osc = np.full((len(qs), cols), np.nan, dtype=np.float32)
+        for i, q in enumerate(qs):
+            cand = ItemList.from_vocabulary(self.items)
+            h = q.query_items
+            if exclude_history and h is not None and len(h) > 0:
+                nums = h.numbers(vocabulary=self.items, missing="negative")
+                cand = cand.remove(numbers=nums[nums >= 0])
+            top = self(q, cand).top_n(n)
+            oi[i, :len(top)] = top.numbers(vocabulary=self.items)
+            osc[i, :len(top)] = top.scores()
+        if device_output:
+            d = self._device_state()["device"]
+            return torch.from_numpy(oi).to(d), torch.from_numpy(osc).to(d)
+        return oi, osc
+
+    def dense_scores_batch(self, queries):
+        """
+        Every item's score for many queries at once, left on the device: (panel f32 [B x items],
+        valid, history CSR) -- ``recommend_batch``'s operands scored by ``lk_score_dense`` and
+        finished by ``lk_bmf_finish_panel``.  The row of a query that cannot be scored is NaN; the
+        history is for the caller to exclude.
+        """
+        if not self._batch_ready():
+            qs = self._query_list(queries)
+            every = ItemList.from_vocabulary(self.items)
+            rows = np.stack([np.asarray(self(q, every).scores(), dtype=np.float32) for q in qs]) \
+                if qs else np.zeros((0, len(self.items)), np.float32)
+            d = self._device_state()["device"]
+            hp, hi, _ = pack_histories(qs, self.items, unknown="drop", sort=True)
+            return (torch.from_numpy(rows).to(d), ~np.isnan(rows).all(axis=1),
+                    D.DeviceCSR.from_arrays(hp, hi, None, rows.shape, d))
+        u, mode, d_mode, ub, hist, pending = self._batch_operands(queries)
+        st = self._device_state()
+        panel = D.score_dense(u, st["Q"], self.config.embedding_size)
+        D.bmf_finish_panel(panel, d_mode, ub, self.bias.global_bias, st["item_biases"])
+        for plan in pending:
+            plan.check_status()
+        return panel, mode != _native.BMF_INVALID, hist
+
+    def _score_pairs(self, queries, tgt_ptr: np.ndarray, d_ptr: torch.Tensor,
+                     d_nums: torch.Tensor) -> torch.Tensor:
+        """
+        The scores of ragged target lists (host int64 offsets ``tgt_ptr`` [B + 1], the same and
+        this scorer's item numbers on the device; -1 = unknown -> NaN), device f32 [entries]: per
+        panel of at most ``PANEL_BYTES`` one ``lk_score_dense`` and one ``lk_bmf_finish_pairs``,
+        which reads each dot product out of the panel -- the entry ``__call__`` reads.
+        """
+        u, _mode, d_mode, ub, _hist, pending = self._batch_operands(queries)
+        st = self._device_state()
+        B = u.shape[0]
+        out = torch.empty(int(tgt_ptr[-1]), dtype=torch.float32, device=st["device"])
+        step = self._panel_rows()
+        for lo in range(0, B, step):
+            hi = min(B, lo + step)
+            first, count = int(tgt_ptr[lo]), int(tgt_ptr[hi] - tgt_ptr[lo])
+            if count == 0:
+                continue
+            panel = D.score_dense(u[lo:hi], st["Q"], self.config.embedding_size)
+            D.bmf_finish_pairs(panel, d_mode[lo:hi], ub[lo:hi], self.bias.global_bias,
+                               st["item_biases"], d_ptr[lo:hi + 1], d_nums, first, count, out)
+        for plan in pending:
+            plan.check_status()
+        return out
+
+    def score_batch(self, queries, item_lists) -> list[ItemList]:
+        "``__call__`` for many queries: the scores are float32(the per-query score), bit for bit."
+        qs = [RecQuery.create(q) for q in queries]
+        if not self._batch_ready():
+            return [self(q, il) for q, il in zip(qs, item_lists)]
+        ptr, nums = pack_targets(item_lists, self.items)
+        d = self._device_state()["device"]
+        if int(ptr[-1]) == 0:
+            return [ItemList(il, scores=np.zeros(0, np.float32)) for il in item_lists]
+        scores = self._score_pairs(
+            qs, ptr, torch.from_numpy(ptr).to(d),
+            torch.from_numpy(np.ascontiguousarray(nums, dtype=np.int32)).to(d)).cpu().numpy()
+        return [ItemList(il, scores=scores[ptr[i]:ptr[i + 1]])
+                for i, il in enumerate(item_lists)]
+
+    def predict_history_batch(self, batch, tgt_ptr, tgt_items, *, h_tgt_ptr=None):
+        """
+        ``score_batch`` for training histories by user number (``UserTrainingHistoryLookup.batch``)
+        and targets already on the device: ``tgt_ptr`` int64 [B + 1], ``tgt_items`` int32 (this
+        scorer's item numbers, -1 = unknown); ``h_tgt_ptr``: the offsets' host copy when the
+        caller has one.  Returns device f32 [entries].
+        """
+        if not self._batch_ready():
+            raise RuntimeError("predict_history_batch needs a bias model with both terms")
+        if h_tgt_ptr is None:
+            h_tgt_ptr = tgt_ptr.cpu().numpy()
+        return self._score_pairs(batch, np.asarray(h_tgt_ptr, dtype=np.int64), tgt_ptr, tgt_items)
 
 
 class BiasedMFTrainer(ModelTrainer):

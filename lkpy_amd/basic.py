@@ -30,6 +30,9 @@ class UserTrainingHistoryLookup(Component):
         return hasattr(self, "interactions")
 
     def train(self, data: Dataset, options: TrainingOptions = TrainingOptions()):
+        # a retrain drops the HBM copy of the previous training matrix (and what was learned
+        # about it, ``ratings_finite``): batch() must never cut rows out of the old one
+        self.__dict__.pop("_dev", None)
         self.interactions = data.interactions(self.config.interaction_class).matrix()
 
     def __call__(self, query) -> RecQuery:
@@ -59,6 +62,25 @@ class UserTrainingHistoryLookup(Component):
                     "has_ratings": rat is not None}
 
         return self._device_cache("matrix", upload, self.interactions)
+
+    def ratings_finite(self) -> bool:
+        """
+        Is every rating of the HBM-resident training matrix finite (and float32 on the host, so
+        that the device copy is the host's values)?  Scanned once per uploaded matrix and kept
+        with it: the scorers that subtract a bias model from whole rows on the device
+        (``BiasedMFScorer``) take the per-query rule -- non-finite ratings are dropped -- only
+        through the host.
+        """
+        st = self._device_matrix()
+        if "ratings_finite" not in st:
+            import torch
+
+            rat = self.interactions._ds._attrs.get("rating")
+            vals = st["csr"].values
+            st["ratings_finite"] = bool(
+                rat is not None and rat.dtype == np.float32 and vals is not None
+                and (vals.numel() == 0 or bool(torch.isfinite(vals).all().item())))
+        return st["ratings_finite"]
 
     def batch(self, user_ids) -> "HistoryBatch":
         """

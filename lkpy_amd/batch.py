@@ -223,10 +223,11 @@ def predict(pipe: Pipeline, pairs, *, batch_size: int = 16384) -> ItemListCollec
     columns (users in order of first appearance, rows in order within a user; the other columns
     become fields of the lists).
 
-    An item-kNN pipeline (``std:topn-predict`` with its ``BiasScorer`` fallback, or without a
-    fallback) whose vocabularies agree is run as whole batches by user number
-    (:func:`_predict_batched`): the lists are the per-query composition's bit for bit.  Every
-    other pipeline runs query by query.
+    An item-kNN or a biased-MF (``BiasedMFScorer``) pipeline (``std:topn-predict`` with its
+    ``BiasScorer`` fallback, or without a fallback) whose vocabularies agree is run as whole
+    batches by user number (:func:`_predict_batched`): the lists are the per-query composition's
+    bit for bit (float32 of it where the biased-MF scorer alone hands out float64).  Every other
+    pipeline runs query by query.
     """
     keys, offsets, item_ids, fields, lists = _ragged_pairs(pairs)
     parts = _batched_predict_parts(pipe)
@@ -286,23 +287,34 @@ def _ragged_pairs(pairs):
 
 def _batched_predict_parts(pipe: Pipeline):
     """(scorer, lookup, BiasScorer or None) when ``rating-predictor`` can run by user number:
-    an ``ItemKNNScorer``, a lookup with ``batch``, no merger or a ``FallbackScorer`` over a
-    ``BiasScorer``, and one item (and user) vocabulary throughout; None otherwise."""
+    an ``ItemKNNScorer`` or a ``BiasedMFScorer``, a lookup with ``batch``, no merger or a
+    ``FallbackScorer`` over a ``BiasScorer``, and one item (and user) vocabulary throughout; None
+    otherwise."""
+    from .als import BiasedMFScorer
     from .basic import BiasScorer, FallbackScorer
     from .knn import ItemKNNScorer
 
     scorer = pipe.node("scorer").component
     lookup = pipe.node("history-lookup").component
-    if not isinstance(scorer, ItemKNNScorer) or not hasattr(lookup, "batch") or \
-            not scorer.is_trained() or getattr(lookup, "interactions", None) is None:
+    if not isinstance(scorer, (ItemKNNScorer, BiasedMFScorer)) or not hasattr(lookup, "batch") \
+            or getattr(lookup, "interactions", None) is None:
         return None
     ds = lookup.interactions._ds
     same = lambda a, b: a is b or a == b  # noqa: E731
-    if not same(scorer.items, ds.items):
-        return None
     rating = ds._attrs.get("rating")
-    if scorer.config.explicit and rating is None:
-        return None  # (the per-query path raises)
+    if isinstance(scorer, BiasedMFScorer):
+        # trained, a bias model with both terms, ratings to fold in (the per-query path raises
+        # without), and the lookup's users where stored rows are taken by user number
+        if getattr(scorer, "item_embeddings", None) is None or \
+                getattr(scorer, "bias", None) is None or not scorer._batch_ready() or \
+                rating is None or not same(scorer.items, ds.items) or \
+                (scorer.users is not None and not same(scorer.users, ds.users)):
+            return None
+    else:
+        if not scorer.is_trained() or not same(scorer.items, ds.items):
+            return None
+        if scorer.config.explicit and rating is None:
+            return None  # (the per-query path raises)
     bias = None
     merger = pipe.nodes.get("rating-merger")
     if merger is not None:
@@ -329,6 +341,10 @@ def _predict_batched(parts, keys, offsets, item_ids, fields, batch_size: int):
     (``lk_predict_merge``) and one download of scores, counts and flags.  The lists carry the
     caller's item ids and fields; a query without history has no ``nbr_counts``
     (item.py:238-245), ``is_fallback`` exists with a fallback only.
+
+    A ``BiasedMFScorer`` scores by ``predict_history_batch`` (fold-in, ``lk_score_dense``,
+    ``lk_bmf_finish_pairs``), has no item means to add back and no ``nbr_counts``; its fallback
+    is the same merge.
     """
     import torch
 
@@ -343,12 +359,13 @@ def _predict_batched(parts, keys, offsets, item_ids, fields, batch_size: int):
     nums = scorer.items.numbers(item_ids, missing="negative") if len(item_ids) else \
         np.zeros(0, np.int32)
     total = int(offsets[-1])
+    knn = hasattr(scorer, "score_history_batch")  # (else: BiasedMFScorer)
     scores = np.empty(total, np.float32)
-    counts = np.empty(total, np.int32)
+    counts = np.empty(total, np.int32) if knn else None
     fb = np.empty(total, np.bool_) if bias is not None else None
     nohist = np.empty(B, np.bool_)
-    d = scorer._device_sims()["device"]
-    means = scorer._device_means()
+    d = scorer._device_sims()["device"] if knn else scorer._device_state()["device"]
+    means = scorer._device_means() if knn else None
     item_biases = bias._device_item_biases() if bias is not None else None
     for s0 in range(0, B, batch_size):
         s1 = min(B, s0 + batch_size)
@@ -366,29 +383,36 @@ def _predict_batched(parts, keys, offsets, item_ids, fields, batch_size: int):
         d_packed = torch.from_numpy(packed).to(d)
         d_ptr = d_packed[:2 * (nb + 1)].view(torch.int64)
         d_nums = d_packed[2 * (nb + 1):2 * (nb + 1) + n]
-        s_dev, c_dev = scorer.score_history_batch(hb, d_ptr, d_nums)
+        if knn:
+            s_dev, c_dev = scorer.score_history_batch(hb, d_ptr, d_nums)
+        else:
+            s_dev = scorer.predict_history_batch(hb, d_ptr, d_nums,
+                                                 h_tgt_ptr=offsets[s0:s1 + 1] - lo)
         out = torch.empty(9 * n, dtype=torch.uint8, device=d)  # scores | counts | flags
         if bias is not None:
             ub, add = bias.user_offsets_batch(hb)
             D.predict_merge(d_ptr, d_nums, n_items, s_dev, means, fallback=True,
                             global_bias=bias.model.global_bias, item_biases=item_biases,
                             user_bias=ub, user_add=add, out_is_fallback=out[8 * n:])
-        else:
+        elif knn:
             D.predict_merge(d_ptr, d_nums, n_items, s_dev, means)
         out[:4 * n] = s_dev.view(torch.uint8)
-        out[4 * n:8 * n] = c_dev.view(torch.uint8)
+        if knn:
+            out[4 * n:8 * n] = c_dev.view(torch.uint8)
         host = out.cpu().numpy()
         scores[lo:hi] = host[:4 * n].view(np.float32)
-        counts[lo:hi] = host[4 * n:8 * n].view(np.int32)
+        if knn:
+            counts[lo:hi] = host[4 * n:8 * n].view(np.int32)
         if fb is not None:
             fb[lo:hi] = host[8 * n:].view(np.bool_)
     out_fields = dict(fields)
-    out_fields["nbr_counts"] = counts
+    if knn:
+        out_fields["nbr_counts"] = counts
     out_fields["score"] = scores
     if fb is not None:
         out_fields["is_fallback"] = fb
     return ItemListCollection.from_ragged(keys, offsets, item_ids, out_fields, key=("user_id",),
-                                          absent={"nbr_counts": nohist})
+                                          absent={"nbr_counts": nohist} if knn else None)
 
 
 def _predict_loop(pipe: Pipeline, pairs: dict) -> ItemListCollection:
