@@ -1333,6 +1333,63 @@ int lk_adamw_dense(float *d_param, float *d_exp_avg, float *d_exp_avg_sq, const 
                    int64_t n, int32_t k, int32_t ld, double lr, double weight_decay, double beta1,
                    double beta2, double eps, double bias_corr1, double bias_corr2, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Hierarchical Poisson factorization (csrc/hpf.hip): the device steps of `HPFScorer.train`
+ * (src/lenskit/hpf.py:81-100), which in the reference is `hpfrec.HPF.fit`.  The algorithm is
+ * coordinate-ascent variational inference (Gopalan, Hofman, Blei 2015, Algorithm 1) on Gamma
+ * shape / rate panels: gamma (users), lambda (items), kappa and tau (the hyper-rates).
+ * Panels are float32 [n x ld], ld a multiple of 4 covering k <= LK_FLEXMF_MAX_K and at most
+ * LK_FLEXMF_MAX_K, bases 16-byte aligned.  Every call is asynchronous on `stream`; nothing is
+ * atomic on floats and every sum has a fixed order.
+ *
+ * lk_hpf_expect_log (hpf.py:81-100; Algorithm 1's E[log theta], E[log beta]):
+ *   d_out[r][c] = psi(d_shp[r][c]) - log(d_rte[r][c]) for c < k, evaluated in float64 (digamma by
+ *   its recurrence up to x >= 6, then the asymptotic series) and rounded to float32 once; the
+ *   columns [k, ld) are written as zero.
+ *
+ * lk_hpf_shape_pass (hpf.py:81-100; Algorithm 1's multinomial phi and the shape updates): for
+ *   every entry e = (r, col_e, y_e) of the CSR matrix, s_c = d_e_rows[r][c] + d_e_cols[col_e][c],
+ *   m = max_c s_c, p_c = exp(s_c - m), Z = sum_c p_c (the lane's four columns in column order,
+ *   then a butterfly over the row's lanes: an order that depends on ld alone), w = y_e / Z;
+ *   d_out[r][c] = prior + sum_e w p_c, c < k; the columns [k, ld) are written as zero.  A row of
+ *   at most lk_spmm_split() entries is one fused-multiply-add chain per column in entry order
+ *   from zero; a longer one is cut into segments of that length, each such a chain, added in
+ *   segment order from zero; the prior is added last.  A row has the same bits alone, in any
+ *   matrix, on any grid.  An index outside 0..n_cols-1 contributes nothing; offsets that do not
+ *   describe entries of the matrix make the row empty (d_out[r][c] = prior).  A spread of s
+ *   beyond float32's exp range gives zero weights, never NaN.  The item side is the same call on
+ *   the transposed CSR (lk_csr_transpose, once per fit) with the two E panels exchanged.
+ *   d_out must not alias an operand.
+ *
+ * lk_hpf_rates (hpf.py:81-100; Algorithm 1's rate updates of one side and of its hyper-rate):
+ *   d_rte[r][c] = shp_hyper / d_hyper_rte[r] + d_other_colsum[c], d_mean[r][c] = d_shp[r][c] /
+ *   d_rte[r][c] (float32; pad columns zero), then d_hyper_rte[r] = prior_ratio + sum_c
+ *   d_mean[r][c] (float64 in column order, rounded once) and d_colsum[c] = sum_r d_mean[r][c]:
+ *   float64 partial sums over blocks of lk_hpf_rates_block() consecutive rows, each in row
+ *   order, added in block order and rounded once -- a function of the panel alone.  d_ws:
+ *   lk_hpf_rates_workspace_bytes(n, k) bytes.  d_colsum must not alias d_other_colsum.
+ *
+ * lk_hpf_loglik_rows (hpf.py:81-100; the data term of hpfrec's `train-llk` stopping criterion):
+ *   d_out[r] = sum over the entries of row r of y_e log(d_theta[r] . d_beta[col_e]), the inner
+ *   product and the sum in float64, the sum in entry order; an index outside 0..n_cols-1
+ *   contributes nothing.
+ * ---------------------------------------------------------------------- */
+int lk_hpf_expect_log(const float *d_shp, const float *d_rte, int64_t n, int32_t k, int32_t ld,
+                      float *d_out, void *stream);
+int lk_hpf_shape_pass(const void *d_indptr, int indptr_is_64, const int32_t *d_indices,
+                      const float *d_values, int64_t n_rows, int64_t n_cols, int64_t nnz,
+                      const float *d_e_rows, const float *d_e_cols, int32_t k, int32_t ld,
+                      float prior, float *d_out, void *stream);
+int32_t lk_hpf_rates_block(void);
+size_t lk_hpf_rates_workspace_bytes(int64_t n, int32_t k);
+int lk_hpf_rates(const float *d_shp, int64_t n, int32_t k, int32_t ld, double shp_hyper,
+                 double prior_ratio, float *d_hyper_rte, const float *d_other_colsum,
+                 float *d_rte, float *d_mean, float *d_colsum, void *d_ws, void *stream);
+int lk_hpf_loglik_rows(const void *d_indptr, int indptr_is_64, const int32_t *d_indices,
+                       const float *d_values, int64_t n_rows, int64_t n_cols, int64_t nnz,
+                       const float *d_theta, const float *d_beta, int32_t k, int32_t ld,
+                       double *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

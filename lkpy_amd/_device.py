@@ -2756,3 +2756,178 @@ class LightGCNState:
         if table.shape != (self.n, self.k):
             raise ValueError(f"the embedding table is {(self.n, self.k)}, got {table.shape}")
         self.X[:, :self.k] = torch.from_numpy(np.ascontiguousarray(table)).to(self.dev)
+
+
+# ---- hierarchical Poisson factorization (csrc/hpf.hip) -------------------------------------------
+def hpf_rates_block() -> int:
+    "The rows behind one partial column sum of ``lk_hpf_rates`` (lk_hpf_rates_block)."
+    return int(_native.load().lk_hpf_rates_block())
+
+
+def _hpf_panels(k: int, *panels) -> tuple[int, int]:
+    n, ld = panels[0].shape
+    assert ld == padded_dim(k)
+    for p in panels:
+        assert p.dtype == torch.float32 and p.is_contiguous() and tuple(p.shape) == (n, ld)
+    return n, ld
+
+
+def hpf_expect_log(shp: torch.Tensor, rte: torch.Tensor, k: int,
+                   out: torch.Tensor | None = None) -> torch.Tensor:
+    "``psi(shp) - log(rte)`` of two padded panels, float64 rounded once (lk_hpf_expect_log)."
+    lib = _native.require_gpu()
+    if out is None:
+        out = torch.empty_like(shp)
+    n, ld = _hpf_panels(k, shp, rte, out)
+    check(lib.lk_hpf_expect_log(_ptr(shp), _ptr(rte), n, int(k), ld, _ptr(out), _stream()),
+          "lk_hpf_expect_log")
+    return out
+
+
+def hpf_shape_pass(csr: DeviceCSR, e_rows: torch.Tensor, e_cols: torch.Tensor, k: int,
+                   prior: float, out: torch.Tensor | None = None) -> torch.Tensor:
+    """
+    ``out[r] = prior + sum_e y_e softmax(e_rows[r] + e_cols[col_e])`` over the entries of CSR row
+    r (lk_hpf_shape_pass): the shape update of the rows' side, a padded panel [rows x LD].
+    """
+    lib = _native.require_gpu()
+    n_rows, n_cols = csr.shape
+    if out is None:
+        out = torch.empty_like(e_rows)
+    _, ld = _hpf_panels(k, e_rows, out)
+    _hpf_panels(k, e_cols)
+    assert e_rows.shape[0] == n_rows and e_cols.shape[0] == n_cols
+    assert csr.values is not None and csr.values.dtype == torch.float32
+    check(lib.lk_hpf_shape_pass(_ptr(csr.indptr), 1 if csr.is64 else 0, _ptr(csr.indices),
+                                _ptr(csr.values), n_rows, n_cols, csr.nnz, _ptr(e_rows),
+                                _ptr(e_cols), int(k), ld, float(prior), _ptr(out), _stream()),
+          "lk_hpf_shape_pass")
+    return out
+
+
+def hpf_rates(shp: torch.Tensor, k: int, shp_hyper: float, prior_ratio: float,
+              hyper_rte: torch.Tensor, other_colsum: torch.Tensor, rte: torch.Tensor,
+              mean: torch.Tensor, colsum: torch.Tensor, ws: torch.Tensor | None = None) -> None:
+    """
+    The rate update of one side (lk_hpf_rates): ``rte = shp_hyper / hyper_rte + other_colsum``,
+    ``mean = shp / rte``, then ``hyper_rte = prior_ratio + mean.sum(1)`` (in place) and
+    ``colsum = mean.sum(0)``, both float64 sums of fixed order rounded once.
+    """
+    lib = _native.require_gpu()
+    n, ld = _hpf_panels(k, shp, rte, mean)
+    for v, m in ((hyper_rte, n), (other_colsum, k), (colsum, k)):
+        assert v.dtype == torch.float32 and v.is_contiguous() and v.numel() == m
+    need = lib.lk_hpf_rates_workspace_bytes(n, int(k))
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=shp.device)
+    assert ws.numel() * ws.element_size() >= need
+    check(lib.lk_hpf_rates(_ptr(shp), n, int(k), ld, float(shp_hyper), float(prior_ratio),
+                           _ptr(hyper_rte), _ptr(other_colsum), _ptr(rte), _ptr(mean),
+                           _ptr(colsum), _ptr(ws), _stream()), "lk_hpf_rates")
+
+
+def hpf_loglik_rows(csr: DeviceCSR, theta: torch.Tensor, beta: torch.Tensor,
+                    k: int) -> torch.Tensor:
+    "Per row ``sum_e y_e log(theta[r] . beta[col_e])`` in float64 (lk_hpf_loglik_rows)."
+    lib = _native.require_gpu()
+    n_rows, n_cols = csr.shape
+    _, ld = _hpf_panels(k, theta)
+    _hpf_panels(k, beta)
+    assert theta.shape[0] == n_rows and beta.shape[0] == n_cols
+    assert csr.values is not None and csr.values.dtype == torch.float32
+    out = torch.empty(n_rows, dtype=torch.float64, device=theta.device)
+    check(lib.lk_hpf_loglik_rows(_ptr(csr.indptr), 1 if csr.is64 else 0, _ptr(csr.indices),
+                                 _ptr(csr.values), n_rows, n_cols, csr.nnz, _ptr(theta),
+                                 _ptr(beta), int(k), ld, _ptr(out), _stream()),
+          "lk_hpf_loglik_rows")
+    return out
+
+
+def _f64_rowsum_f32(x: np.ndarray, first: float) -> np.ndarray:
+    "``first + sum_c x[:, c]`` in float64 in column order, rounded to float32 once"
+    s = np.zeros(len(x), dtype=np.float64)
+    for c in range(x.shape[1]):
+        s += x[:, c]
+    return (first + s).astype(np.float32)
+
+
+class HPFState:
+    """
+    The variational state of a hierarchical Poisson factorization in HBM: the count matrix Y and
+    its transpose (CSR), the shape, rate and mean panels of the users (gamma, theta) and of the
+    items (lambda, beta) [n x LD], the hyper-rates kappa [users] and tau [items], the column sums
+    T = sum_u theta and S = sum_i beta [k], two E panels and the rate pass's workspace.
+
+    ``start``: the four host panels gamma_shp, gamma_rte, lambda_shp, lambda_rte ([n x k]
+    float32); the means, hyper-rates and column sums of the start are formed on the host as
+    ``lk_hpf_rates`` forms them.  ``iterate`` queues whole iterations -- two
+    ``lk_hpf_expect_log``, two ``lk_hpf_shape_pass``, two ``lk_hpf_rates`` -- and synchronises
+    nothing; ``loglik`` does.
+    """
+
+    def __init__(self, csr: DeviceCSR, start, *, a: float = 0.3, a_prime: float = 0.3,
+                 b_prime: float = 1.0, c: float = 0.3, c_prime: float = 0.3,
+                 d_prime: float = 1.0, lgamma_sum: float = 0.0):
+        g_shp, g_rte, l_shp, l_rte = (np.ascontiguousarray(p, dtype=np.float32) for p in start)
+        n_users, n_items = csr.shape
+        self.k = k = g_shp.shape[1]
+        if not 1 <= k <= _native.FLEXMF_MAX_K:
+            raise ValueError(f"unsupported embedding size {k} "
+                             f"(supported: 1..{_native.FLEXMF_MAX_K})")
+        if g_shp.shape != (n_users, k) or g_rte.shape != (n_users, k) or \
+                l_shp.shape != (n_items, k) or l_rte.shape != (n_items, k):
+            raise ValueError("the start panels do not fit the matrix")
+        for name, v in (("a", a), ("a_prime", a_prime), ("b_prime", b_prime), ("c", c),
+                        ("c_prime", c_prime), ("d_prime", d_prime)):
+            if not v > 0:
+                raise ValueError(f"{name} must be positive, got {v}")
+        self.dev = dev = csr.indices.device
+        self.csr, self.csr_t = csr, csr_transpose(csr)
+        self.a, self.c = float(a), float(c)
+        self.k_shp, self.t_shp = a_prime + k * a, c_prime + k * c
+        self.k_ratio, self.t_ratio = a_prime / b_prime, c_prime / d_prime
+        self.lgamma_sum = float(lgamma_sum)
+        theta, beta = g_shp / g_rte, l_shp / l_rte
+
+        def vec(x):
+            return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
+
+        self.g_shp, self.g_rte = to_device_padded(g_shp, dev), to_device_padded(g_rte, dev)
+        self.l_shp, self.l_rte = to_device_padded(l_shp, dev), to_device_padded(l_rte, dev)
+        self.theta, self.beta = to_device_padded(theta, dev), to_device_padded(beta, dev)
+        self.k_rte = vec(_f64_rowsum_f32(theta, self.k_ratio))
+        self.t_rte = vec(_f64_rowsum_f32(beta, self.t_ratio))
+        self.T = vec(theta.sum(axis=0, dtype=np.float64))
+        self.S = vec(beta.sum(axis=0, dtype=np.float64))
+        self.e_u, self.e_i = torch.empty_like(self.g_shp), torch.empty_like(self.l_shp)
+        lib = _native.require_gpu()
+        self._ws = torch.empty(max(lib.lk_hpf_rates_workspace_bytes(n_users, k),
+                                   lib.lk_hpf_rates_workspace_bytes(n_items, k)),
+                               dtype=torch.uint8, device=dev)
+        self.iterations = 0
+
+    def iterate(self, n: int = 1) -> None:
+        "``n`` iterations, queued: users against the items as they stand, then items"
+        k = self.k
+        for _ in range(int(n)):
+            hpf_expect_log(self.g_shp, self.g_rte, k, self.e_u)
+            hpf_expect_log(self.l_shp, self.l_rte, k, self.e_i)
+            hpf_shape_pass(self.csr, self.e_u, self.e_i, k, self.a, self.g_shp)
+            hpf_shape_pass(self.csr_t, self.e_i, self.e_u, k, self.c, self.l_shp)
+            hpf_rates(self.g_shp, k, self.k_shp, self.k_ratio, self.k_rte, self.S, self.g_rte,
+                      self.theta, self.T, self._ws)
+            hpf_rates(self.l_shp, k, self.t_shp, self.t_ratio, self.t_rte, self.T, self.l_rte,
+                      self.beta, self.S, self._ws)
+            self.iterations += 1
+
+    def loglik(self) -> float:
+        """``sum y log(theta . beta) - sum_c T_c S_c - sum lgamma(y + 1)``: the rows from
+        ``lk_hpf_loglik_rows`` added on the host in row order (synchronises)."""
+        rows = hpf_loglik_rows(self.csr, self.theta, self.beta, self.k).cpu().numpy()
+        ts = torch.stack([self.T, self.S]).cpu().numpy().astype(np.float64)
+        data = float(np.cumsum(rows)[-1]) if len(rows) else 0.0
+        return data - float(np.cumsum(ts[0] * ts[1])[-1]) - self.lgamma_sum
+
+    def host_factors(self) -> tuple[np.ndarray, np.ndarray]:
+        "(theta [users x k], beta [items x k]) on the host"
+        return to_host_unpadded(self.theta, self.k), to_host_unpadded(self.beta, self.k)

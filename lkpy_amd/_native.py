@@ -348,6 +348,20 @@ def _declare(lib):
         "lk_adamw_dense": (
             c_int, [vp, vp, vp, vp, c_int64, c_int32, c_int32] + [ctypes.c_double] * 7 + [vp]
         ),
+        "lk_hpf_expect_log": (c_int, [vp, vp, c_int64, c_int32, c_int32, vp, vp]),
+        "lk_hpf_shape_pass": (
+            c_int, [vp, c_int, vp, vp, c_int64, c_int64, c_int64, vp, vp, c_int32, c_int32,
+                    c_float, vp, vp]
+        ),
+        "lk_hpf_rates_block": (c_int32, []),
+        "lk_hpf_rates_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+        "lk_hpf_rates": (
+            c_int, [vp, c_int64, c_int32, c_int32, ctypes.c_double, ctypes.c_double, vp, vp, vp,
+                    vp, vp, vp, vp]
+        ),
+        "lk_hpf_loglik_rows": (
+            c_int, [vp, c_int, vp, vp, c_int64, c_int64, c_int64, vp, vp, c_int32, c_int32, vp, vp]
+        ),
         "lk_als_implicit_half_epoch_host": (
             c_int,
             [vp, c_int, vp, vp, c_int64, c_int64, c_int32, vp, vp, vp, c_int32, vp],
