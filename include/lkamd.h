@@ -402,6 +402,16 @@ int lk_score_topk(const float *d_users, int32_t ld_users, int64_t n_users, const
                   int32_t ld_items, int64_t n_items, int32_t k, int32_t n,
                   const int64_t *d_excl_ptr, const int32_t *d_excl_items, void *d_ws,
                   int32_t *d_out_idx, float *d_out_score, void *stream);
+/* Test hook: what the calling thread's last lk_score_topk call did, from values the host holds
+ * anyway (no launch, copy or synchronisation of its own).  out12 = {path: 1 fused, 0 panel, -1 no
+ * call yet; fused batches; parts of the item split (1: none); candidates per part; 1 if a batch
+ * ran its two row ranges on two streams; rows listed for the exact redo; 1 if that list
+ * overflowed and EVERY row went through the panel path; sample stride; sample items; threshold
+ * rank of a row without exclusions; padded features; 1 class-maxima / 0 sample-panel stage 1}
+ * (everything after `path` is 0 for a panel call, the padded features excepted).  The rows redone
+ * one by one (at most 4096, in the order the device listed them) are copied to redo_rows[0 .. cap);
+ * returns how many were copied.  Product code must not read it. */
+int32_t lk_score_topk_last_report(int64_t *out12, int32_t *redo_rows, int32_t cap);
 
 /* Scores only: out[b][i] = the same exact k-ordered chain, for every (user, item) pair
  * (`ALSBase.__call__`, src/lenskit/als/_common.py:159-170). */

@@ -810,6 +810,25 @@ def score_topk(users: torch.Tensor, items: torch.Tensor, k: int, n: int,
     return out_idx, out_sc
 
 
+def score_topk_last_report() -> dict:
+    """
+    What this thread's last ``score_topk`` call did (lk_score_topk_last_report; test hook, not for
+    product code): path, fused geometry, and the rows redone exactly through the panel path.
+    """
+    import ctypes
+
+    out = (ctypes.c_int64 * 12)()
+    rows = (ctypes.c_int32 * 4096)()
+    m = _native.load().lk_score_topk_last_report(out, rows, 4096)
+    names = ("path", "batches", "parts", "part_cap", "overlap", "n_redo", "all_panel", "stride",
+             "n_sample", "r_tau", "kp", "cmax")
+    rep = {k: int(v) for k, v in zip(names, out)}
+    rep["path"] = {1: "fused", 0: "panel"}.get(rep["path"])
+    rep["overlap"], rep["all_panel"], rep["cmax"] = (bool(rep[k]) for k in ("overlap", "all_panel", "cmax"))
+    rep["redo_rows"] = sorted(int(rows[i]) for i in range(m))
+    return rep
+
+
 def argtopn(scores: torch.Tensor, n: int) -> torch.Tensor:
     """
     Per-row top-N indices (lk_argtopn) of a [rows x len] f32 device matrix, -1 padding;

@@ -252,6 +252,7 @@ def _declare(lib):
             c_int,
             [vp, c_int32, c_int64, vp, c_int32, c_int64, c_int32, c_int32, vp, vp, vp, vp, vp, vp],
         ),
+        "lk_score_topk_last_report": (c_int32, [POINTER(c_int64), POINTER(c_int32), c_int32]),
         "lk_score_dense": (
             c_int, [vp, c_int32, c_int64, vp, c_int32, c_int64, c_int32, vp, c_int64, vp]
         ),

@@ -2228,6 +2228,18 @@ static FusedLayout fused_layout(int64_t n_users, int64_t n_items, int32_t n, int
     return L;
 }
 
+// What the calling thread's last lk_score_topk call did (lk_score_topk_last_report: test hook).
+// Filled from values the host holds anyway -- no launch, copy or synchronisation of its own.
+struct TopkReport {
+    int64_t v[12] = {-1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    std::vector<int> rows;  // the rows redone one by one
+};
+static TopkReport &topk_report()
+{
+    static thread_local TopkReport r;
+    return r;
+}
+
 }  // namespace lk
 
 #ifdef LK_WSEL_PHASES
@@ -2256,6 +2268,17 @@ extern "C" size_t lk_score_topk_workspace_bytes(int64_t n_users, int64_t n_items
     // fused path: its buffers sit behind the panel (the panel serves overflowing batches)
     if (lk::use_fused(n_users, n_items, n)) bytes += lk::fused_layout(n_users, n_items, n).bytes;
     return bytes;
+}
+
+extern "C" int32_t lk_score_topk_last_report(int64_t *out12, int32_t *redo_rows, int32_t cap)
+{
+    const lk::TopkReport &rep = lk::topk_report();
+    if (out12)
+        for (int i = 0; i < 12; ++i) out12[i] = rep.v[i];
+    int32_t m = 0;
+    if (redo_rows)
+        for (; m < cap && (size_t)m < rep.rows.size(); ++m) redo_rows[m] = rep.rows[(size_t)m];
+    return m;
 }
 
 namespace lk {
@@ -2351,6 +2374,10 @@ extern "C" int lk_score_topk(const float *d_users, int32_t ld_users, int64_t n_u
     LK_REQUIRE(d_users && d_ws && d_out_idx && (n_items == 0 || d_items),
                "lk_score_topk: null pointer");
     hipStream_t st = lk::as_stream(stream);
+    lk::TopkReport &rep = lk::topk_report();
+    for (int64_t &x : rep.v) x = 0;  // [0] = 0: the panel path, unless the fused path says otherwise
+    rep.rows.clear();
+    rep.v[10] = KP;
     float *panel = static_cast<float *>(d_ws);
     const int64_t ld_s = lk::padded_items(n_items);
     const int64_t pb = n_users < lk::score_batch() ? n_users : lk::score_batch();
@@ -2400,6 +2427,14 @@ extern "C" int lk_score_topk(const float *d_users, int32_t ld_users, int64_t n_u
         const bool use_cmax = lk::cmax_usable(n_items, n);
         const int64_t FUSED_ROWS = lk::fused_rows(ld_sub, !use_cmax);
         const int64_t batches = (n_users + FUSED_ROWS - 1) / FUSED_ROWS;
+        rep.v[0] = 1;
+        rep.v[1] = batches;
+        rep.v[2] = batches == 1 ? L.parts : 1;
+        rep.v[3] = batches == 1 ? L.part_cap : lk::FUSED_CAP;
+        rep.v[7] = stride;
+        rep.v[8] = n_sub;
+        rep.v[9] = r_tau;
+        rep.v[11] = use_cmax ? 1 : 0;
         LK_HIP_CHECK(hipMemsetAsync(redo, 0, sizeof(int), st));
         // the sample rows of the item factors, contiguous
         {
@@ -2555,6 +2590,7 @@ extern "C" int lk_score_topk(const float *d_users, int32_t ld_users, int64_t n_u
                                    lk::FUSED_BIG_CAP, list);
             };
             if (rows_a < rows) {
+                rep.v[4] = 1;
                 lk::TopkSide &sd = lk::topk_side();
                 if (!sd.stream) {
                     LK_HIP_CHECK(hipStreamCreateWithFlags(&sd.stream, hipStreamNonBlocking));
@@ -2593,6 +2629,8 @@ extern "C" int lk_score_topk(const float *d_users, int32_t ld_users, int64_t n_u
         LK_HIP_CHECK(hipMemcpyAsync(h_redo.data(), redo, sizeof(int), hipMemcpyDeviceToHost, st));
         LK_HIP_CHECK(hipStreamSynchronize(st));
         const int n_redo = h_redo[0];
+        rep.v[5] = n_redo;
+        rep.v[6] = n_redo > lk::FUSED_REDO_CAP ? 1 : 0;
         if (n_redo > lk::FUSED_REDO_CAP) {
             for (int64_t ub = 0; ub < n_users; ub += lk::score_batch()) {
                 const int64_t rows = (n_users - ub) < lk::score_batch() ? (n_users - ub)
@@ -2604,6 +2642,7 @@ extern "C" int lk_score_topk(const float *d_users, int32_t ld_users, int64_t n_u
             LK_HIP_CHECK(hipMemcpyAsync(h_redo.data() + 1, redo + 1, sizeof(int) * (size_t)n_redo,
                                         hipMemcpyDeviceToHost, st));
             LK_HIP_CHECK(hipStreamSynchronize(st));
+            rep.rows.assign(h_redo.begin() + 1, h_redo.begin() + 1 + n_redo);
             for (int i = 0; i < n_redo; ++i) {
                 int rc = run_panel((int64_t)h_redo[(size_t)1 + i], 1);
                 if (rc != LK_OK) return rc;

@@ -130,7 +130,7 @@ def _variant(monkeypatch, variant):
 
 
 @pytest.mark.parametrize("variant", [ROUND5, ROUND4, ("cmax", "sort")])
-@pytest.mark.parametrize("k,n", [(64, 100), (25, 10), (128, 128), (10, 10)])
+@pytest.mark.parametrize("k,n", [(64, 100), (25, 10), (128, 128), (10, 10), (256, 100), (200, 50)])
 def test_score_topk_fused_path(gpu, oracle, rng, k, n, monkeypatch, variant):
     """
     The fused scoring + selection path (catalogues >= 16 384 items: stage-1 threshold from an
