@@ -158,6 +158,12 @@ void lk_als_plan_destroy(lk_als_plan *plan);
  * hybrid plans; 256 for strict reference-order plans): the first tasks of the longest-first
  * order, i.e. the rows sorted by descending length, ties in row order. */
 int64_t lk_als_plan_long_rows(const lk_als_plan *plan);
+/* The chunk kernel's work units of those rows: how many the plan has, and the CSR entries per
+ * unit (a multiple of the 256-entry slab block).  Hybrid plans at padded k = 64 choose 1024, 512 or
+ * 256 at creation -- the largest that leaves twice as many units as the device holds chunk waves
+ * -- unless LK_ALS_REF_UNIT says otherwise. */
+int64_t lk_als_plan_units(const lk_als_plan *plan);
+int32_t lk_als_plan_unit(const lk_als_plan *plan);
 /* Hybrid plans: the right-hand sides of those rows as the last half-epoch run with workspace
  * `d_ws` formed them in the reference's order -- [lk_als_plan_long_rows x lk_padded_dim(k)]
  * floats, row t = the t-th longest row (device pointer into d_ws; NULL for other plans).

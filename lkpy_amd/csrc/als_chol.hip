@@ -156,7 +156,7 @@ __device__ __forceinline__ void ring_issue(GatherRing<NT> &R, const int slot_idx
     load_q<NT>(other + (int64_t)col * KP + (lane & 15) * NT, R.q[slot_idx]);
 }
 
-template <int NT, bool MASKED, bool SEQY = false>
+template <int NT, bool MASKED, bool SEQY = false, bool WITH_Y = true>
 __device__ __forceinline__ void ring_consume(Gram<NT> &G, const GatherRing<NT> &R,
                                              const int slot_idx, const int g, const int nb,
                                              const bool expl)
@@ -181,18 +181,20 @@ __device__ __forceinline__ void ring_consume(Gram<NT> &G, const GatherRing<NT> &
         for (int ti = 0; ti <= tj; ++ti)
             G.t[tidx(ti, tj)] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ti], q[tj],
                                                                      G.t[tidx(ti, tj)], 0, 0, 0);
-    const float v1 = expl ? v : v + 1.0f;  // `vals += 1.0` (implicit.rs:116)
-    if constexpr (SEQY) {
-        y_chain_step<NT>(G.yc, q, v1);
-    } else {
+    if constexpr (WITH_Y) {
+        const float v1 = expl ? v : v + 1.0f;  // `vals += 1.0` (implicit.rs:116)
+        if constexpr (SEQY) {
+            y_chain_step<NT>(G.yc, q, v1);
+        } else {
 #pragma unroll
-        for (int t = 0; t < NT; ++t) G.y[t] = fmaf(q[t], v1, G.y[t]);
+            for (int t = 0; t < NT; ++t) G.y[t] = fmaf(q[t], v1, G.y[t]);
+        }
     }
 }
 
 constexpr int GRAM_STAGE_WORDS = 256;  // two batches of 64 (column, value) pairs
 
-template <int NT, bool SEQY = false>
+template <int NT, bool SEQY = false, bool WITH_Y = true>
 __device__ __forceinline__ void gram_accumulate(Gram<NT> &G, const int32_t *__restrict__ cols,
                                                 const float *__restrict__ vals, int64_t beg,
                                                 int64_t end, const float *__restrict__ other,
@@ -232,7 +234,7 @@ __device__ __forceinline__ void gram_accumulate(Gram<NT> &G, const int32_t *__re
         }
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
-            ring_consume<NT, false, SEQY>(G, R, g % RING, g, 64, expl);
+            ring_consume<NT, false, SEQY, WITH_Y>(G, R, g % RING, g, 64, expl);
             if (g == 16 - RING - 2) {
                 // the next batch goes to LDS two groups before its first entries are needed
                 wr_nxt[0] = __builtin_bit_cast(float, nxt_col);
@@ -259,7 +261,7 @@ __device__ __forceinline__ void gram_accumulate(Gram<NT> &G, const int32_t *__re
         const int ngroups = (nb + 3) >> 2;
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
-            if (g < ngroups) ring_consume<NT, true, SEQY>(G, R, g % RING, g, nb, expl);
+            if (g < ngroups) ring_consume<NT, true, SEQY, WITH_Y>(G, R, g % RING, g, nb, expl);
             if (g < 16 - RING) ring_issue<NT>(R, g % RING, g + RING, rd_cur, other);
         }
     }
@@ -280,8 +282,7 @@ __device__ __forceinline__ void gram_accumulate(Gram<NT> &G, const int32_t *__re
 #ifndef LK_ALS_DMA_RING
 #define LK_ALS_DMA_RING 8
 #endif
-constexpr int DMA_RING = LK_ALS_DMA_RING;
-constexpr int GRAM_DMA_WORDS = DMA_RING * 256;  // ring, followed by nothing
+constexpr int DMA_RING = LK_ALS_DMA_RING;  // (the solve kernel's ring: DMA_RING * 256 floats)
 
 template <int N>
 __device__ __forceinline__ void wait_vm()
@@ -335,7 +336,9 @@ __device__ __forceinline__ DmaOperand dma_fetch(const float *ring, const int slo
     return o;
 }
 
-template <bool MASKED, bool SEQY = false>
+// WITH_Y = false (the chunk kernel of plans whose chunked rows all take y from the reference-order
+// chains): no v + 1, no y arithmetic -- the slab's y words are never read
+template <bool MASKED, bool SEQY = false, bool WITH_Y = true>
 __device__ __forceinline__ void dma_apply(Gram<4> &G, const DmaOperand &o, const int g,
                                           const int nb, const bool expl)
 {
@@ -355,45 +358,47 @@ __device__ __forceinline__ void dma_apply(Gram<4> &G, const DmaOperand &o, const
         for (int ti = 0; ti <= tj; ++ti)
             G.t[tidx(ti, tj)] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ti], q[tj],
                                                                      G.t[tidx(ti, tj)], 0, 0, 0);
-    const float v1 = expl ? v : v + 1.0f;
-    if constexpr (SEQY) {
-        y_chain_step<4>(G.yc, q, v1);
-    } else {
+    if constexpr (WITH_Y) {
+        const float v1 = expl ? v : v + 1.0f;
+        if constexpr (SEQY) {
+            y_chain_step<4>(G.yc, q, v1);
+        } else {
 #pragma unroll
-        for (int t = 0; t < 4; ++t) G.y[t] = fmaf(q[t], v1, G.y[t]);
+            for (int t = 0; t < 4; ++t) G.y[t] = fmaf(q[t], v1, G.y[t]);
+        }
     }
 }
 
-template <bool MASKED, bool SEQY = false>
+template <bool MASKED, bool SEQY = false, bool WITH_Y = true>
 __device__ __forceinline__ void dma_consume(Gram<4> &G, const float *ring, const int slot_idx,
                                             const int g, const int nb, const float *stage_slot,
                                             const bool expl)
 {
-    dma_apply<MASKED, SEQY>(G, dma_fetch(ring, slot_idx, g, stage_slot), g, nb, expl);
+    dma_apply<MASKED, SEQY, WITH_Y>(G, dma_fetch(ring, slot_idx, g, stage_slot), g, nb, expl);
 }
 
 template <int NT>
 __host__ __device__ constexpr int slab_floats();
-template <int NT>
+template <int NT, bool WITH_Y = true>
 __device__ __forceinline__ void slab_store(const Gram<NT> &G, float *__restrict__ slab);
-template <int NT>
+template <int NT, bool WITH_Y = true>
 __device__ __forceinline__ void gram_zero(Gram<NT> &G);
 
-// ring: GRAM_DMA_WORDS floats, stage: GRAM_STAGE_WORDS floats, both wave-private LDS
+// ring: RING * 256 floats, stage: GRAM_STAGE_WORDS floats, both wave-private LDS
 // `slab` (optional; reference-order work units, als_plan.h): at every 256-entry boundary that is
 // followed by more entries the accumulators are stored to *slab (the next slab follows it) and
 // start again from zero -- matrixmultiply's KC = 256 blocks, each an fma chain of its own -- while
 // the gather ring keeps running: the wave never drains its memory queue inside a unit.  (The
 // slab stores count in vmcnt like the loads: the first waits after a boundary are a little more
 // conservative than needed, never less.)  The last block of the range is left in G.
-template <bool SEQY = false>
+// RING: groups in flight (ring: RING * 256 floats); the solve kernel's 8, the chunk kernel's own
+template <bool SEQY = false, bool WITH_Y = true, int RING = DMA_RING>
 __device__ __forceinline__ void gram_accumulate_dma(Gram<4> &G, const int32_t *__restrict__ cols,
                                                     const float *__restrict__ vals, int64_t beg,
                                                     int64_t end, const float *__restrict__ other,
                                                     const bool expl, float *ring, float *stage,
                                                     float *__restrict__ slab = nullptr)
 {
-    constexpr int RING = DMA_RING;
     static_assert(RING == 8 || RING == 4, "DMA ring: 4 or 8 groups");
     const int lane = lane_id();
     const int64_t last = end - 1;  // end > beg
@@ -437,7 +442,7 @@ __device__ __forceinline__ void gram_accumulate_dma(Gram<4> &G, const int32_t *_
                 wait_vm<RING - 2>();
                 nxt = dma_fetch(ring, (g + 1) % RING, g + 1, rd_cur);
             }
-            dma_apply<false, SEQY>(G, cur, g, 64, expl);
+            dma_apply<false, SEQY, WITH_Y>(G, cur, g, 64, expl);
             if (g == 16 - RING - 2) {
                 wr_nxt[0] = __builtin_bit_cast(float, nxt_col);
                 wr_nxt[64] = nxt_val;
@@ -450,9 +455,9 @@ __device__ __forceinline__ void gram_accumulate_dma(Gram<4> &G, const int32_t *_
             __builtin_amdgcn_sched_barrier(0);
         }
         if (slab && ((g0 + 16) & 63) == 0) {  // (wave-uniform) a 256-entry block is complete
-            slab_store<4>(G, slab);
+            slab_store<4, WITH_Y>(G, slab);
             slab += slab_floats<4>();
-            gram_zero<4>(G);
+            gram_zero<4, WITH_Y>(G);
         }
         float *tw = wr_cur;
         wr_cur = wr_nxt;
@@ -478,7 +483,7 @@ __device__ __forceinline__ void gram_accumulate_dma(Gram<4> &G, const int32_t *_
             if (gg < total) {
                 const int later = total - 1 - gg;  // groups issued after this one
                 wait_vm_upto(later < RING - 1 ? later : RING - 1);
-                dma_consume<true, SEQY>(G, ring, g % RING, g, nb, rd_cur, expl);
+                dma_consume<true, SEQY, WITH_Y>(G, ring, g % RING, g, nb, rd_cur, expl);
             }
             if (g == 16 - RING - 2 && more) {
                 wr_nxt[0] = __builtin_bit_cast(float, nxt_col);
@@ -492,9 +497,9 @@ __device__ __forceinline__ void gram_accumulate_dma(Gram<4> &G, const int32_t *_
             }
         }
         if (slab && ((g0 + 16) & 63) == 0 && g0 + 16 < total) {  // a block boundary, more follows
-            slab_store<4>(G, slab);
+            slab_store<4, WITH_Y>(G, slab);
             slab += slab_floats<4>();
-            gram_zero<4>(G);
+            gram_zero<4, WITH_Y>(G);
         }
         float *tw = wr_cur;
         wr_cur = wr_nxt;
@@ -512,12 +517,13 @@ __device__ __forceinline__ void gram_accumulate_dma(Gram<4> &G, const int32_t *_
 // shrink); for a 256-entry chunk that is a quarter of the work.  Here the batch loop is unrolled
 // over the four batches, so every guard and every wait count is a compile-time constant.  Same
 // operations in the same order: bit-identical to gram_accumulate_dma on the same range.
+template <bool WITH_Y = true, int RING = DMA_RING>
 __device__ __forceinline__ void gram_accumulate_dma_256(Gram<4> &G, const int32_t *__restrict__ cols,
                                                         const float *__restrict__ vals, int64_t beg,
                                                         const float *__restrict__ other,
                                                         const bool expl, float *ring, float *stage)
 {
-    constexpr int RING = DMA_RING, TOTAL = 64;
+    constexpr int TOTAL = 64;
     const int lane = lane_id();
     const unsigned ring_lds =
         __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t) reinterpret_cast<void *>(ring));
@@ -553,7 +559,7 @@ __device__ __forceinline__ void gram_accumulate_dma_256(Gram<4> &G, const int32_
                 wait_vm_upto(issued_after < later ? issued_after : later);
                 nxt = dma_fetch(ring, (g + 1) % RING, g + 1, rd_cur);
             }
-            dma_apply<false>(G, cur, g, 64, expl);
+            dma_apply<false, false, WITH_Y>(G, cur, g, 64, expl);
             if (g == 16 - RING - 2 && b < 3) {
                 wr_nxt[0] = __builtin_bit_cast(float, nxt_col);
                 wr_nxt[64] = nxt_val;
@@ -580,7 +586,7 @@ __host__ __device__ constexpr int slab_floats()
     return (als_tiles(NT) * 4 + NT) * 64;
 }
 
-template <int NT>
+template <int NT, bool WITH_Y>
 __device__ __forceinline__ void slab_store(const Gram<NT> &G, float *__restrict__ slab)
 {
     const int lane = lane_id();
@@ -589,41 +595,50 @@ __device__ __forceinline__ void slab_store(const Gram<NT> &G, float *__restrict_
 #pragma unroll
     for (int e = 0; e < als_tiles(NT); ++e)
         __builtin_nontemporal_store(G.t[e], reinterpret_cast<f32x4 *>(slab + (e * 64 + lane) * 4));
+    if constexpr (WITH_Y) {
 #pragma unroll
-    for (int t = 0; t < NT; ++t) slab[als_tiles(NT) * 256 + lane * NT + t] = G.y[t];
+        for (int t = 0; t < NT; ++t) slab[als_tiles(NT) * 256 + lane * NT + t] = G.y[t];
+    }
 }
 
-template <int NT>
+// WITH_Y = false: the tiles only (the y words of such a slab may never have been written)
+template <int NT, bool WITH_Y = true>
 __device__ __forceinline__ void slab_add(Gram<NT> &G, const float *__restrict__ slab)
 {
     const int lane = lane_id();
 #pragma unroll
     for (int e = 0; e < als_tiles(NT); ++e)
         G.t[e] += *reinterpret_cast<const f32x4 *>(slab + (e * 64 + lane) * 4);
+    if constexpr (WITH_Y) {
 #pragma unroll
-    for (int t = 0; t < NT; ++t) G.y[t] += slab[als_tiles(NT) * 256 + lane * NT + t];
+        for (int t = 0; t < NT; ++t) G.y[t] += slab[als_tiles(NT) * 256 + lane * NT + t];
+    }
 }
 
-template <int NT>
+template <int NT, bool WITH_Y>
 __device__ __forceinline__ void gram_zero(Gram<NT> &G)
 {
 #pragma unroll
     for (int e = 0; e < als_tiles(NT); ++e) G.t[e] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (WITH_Y) {
 #pragma unroll
-    for (int t = 0; t < NT; ++t) G.y[t] = 0.f;
+        for (int t = 0; t < NT; ++t) G.y[t] = 0.f;
+    }
 }
 
 // ---- slab groups: slab[head] += slab[head + 1] + ... + slab[head + cnt - 1] ------------------
-// (grid: groups x ceil(slab_floats / 1024); float4 per thread; chunk order inside the group)
+// (grid: groups x ceil(sum_floats / 1024); float4 per thread; chunk order inside the group;
+// only the first sum_floats words of a slab are summed -- all of it, or the tiles without y)
 __global__ __launch_bounds__(256) void slab_group_reduce_kernel(float *__restrict__ slabs,
                                                                 int64_t slab_floats,
+                                                                int64_t sum_floats,
                                                                 const int32_t *__restrict__ grp_head,
                                                                 const int32_t *__restrict__ grp_cnt,
                                                                 int parts)
 {
     const int g = blockIdx.x / parts;
     const int64_t e = ((int64_t)(blockIdx.x - g * parts) * 256 + threadIdx.x) * 4;
-    if (e >= slab_floats) return;
+    if (e >= sum_floats) return;
     float *head = slabs + (size_t)grp_head[g] * slab_floats + e;
     const int cnt = grp_cnt[g];
     f32x4 acc = *reinterpret_cast<const f32x4 *>(head);
@@ -644,24 +659,45 @@ __global__ __launch_bounds__(256) void slab_group_reduce_kernel(float *__restric
     *reinterpret_cast<f32x4 *>(head) = acc;
 }
 
-int launch_slab_group_reduce(const lk_als_plan *p, float *slabs, size_t slab_floats, hipStream_t st)
+int launch_slab_group_reduce(const lk_als_plan *p, float *slabs, size_t slab_floats, hipStream_t st,
+                             size_t sum_floats)
 {
     if (p->n_groups <= 0) return LK_OK;
-    const int parts = (int)((slab_floats / 4 + 255) / 256);
+    if (sum_floats == 0) sum_floats = slab_floats;
+    const int parts = (int)((sum_floats / 4 + 255) / 256);
     hipLaunchKernelGGL(slab_group_reduce_kernel, dim3((unsigned)(p->n_groups * parts)), dim3(256),
-                       0, st, slabs, (int64_t)slab_floats, p->d_grp_head, p->d_grp_cnt, parts);
+                       0, st, slabs, (int64_t)slab_floats, (int64_t)sum_floats, p->d_grp_head,
+                       p->d_grp_cnt, parts);
     LK_HIP_CHECK(hipGetLastError());
     return LK_OK;
 }
 
 // ---- chunk kernel: one wave per chunk of a long row ------------------------
+// The chunk kernel's own DMA ring depth (4 or 8 groups): its LDS -- 4 waves x (stage + ring) --
+// decides how many of its workgroups a CU holds.  8 deep: 36 864 B, four per CU; 4 deep: 20 480 B,
+// the five per CU that the registers of the kernel without y allow (36 + 60 accumulation
+// registers).  The 4-deep ring was measured and bought nothing: 8 it is.
+#ifndef LK_ALS_CHUNK_RING
+#define LK_ALS_CHUNK_RING 8
+#endif
+constexpr int CHUNK_RING = LK_ALS_CHUNK_RING;
+
 template <int NT>
 __host__ __device__ constexpr int chunk_lds_floats()
 {
-    return GRAM_STAGE_WORDS + (NT == 4 ? GRAM_DMA_WORDS : 0);
+    return GRAM_STAGE_WORDS + (NT == 4 ? CHUNK_RING * 256 : 0);
 }
 
-template <int NT, bool EXPL>
+// chunk workgroups a CU holds at padded k = 64: LDS (160 KiB per CU), at most the 5 waves per
+// SIMD its registers allow (als_plan.hip sizes the work units of hybrid plans by it)
+int als_chol_chunk_wgs_per_cu()
+{
+    const int by_lds = (int)(160 * 1024 / (4 * chunk_lds_floats<4>() * sizeof(float)));
+    return by_lds < 5 ? by_lds : 5;
+}
+
+// WITH_Y = false: the slabs carry the tiles only (chol_front)
+template <int NT, bool EXPL, bool WITH_Y>
 __device__ __forceinline__ void als_chunk_body(
     const int32_t *__restrict__ indices, const float *__restrict__ values,
     const int64_t *__restrict__ chunk_beg, const int32_t *__restrict__ chunk_len,
@@ -676,29 +712,32 @@ __device__ __forceinline__ void als_chunk_body(
     const int64_t c = blk * 4 + wave;
     if (c >= n_chunks) return;
     Gram<NT> G;
-    gram_zero<NT>(G);
+    gram_zero<NT, WITH_Y>(G);
     const int64_t beg = chunk_beg[c];
     // the unit's first slab (a unit of several 256-entry blocks stores one slab per block)
     float *slab = slabs + (size_t)(chunk_slab ? chunk_slab[c] : c) * slab_floats<NT>();
     if constexpr (DMA) {
         const int len = chunk_len[c];
         if (block_len == 256 && len > 256) {  // (wave-uniform) a reference-order work unit
-            gram_accumulate_dma(G, indices, values, beg, beg + len, other, EXPL,
-                                stage_all[wave] + GRAM_STAGE_WORDS, stage_all[wave], slab);
+            gram_accumulate_dma<false, WITH_Y, CHUNK_RING>(
+                G, indices, values, beg, beg + len, other, EXPL,
+                stage_all[wave] + GRAM_STAGE_WORDS, stage_all[wave], slab);
             slab += (size_t)((len - 1) >> 8) * slab_floats<NT>();  // the last block is still in G
         } else if (len == 256)  // a full reference-order block
-            gram_accumulate_dma_256(G, indices, values, beg, other, EXPL,
-                                    stage_all[wave] + GRAM_STAGE_WORDS, stage_all[wave]);
+            gram_accumulate_dma_256<WITH_Y, CHUNK_RING>(
+                G, indices, values, beg, other, EXPL, stage_all[wave] + GRAM_STAGE_WORDS,
+                stage_all[wave]);
         else
-            gram_accumulate_dma(G, indices, values, beg, beg + len, other, EXPL,
-                                stage_all[wave] + GRAM_STAGE_WORDS, stage_all[wave]);
+            gram_accumulate_dma<false, WITH_Y, CHUNK_RING>(
+                G, indices, values, beg, beg + len, other, EXPL,
+                stage_all[wave] + GRAM_STAGE_WORDS, stage_all[wave]);
     } else
-        gram_accumulate<NT>(G, indices, values, beg, beg + chunk_len[c], other, ld, EXPL,
-                            stage_all[wave]);
-    slab_store<NT>(G, slab);
+        gram_accumulate<NT, false, WITH_Y>(G, indices, values, beg, beg + chunk_len[c], other, ld,
+                                           EXPL, stage_all[wave]);
+    slab_store<NT, WITH_Y>(G, slab);
 }
 
-template <int NT, bool EXPL>
+template <int NT, bool EXPL, bool WITH_Y>
 __global__ __launch_bounds__(256) void als_chunk_kernel(
     const int32_t *__restrict__ indices, const float *__restrict__ values,
     const int64_t *__restrict__ chunk_beg, const int32_t *__restrict__ chunk_len,
@@ -706,8 +745,8 @@ __global__ __launch_bounds__(256) void als_chunk_kernel(
     const int32_t *__restrict__ chunk_slab, int block_len)
 {
     __shared__ __attribute__((aligned(16))) float lds_flat[4 * chunk_lds_floats<NT>()];
-    als_chunk_body<NT, EXPL>(indices, values, chunk_beg, chunk_len, n_chunks, other, ld, slabs,
-                             (int64_t)blockIdx.x, lds_flat, chunk_slab, block_len);
+    als_chunk_body<NT, EXPL, WITH_Y>(indices, values, chunk_beg, chunk_len, n_chunks, other, ld,
+                                     slabs, (int64_t)blockIdx.x, lds_flat, chunk_slab, block_len);
 }
 
 // ---- solve: the packed L image ---------------------------------------------------------------
@@ -945,7 +984,8 @@ __device__ __forceinline__ void als_solve_body(
         // many chunks: the groups were pre-summed into their heads (slab_group_reduce_kernel)
         const int step = refo ? ns : (ns > LK_ALS_SLAB_GROUP ? LK_ALS_SLAB_GROUP : 1);
         for (int s = 0; s < ns; s += step)
-            slab_add<NT>(G, slabs + (size_t)(first_slab + s) * slab_floats<NT>());
+            // (YREF: y comes from y_ref below; the slab's y words may never have been written)
+            slab_add<NT, !YREF>(G, slabs + (size_t)(first_slab + s) * slab_floats<NT>());
     } else {
         // (the solver's LDS is idle while the normal matrix is built: it stages the CSR
         // batches and, for k = 64, holds the ring of prefetched factor rows)
@@ -1407,12 +1447,21 @@ static int chol_front(CholHalf &h, CholKind<NT, IS64, EXPL>)
         if (rc != LK_OK) return rc;
         h.forked = h.sr != st;
     }
+    // every row that owns slabs (the first n_long tasks) takes its y from the chains: the chunk
+    // kernel forms no right-hand side, the slabs' y words stay unwritten and nobody reads them
+    // (the YREF solve skips them, the slab sums below stop in front of them)
+    const bool chunk_y = !(h.yref != nullptr && h.n_y >= p->n_long);
     if (p->n_chunks > 0) {
-        hipLaunchKernelGGL((als_chunk_kernel<NT, EXPL>),
-                           dim3((unsigned)((p->n_chunks + 3) / 4)), dim3(256), 0, st,
-                           h.indices, h.values, p->d_chunk_beg, p->d_chunk_len, p->n_chunks,
-                           h.other, h.ld_other, slabs, p->d_chunk_slab,
-                           p->unit > p->chunk ? (int)p->chunk : 0);
+#define LK_CHUNK_LAUNCH(WITHY)                                                                  \
+    hipLaunchKernelGGL((als_chunk_kernel<NT, EXPL, WITHY>),                                    \
+                       dim3((unsigned)((p->n_chunks + 3) / 4)), dim3(256), 0, st, h.indices,   \
+                       h.values, p->d_chunk_beg, p->d_chunk_len, p->n_chunks, h.other,         \
+                       h.ld_other, slabs, p->d_chunk_slab, p->unit > p->chunk ? (int)p->chunk : 0)
+        if (chunk_y)
+            LK_CHUNK_LAUNCH(true);
+        else
+            LK_CHUNK_LAUNCH(false);
+#undef LK_CHUNK_LAUNCH
     }
     if (h.n_y > 0) {
         int rc = launch_rhs_reference(p, h.indptr, IS64 ? 1 : 0, h.indices, h.values, p->d_order,
@@ -1428,7 +1477,8 @@ static int chol_front(CholHalf &h, CholKind<NT, IS64, EXPL>)
             if (rc != LK_OK) return rc;
             sg = h.sr;
         }
-        int rc = launch_slab_group_reduce(p, slabs, slab_floats<NT>(), sg);
+        int rc = launch_slab_group_reduce(p, slabs, slab_floats<NT>(), sg,
+                                          chunk_y ? 0 : (size_t)als_tiles(NT) * 256);
         if (rc != LK_OK) return rc;
     }
     if (h.tm) LK_HIP_CHECK(hipEventRecord(p->ev[p->timing_n][1], st));

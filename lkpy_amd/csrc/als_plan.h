@@ -87,10 +87,12 @@ struct lk_als_plan {
     size_t off_yref = 0;                 // hybrid: [n_long x KP] floats in the workspace
     int32_t chunk = LK_ALS_CHUNK;        // CSR entries per chunk (= per slab) of a long row
     // entries per WORK UNIT of the chunk kernel (a multiple of `chunk`): hybrid plans at padded
-    // k = 64 (als_chunk_kernel) and k = 256 (the LDS-staged als_blk_chunk_dma_kernel) keep the
-    // tuned kernels' 1024-entry units -- one wave / workgroup runs its gather ring across the four
-    // 256-entry blocks of a unit and stores a slab at every block boundary (d_chunk_slab = the
-    // unit's first slab); everywhere else a unit is one chunk
+    // k = 64 (als_chunk_kernel) and k = 256 (the LDS-staged als_blk_chunk_dma_kernel) run units of
+    // several blocks -- one wave / workgroup runs its gather ring across the 256-entry blocks of a
+    // unit and stores a slab at every block boundary (d_chunk_slab = the unit's first slab).
+    // k = 256: 1024 entries.  k = 64: 1024, 512 or 256, the largest for which the plan still has
+    // twice as many units as the device holds chunk waves (lk_als_plan_create_ex; LK_ALS_REF_UNIT
+    // overrides).  Everywhere else a unit is one chunk
     int32_t unit = LK_ALS_CHUNK;
     int64_t n_slabs = 0;                 // slabs of all long rows (n_chunks counts the UNITS)
     int32_t *d_chunk_slab = nullptr;     // [n_chunks] first slab of the unit
@@ -200,8 +202,12 @@ int plan_fork_rhs(const lk_als_plan *p, hipStream_t st, hipStream_t *side);
 int plan_join_rhs(const lk_als_plan *p, hipStream_t st);
 // the rhs side stream waits for what `st` holds now (a second fork point inside the half-epoch)
 int plan_rhs_wait_main(const lk_als_plan *p, hipStream_t st);
-// slab[head] += slab[head + 1] + ... (chunk order) for every group of the plan (als_chol.hip)
-int launch_slab_group_reduce(const lk_als_plan *p, float *slabs, size_t slab_floats, hipStream_t st);
+// slab[head] += slab[head + 1] + ... (chunk order) for every group of the plan (als_chol.hip);
+// sum_floats (0 = slab_floats): the leading words of each slab that are summed
+int launch_slab_group_reduce(const lk_als_plan *p, float *slabs, size_t slab_floats, hipStream_t st,
+                             size_t sum_floats = 0);
+// workgroups of als_chunk_kernel (padded k = 64) that one CU holds (als_chol.hip)
+int als_chol_chunk_wgs_per_cu();
 // deterministic two-stage sum of the per-row squared deltas -> sqrt (als_chol.hip)
 int launch_delta_reduce(const float *row_delta, int64_t n_rows, float *partial, float *out_frob,
                         hipStream_t st);

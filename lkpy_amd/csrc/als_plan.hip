@@ -131,6 +131,23 @@ static bool switch_on(const char *name)
     return !(e && e[0] == '0');
 }
 
+// compute units of a device, 0 if it cannot be asked (asked once per device: fold-in plans are
+// built per call)
+static int device_cu_count(int dev)
+{
+    static std::mutex mu;
+    static int known[64] = {};
+    std::lock_guard<std::mutex> lock(mu);
+    const bool slot = dev >= 0 && dev < 64;
+    if (slot && known[dev] > 0) return known[dev];
+    int n = 0;
+    if (dev < 0 ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 0)
+        n = 0;
+    if (slot) known[dev] = n;
+    return n;
+}
+
 extern "C" int lk_als_plan_create_ex(lk_als_plan **out, const void *h_indptr, int indptr_is_64,
                                      int64_t n_rows, int32_t k, int32_t solver, int32_t flags);
 
@@ -296,8 +313,9 @@ extern "C" int lk_als_plan_create_ex(lk_als_plan **out, const void *h_indptr, in
     std::vector<int32_t> chunk_row, chunk_slab;
     std::vector<int64_t> chunk_beg;
     std::vector<int32_t> chunk_len;
-    // work units (als_plan.h): hybrid plans at padded k = 64 keep 1024-entry units, one slab per
-    // 256-entry block (LK_ALS_REF_UNIT: entries per unit, a multiple of 256; 256 = a unit per block)
+    // work units (als_plan.h): hybrid plans at padded k = 64 run units of 1024, 512 or 256 entries,
+    // one slab per 256-entry block (LK_ALS_REF_UNIT: entries per unit, a multiple of 256; 256 = a
+    // unit per block)
     p->unit = p->chunk;
     // (padded k = 256: the LDS-staged chunk kernel of als_blk.hip takes units as well; the
     // register-ring kernel -- no chunk_dma -- has no block boundaries: a unit is a chunk)
@@ -305,6 +323,28 @@ extern "C" int lk_als_plan_create_ex(lk_als_plan **out, const void *h_indptr, in
     if (p->hybrid && (KP == 64 || p->chunk_dma)) {
         const char *e = getenv("LK_ALS_REF_UNIT");
         int u = e ? atoi(e) : LK_ALS_CHUNK;
+        if (!e && KP == 64) {
+            // als_chunk_kernel runs one wave per unit: the largest unit of 1024 / 512 / 256 entries
+            // that still gives every chunk wave the device holds two units (a plan with fewer
+            // long-row entries than that fills the machine only with a unit per block: ML-25M's
+            // user side, 5 310 blocks in 1 507 units of 1024, ran one or two waves per SIMD)
+            const int cus = device_cu_count(p->device);
+            if (cus <= 0) {
+                delete p;
+                lk::set_error("lk_als_plan_create: cannot read the device's compute-unit count");
+                return LK_E_HIP;
+            }
+            const int64_t want = 2 * (int64_t)cus * lk::als_chol_chunk_wgs_per_cu() * 4;
+            int64_t units_1024 = 0, units_512 = 0;
+            for (int64_t r = 0; r < n_rows; ++r) {
+                const int64_t n = len(r);
+                if (n > LONG_ROW) {
+                    units_1024 += (n + 1023) / 1024;
+                    units_512 += (n + 511) / 512;
+                }
+            }
+            u = units_1024 >= want ? 1024 : (units_512 >= want ? 512 : 256);
+        }
         if (u < p->chunk) u = p->chunk;
         p->unit = u / p->chunk * p->chunk;
     }
@@ -522,6 +562,8 @@ extern "C" int64_t lk_als_plan_short_rows(const lk_als_plan *p)
 }
 
 extern "C" int64_t lk_als_plan_long_rows(const lk_als_plan *p) { return p ? p->n_long : 0; }
+extern "C" int64_t lk_als_plan_units(const lk_als_plan *p) { return p ? p->n_chunks : 0; }
+extern "C" int32_t lk_als_plan_unit(const lk_als_plan *p) { return p ? p->unit : 0; }
 
 extern "C" const float *lk_als_plan_yref(const lk_als_plan *p, const void *d_ws)
 {
