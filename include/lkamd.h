@@ -833,6 +833,23 @@ int lk_take_scores(const float *d_scores, int64_t n_rows, int64_t row_len, const
                    int64_t n, float *d_out, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Top-N lists from one shared order (`PopScorer.recommend_batch`; csrc/popular.hip): every
+ * row's list is the same sorted item order with the row's own history skipped.
+ * lk_shared_order_topn: d_order int32 [n_order] (item numbers, best first) and d_order_scores f32
+ *   [n_order] (their scores, copied bit for bit).  List b = the first n entries of the order that
+ *   do not occur in the history of row b, in order, written to d_out_idx / d_out_scores
+ *   [n_rows x width], width = n (n < 0: n_order); positions past the end are -1 / NaN.  The
+ *   history is a CSR of n_hist_rows rows (offsets int32 or int64, see hist_ptr_is_64) whose rows
+ *   are in ascending item number; repeated entries are fine.  d_rows int32 [n_rows]: list b reads
+ *   history row d_rows[b], -1 or out of range = no history (the plain first n); NULL: list b
+ *   reads row b.  d_hist_ptr NULL: no list has a history.  One wave per list.
+ * ---------------------------------------------------------------------- */
+int lk_shared_order_topn(const int32_t *d_order, const float *d_order_scores, int64_t n_order,
+                         const void *d_hist_ptr, int hist_ptr_is_64, const int32_t *d_hist_idx,
+                         int64_t n_hist_rows, const int32_t *d_rows, int64_t n_rows, int64_t n,
+                         int32_t *d_out_idx, float *d_out_scores, void *stream);
+
+/* ------------------------------------------------------------------------
  * Association rules (`AssociationScorer`, src/lenskit/knn/association.py:59-163; csrc/assoc.hip).
  * The co-occurrence counts are the similarity build on unit values (lk_iknn_build_*, threshold
  * 0.5: `interact.co_occurrences("item")`, association.py:103).

@@ -1600,6 +1600,46 @@ def take_scores(scores: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def shared_order_topn(order: torch.Tensor, order_scores: torch.Tensor, n: int, rows_out: int, *,
+                      hist: DeviceCSR | None = None, rows: torch.Tensor | None = None):
+    """
+    ``rows_out`` top-N lists from one shared order (lk_shared_order_topn): list b is the first
+    ``n`` entries of ``order`` (device int32 [L], with ``order_scores`` f32 [L]) that are not in
+    row ``rows[b]`` of ``hist`` (device int32 [rows_out], -1 = no history; None: row b) -- a CSR
+    of item-sorted rows, either offset width; ``hist=None``: nothing is skipped.  Returns device
+    (item numbers int32 [rows_out x width], scores f32 [rows_out x width]) with -1 / NaN padding,
+    width = ``n`` (``n < 0``: L).
+    """
+    lib = _native.require_gpu()
+    assert order.dtype == torch.int32 and order.is_contiguous() and order.dim() == 1
+    assert order_scores.dtype == torch.float32 and order_scores.is_contiguous()
+    assert order_scores.shape == order.shape
+    L, n, B = int(order.shape[0]), int(n), int(rows_out)
+    width = L if n < 0 else n
+    dev = order.device
+    idx = torch.empty((B, width), dtype=torch.int32, device=dev)
+    sc = torch.empty((B, width), dtype=torch.float32, device=dev)
+    if B == 0 or width == 0:
+        return idx, sc
+    ptr = ind = None
+    n_hist = 0
+    if hist is not None and hist.indices.numel() == 0:
+        hist = rows = None  # (a CSR without entries: nothing to skip, and no address to pass)
+    if hist is not None:
+        ptr, ind, n_hist = hist.indptr, hist.indices, int(hist.shape[0])
+        assert ptr.dtype in (torch.int32, torch.int64) and ptr.is_contiguous()
+        assert ptr.shape == (n_hist + 1,) and ind.dtype == torch.int32 and ind.is_contiguous()
+    if rows is not None:
+        assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.shape == (B,)
+    else:
+        assert hist is None or n_hist >= B
+    check(lib.lk_shared_order_topn(_ptr(order), _ptr(order_scores), L, _ptr(ptr),
+                                   1 if (ptr is not None and ptr.dtype == torch.int64) else 0,
+                                   _ptr(ind), n_hist, _ptr(rows), B, n, _ptr(idx), _ptr(sc),
+                                   _stream()), "lk_shared_order_topn")
+    return idx, sc
+
+
 def score_dense(users: torch.Tensor, items: torch.Tensor, k: int) -> torch.Tensor:
     "All (user, item) scores, [B x I] f32 (lk_score_dense)."
     lib = _native.require_gpu()

@@ -242,6 +242,9 @@ def _declare(lib):
             c_int, [vp, vp, c_int64, vp, vp, vp, c_int64, vp, c_int64, c_int, vp]
         ),
         "lk_take_scores": (c_int, [vp, c_int64, c_int64, vp, c_int64, vp, vp]),
+        "lk_shared_order_topn": (
+            c_int, [vp, vp, c_int64, vp, c_int, vp, c_int64, vp, c_int64, c_int64, vp, vp, vp]
+        ),
         "lk_assoc_window": (c_int32, []),
         "lk_assoc_scale": (
             c_int, [vp, vp, vp, vp, c_int64, c_int64, c_int, ctypes.c_double, vp]

@@ -7,16 +7,28 @@ two target TOMLs need it (host NumPy; not on the accelerated path except ``TopNR
 ``TopNRanker``                      src/lenskit/basic/topn.py:32-69 (-> ItemList.top_n ->
                                     the GPU top-N kernel)
 ``BiasScorer`` / ``FallbackScorer`` src/lenskit/basic/bias.py, composite.py (std:topn-predict)
+``PopScorer`` / ``TimeBoundedPopScore``  src/lenskit/basic/popularity.py (host training; the batch
+                                    path is one walk over a shared order, csrc/popular.hip)
+``RandomSelector``                  src/lenskit/basic/random.py (the stochastic ranker's draws
+                                    over equal weights)
 """
 
 from __future__ import annotations
 
+import logging
+from datetime import datetime, timezone
+from typing import Any, Literal
+
 import numpy as np
+import pandas as pd
 from pydantic import BaseModel
 
+from ._streams import RowStreams
 from .data import Dataset, ItemList, RecQuery, Vocabulary
 from .pipeline import Component
-from .training import TrainingOptions
+from .training import Trainable, TrainingOptions
+
+_log = logging.getLogger(__name__)
 
 
 class LookupConfig(BaseModel):
@@ -375,3 +387,256 @@ class FallbackScorer(Component):
                 for i in np.flatnonzero(missing):
                     ps[i] = lookup.get(primary.ids()[i], np.nan)
         return ItemList(primary, scores=ps, is_fallback=missing)
+
+
+class PopConfig(BaseModel):
+    "src/lenskit/basic/popularity.py:24-33"
+
+    score: Literal["quantile", "rank", "count"] = "quantile"
+
+
+class PopScorer(Component, Trainable):
+    """
+    Score items by their popularity (``PopScorer``, src/lenskit/basic/popularity.py:36-91):
+    ``items`` and ``item_scores`` (float32, one per item number), trained on the host from
+    ``data.item_stats()["count"]`` with the reference's own pandas calls -- ``quantile`` depends on
+    the tie order of pandas' unstable sort, which only the same call reproduces.
+
+    Every user's top-N over these scores is one globally sorted list with the user's own items
+    skipped: :meth:`recommend_batch` walks that shared order (``lk_shared_order_topn``) instead of
+    scoring and selecting per user.  The scorer never looks at the user, so an unknown user gets
+    the plain top ``n`` -- in ``pipe.run`` and here.
+    """
+
+    config: PopConfig
+    items: Vocabulary
+    item_scores: np.ndarray
+
+    accepts_history_batch = True  # recommend_batch takes a HistoryBatch
+    returns_device_lists = True  # ... and has ``device_output``: the lists left on the device
+
+    def is_trained(self):
+        return hasattr(self, "item_scores")
+
+    def train(self, data: Dataset, options: TrainingOptions = TrainingOptions()):
+        self.items = data.items
+        self.item_scores = np.require(self._train_internal(data.item_stats()["count"]).values,
+                                      np.float32)
+
+    def _train_internal(self, scores: pd.Series) -> pd.Series:
+        "popularity.py:68-82, call for call"
+        if self.config.score == "rank":
+            return scores.rank()
+        elif self.config.score == "quantile":
+            cmass = scores.sort_values()
+            cmass = cmass.cumsum()
+            cdens = cmass / scores.sum()
+            return cdens.reindex(scores.index)
+        elif self.config.score == "count":
+            return scores
+        raise ValueError("invalid scoring method " + repr(self.config.score))
+
+    def __call__(self, items: ItemList) -> ItemList:
+        inums = items.numbers(vocabulary=self.items, missing="negative")
+        mask = inums >= 0
+        scores = np.full(len(items), np.nan, np.float32)
+        scores[mask] = self.item_scores[inums[mask]]
+        return ItemList(items, scores=scores)
+
+    # -- whole batches of queries ---------------------------------------------------------------
+    def _device_order(self):
+        """
+        The model in HBM, built once per training: ``scores`` f32 [items], ``order`` int32 [L] --
+        the items with a non-NaN score by score descending, then item number ascending -- and
+        ``order_scores`` f32 [L].  The order is ``lk_argtopn``'s over the whole score row, the
+        call ``ItemList.top_n`` makes per query: the tie rule is the per-query one by construction.
+        """
+        def build():
+            import torch
+
+            from . import _device as D
+
+            d = D.device()
+            sc = torch.from_numpy(np.ascontiguousarray(self.item_scores, dtype=np.float32)).to(d)
+            if sc.numel() == 0:
+                order, osc = torch.zeros(0, dtype=torch.int32, device=d), sc
+            else:
+                full = D.argtopn(sc[None], -1)
+                vals = D.take_scores(sc[None], full)
+                keep = full[0] >= 0
+                order, osc = full[0][keep].contiguous(), vals[0][keep].contiguous()
+            return {"device": d, "scores": sc, "order": order, "order_scores": osc}
+
+        return self._device_cache("order", build, self.item_scores)
+
+    def _history_rows(self, queries):
+        "(queries resolved, the CSR to skip, device row numbers into it | None: row b)"
+        import torch
+
+        from . import _device as D
+        from ._queries import pack_histories, resolve_queries
+
+        queries = resolve_queries(queries, self.items)
+        dev = self._device_order()["device"]
+        if isinstance(queries, HistoryBatch):
+            # the training matrix itself, by user number: no row gather
+            return queries, queries.lookup._device_matrix()["csr"], \
+                torch.from_numpy(queries.user_nums).to(dev)
+        ptr, idx, _ = pack_histories(queries, self.items, unknown="drop", sort=True)
+        return queries, D.DeviceCSR.from_arrays(ptr, idx, None, (len(queries), len(self.items)),
+                                                dev), None
+
+    def recommend_batch(self, queries, n: int | None, *, exclude_history: bool = True,
+                        device_output: bool = False):
+        """
+        The top ``n`` (None or negative: all) of many queries at once: (item numbers [B x n] with
+        -1 padding, scores [B x n] with NaN padding), each row the shared order with the query's
+        history skipped.  ``queries``: a list of queries or a :class:`HistoryBatch`, whose rows
+        are read from the HBM-resident training matrix by user number.
+        """
+        from . import _device as D
+
+        st = self._device_order()
+        n = -1 if n is None else int(n)
+        if exclude_history:
+            queries, hist, rows = self._history_rows(queries)
+        else:
+            hist = rows = None
+        idx, sc = D.shared_order_topn(st["order"], st["order_scores"], n, len(queries),
+                                      hist=hist, rows=rows)
+        if device_output:
+            return idx, sc
+        return D.lists_to_host(idx, sc)
+
+    def dense_scores_batch(self, queries):
+        """
+        (panel f32 [B x items], valid -- all True --, history CSR): ``item_scores`` repeated per
+        row, contiguous as the stochastic kernels take it; the history is for the caller to
+        exclude.
+        """
+        from . import _device as D
+        from ._queries import pack_histories, resolve_queries
+
+        st = self._device_order()
+        queries = resolve_queries(queries, self.items)
+        B = len(queries)
+        if isinstance(queries, HistoryBatch):
+            hist = queries.csr(with_values=False)
+        else:
+            ptr, idx, _ = pack_histories(queries, self.items, unknown="drop", sort=True)
+            hist = D.DeviceCSR.from_arrays(ptr, idx, None, (B, len(self.items)), st["device"])
+        panel = st["scores"][None].expand(B, -1).contiguous()
+        return panel, np.ones(B, dtype=bool), hist
+
+
+class TimeBoundedPopConfig(PopConfig):
+    # required by the reference's config (popularity.py:94-98); here every component can be
+    # built from its defaults, so a missing cutoff is refused by ``train`` instead
+    cutoff: datetime | None = None
+
+
+class TimeBoundedPopScore(PopScorer):
+    """
+    Popularity among the interactions whose ``timestamp`` is later than ``config.cutoff``
+    (``TimeBoundedPopScore``, popularity.py:101-134); without a ``timestamp`` attribute it trains
+    as :class:`PopScorer` and logs a warning.  ``timestamp`` may be ``datetime64`` or numeric
+    seconds since the epoch; a cutoff without a time zone is taken as UTC.
+
+    The reference skips a retrain on ``hasattr(self, "item_scores_")``, an attribute it never
+    sets; here ``train`` follows the ordinary rule of a ``Trainable``: it returns at once when
+    ``is_trained()`` and ``options.retrain`` is off.  Where no interaction passes the cutoff,
+    ``quantile`` is 0 / 0: every score is NaN and every list is empty, as in the reference.
+    """
+
+    config: TimeBoundedPopConfig
+
+    def train(self, data: Dataset, options: TrainingOptions = TrainingOptions()):
+        if self.is_trained() and not options.retrain:
+            return
+        if self.config.cutoff is None:
+            raise ValueError("TimeBoundedPopScore needs a cutoff")
+        stamps = data._attrs.get("timestamp")
+        if stamps is None:
+            _log.warning("no timestamps in interaction log; falling back to PopScorer")
+            super().train(data, options)
+            return
+        cutoff = self.config.cutoff
+        if cutoff.tzinfo is not None:
+            cutoff = cutoff.astimezone(timezone.utc).replace(tzinfo=None)
+        stamps = np.asarray(stamps)
+        if stamps.dtype.kind == "M":
+            late = stamps > np.datetime64(cutoff)
+        else:
+            late = stamps > cutoff.replace(tzinfo=timezone.utc).timestamp()
+        counts = np.bincount(data._cols[late], minlength=data.item_count)
+        series = pd.Series(counts, index=pd.Index(data.items.ids(), name="item_id"))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            scores = self._train_internal(series)
+        self.items = data.items
+        self.item_scores = np.require(scores.values, np.float32)
+
+
+class RandomConfig(BaseModel, arbitrary_types_allowed=True):
+    "src/lenskit/basic/random.py:15-24"
+
+    n: int | None = None  # how many items to select; -1 or None: all of them, permuted
+    rng: Any = None  # DerivableSeed: a seed, "user", or (seed, "user")
+
+
+class RandomSelector(RowStreams, Component):
+    """
+    Pick items uniformly at random without replacement (``RandomSelector``,
+    src/lenskit/basic/random.py:27-78).  The reference draws ``rng.choice`` from a NumPy
+    generator; a device cannot reproduce that stream, so the draws are this package's (DESIGN.md
+    section 4.18): a uniform ordered sample without replacement is the Plackett-Luce ranking over
+    equal weights, i.e. the stochastic ranker's keys over a constant score with no transform.
+    ``seed``, ``by_user``, ``streams()`` and the call counter are ``StochasticTopNRanker``'s; an
+    item's draw is addressed by its item number, so one list and the same list inside a batch
+    agree.  The result keeps the input's fields and carries no score of its own.
+    """
+
+    config: RandomConfig
+
+    def __init__(self, config=None, **kwargs):
+        if isinstance(config, dict) and isinstance(config.get("rng"), list):
+            config = {**config, "rng": tuple(config["rng"])}  # (a TOML / JSON [seed, "user"])
+        super().__init__(config, **kwargs)
+        self._init_streams(self.config.rng)
+
+    def _length(self, n: int | None) -> int:
+        if n is None:
+            n = self.config.n or -1  # (random.py:63-64)
+        return int(n)
+
+    def rank_panel(self, panel, streams, n: int | None, *, excl=None, samples: int = 1,
+                   first_sample: int = 0, device_output: bool = False):
+        "``stochastic.rank_panel`` with no transform over a panel of one constant"
+        from .stochastic import rank_panel
+
+        return rank_panel(panel, streams, self._length(n), transform=None, scale=1.0,
+                          seed=self.seed, excl=excl, samples=samples, first_sample=first_sample,
+                          device_output=device_output)
+
+    def __call__(self, items: ItemList, query=None, n: int | None = None) -> ItemList:
+        import torch
+
+        from . import _device as D
+
+        n = self._length(n)
+        query = RecQuery.create(query)
+        stream = self.streams(None if query.user_id is None else [query.user_id], 1)
+        n = len(items) if n < 0 else min(n, len(items))  # (random.py:69-72)
+        if n == 0:
+            return items[np.zeros(0, dtype=np.int32)]
+        # a one-row panel over the item numbers: the kernels, and the draws, of a batch row
+        if items.vocabulary is not None:
+            nums, width = items.numbers(), len(items.vocabulary)
+        else:
+            nums, width = np.arange(len(items)), len(items)
+        row = np.full((1, width), np.nan, dtype=np.float32)
+        row[0, nums] = 1.0
+        position = np.full(width, -1, dtype=np.int64)
+        position[nums] = np.arange(len(items))
+        idx, _keys = self.rank_panel(torch.from_numpy(row).to(D.device()), stream, n)
+        picked = idx[0, 0]
+        return items[position[picked[picked >= 0]]]

@@ -21,7 +21,9 @@ def recommend(pipe: Pipeline, users, n: int, *, batch_size: int = 16384,
     src/lenskit/batch/_runner.py:157-191): ``out.lookup(user)`` / ``out.lookup(user_id=user)``,
     iteration over ``(key, list)``, ``out.to_df()``.  A pipeline whose ranker is a
     ``StochasticTopNRanker`` gets sampled rankings (``_sample_panels``), any other the scorer's
-    own top-N.
+    own top-N.  A pipeline whose ranker is a ``RandomSelector`` over the candidates, with an empty
+    scorer slot (``random_pipeline``), is drawn by panels of one constant (``_recommend_random``);
+    its lists carry no score.
 
     A pipeline with a ``reranker`` node (``Pipeline.add_reranker``) has the [B x n] arrays of
     every branch passed through the component's ``rerank_batch`` before the lists are built -- on
@@ -35,6 +37,12 @@ def recommend(pipe: Pipeline, users, n: int, *, batch_size: int = 16384,
     scorer = pipe.node("scorer").component
     lookup = pipe.node("history-lookup").component
     reranker = _reranker(pipe)
+    if scorer is None and _random_selector(pipe) is not None:
+        if reranker is not None or rerank_depth is not None or not _random_by_panels(pipe):
+            if rerank_depth is not None:
+                raise ValueError("rerank_depth does not apply to a random selection")
+            return _recommend_loop(pipe, users, n)
+        return _recommend_random(pipe, users, n, batch_size)
     batched = _reranks_batches(reranker, scorer)
     if rerank_depth is not None:
         if not batched:
@@ -137,6 +145,65 @@ def _stochastic_ranker(pipe: Pipeline):
     node = pipe.nodes.get(pipe.aliases.get("ranker", "ranker"))
     comp = None if node is None else node.component
     return comp if isinstance(comp, StochasticTopNRanker) else None
+
+
+def _random_selector(pipe: Pipeline):
+    "the pipeline's ranker when it is a ``RandomSelector``, else None"
+    from .basic import RandomSelector
+
+    node = pipe.nodes.get(pipe.aliases.get("ranker", "ranker"))
+    comp = None if node is None else node.component
+    return comp if isinstance(comp, RandomSelector) else None
+
+
+def _random_by_panels(pipe: Pipeline) -> bool:
+    """the selector picks from the standard candidates -- every training item but the query's
+    history -- and the lookup hands out ``HistoryBatch`` es over those items"""
+    from .basic import TrainingItemsCandidateSelector
+
+    ranker = pipe.nodes[pipe.aliases.get("ranker", "ranker")]
+    lookup = pipe.node("history-lookup").component
+    cand = pipe.nodes.get("candidate-selector")
+    cand = None if cand is None else cand.component
+    if ranker.wiring.get("items") != "candidates" or not hasattr(lookup, "batch") or \
+            getattr(lookup, "interactions", None) is None or \
+            not isinstance(cand, TrainingItemsCandidateSelector) or not cand.is_trained() or \
+            cand.config.exclude not in ("query", "all"):
+        return False
+    items = lookup.interactions._ds.items
+    return cand.items_ is items or cand.items_ == items
+
+
+def _recommend_random(pipe: Pipeline, users, n, batch_size: int) -> ItemListCollection:
+    """
+    ``recommend`` for a ``random_pipeline``: per chunk of ``STOCHASTIC_PANEL_BYTES / (8 n_items)``
+    rows a panel of one constant, the users' training rows as the exclusion (an unknown user has
+    none: every item is a candidate) and the selector's ``rank_panel`` -- the stochastic ranker's
+    keys with no transform.  The lists hold item numbers only.
+    """
+    import torch
+
+    from . import _device as D
+
+    selector = _random_selector(pipe)
+    lookup = pipe.node("history-lookup").component
+    ids = users if isinstance(users, np.ndarray) else np.asarray(list(users))
+    if len(ids) == 0:
+        return ItemListCollection(("user_id",))
+    hb = lookup.batch(ids)
+    n_items = len(hb.items)
+    n = selector._length(n)
+    width = n_items if n < 0 else n
+    rows = max(1, min(batch_size, len(ids), STOCHASTIC_PANEL_BYTES // (8 * max(1, n_items))))
+    streams = selector.streams(hb.user_ids)  # (the ids as the lookup types them, like a query's)
+    idx = np.full((len(ids), width), -1, np.int32)
+    panel = torch.ones((rows, n_items), dtype=torch.float32, device=D.device())
+    for s in range(0, len(ids), rows):
+        sub = hb.subset(slice(s, s + rows))
+        i, _keys = selector.rank_panel(panel[:len(sub)], streams[s:s + rows], n,
+                                       excl=sub.csr(with_values=False))
+        idx[s:s + rows, :i.shape[2]] = i[:, 0]
+    return ItemListCollection.from_arrays(ids, idx, None, hb.items, key=("user_id",))
 
 
 def _has_panels(scorer, lookup) -> bool:

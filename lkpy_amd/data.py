@@ -264,13 +264,14 @@ class ItemListCollection:
         return self._key_class
 
     @classmethod
-    def from_arrays(cls, keys, item_nums: np.ndarray, scores: np.ndarray, vocabulary: Vocabulary,
-                    key=("user_id",)) -> "ItemListCollection":
+    def from_arrays(cls, keys, item_nums: np.ndarray, scores: np.ndarray | None,
+                    vocabulary: Vocabulary, key=("user_id",)) -> "ItemListCollection":
         """
         A collection over the [B x n] result arrays of a batched recommend call (item numbers with
-        -1 padding, scores): the ``ItemList`` of a key is only built when somebody asks for it
-        (``lookup`` / iteration / ``[i]``), so handing back ten thousand lists costs nothing per
-        list.  ``to_df`` and ``total_items`` work on the arrays directly.
+        -1 padding, scores; ``scores=None``: lists without a score, a random selection's): the
+        ``ItemList`` of a key is only built when somebody asks for it (``lookup`` / iteration /
+        ``[i]``), so handing back ten thousand lists costs nothing per list.  ``to_df`` and
+        ``total_items`` work on the arrays directly.
         """
         ilc = cls(key)
         ilc._lists = _LazyLists(ilc._key_class, keys, item_nums, scores, vocabulary)
@@ -405,8 +406,9 @@ class _LazyLists:
         if hit is None:
             row = self.nums[pos]
             keep = row >= 0
+            sc = None if self.scores is None else self.scores[pos][keep]
             hit = (self.key(pos), ItemList(item_nums=row[keep], vocabulary=self.vocab,
-                                           scores=self.scores[pos][keep], ordered=True))
+                                           scores=sc, ordered=True))
             self._made[pos] = hit
         return hit
 
@@ -438,7 +440,8 @@ class _LazyLists:
                 np.asarray([self.key(p)[j] for p in range(len(self.raw_keys))])
             cols[f] = np.repeat(col, counts)
         cols["item_id"] = self.vocab.ids(self.nums[keep])
-        cols["score"] = self.scores[keep]
+        if self.scores is not None:
+            cols["score"] = self.scores[keep]
         ends = np.cumsum(counts)
         cols["rank"] = np.arange(1, int(ends[-1]) + 1 if len(ends) else 1) - \
             np.repeat(ends - counts, counts)

@@ -308,6 +308,17 @@ def topn_pipeline(scorer, *, predicts_ratings: bool = False, n: int | None = Non
     return p
 
 
+def random_pipeline(n: int | None = None, rng=None, *, name: str | None = None) -> Pipeline:
+    """The Random baseline: ``std:topn`` whose ranker is a ``RandomSelector`` over the candidates
+    (the training items without the user's history); the scorer slot stays empty."""
+    from .basic import RandomSelector
+
+    p = Pipeline.std_topn(name)
+    p.replace_component("ranker", RandomSelector(n=n, rng=rng), items="candidates",
+                        query="history-lookup")
+    return p
+
+
 def predict_pipeline(scorer, *, fallback: bool = True, n: int | None = None,
                      name: str | None = None, reranker=None) -> Pipeline:  # fmt: skip
     p = Pipeline.std_topn_predict(name, {"default_length": n, "fallback_predictor": fallback})

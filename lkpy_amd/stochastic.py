@@ -30,16 +30,47 @@ batch therefore agree bit for bit.
 
 from __future__ import annotations
 
-from hashlib import md5
 from typing import Any, Literal
 
 import numpy as np
 from pydantic import BaseModel
 
+from ._streams import RowStreams, parse_rng, user_stream  # noqa: F401 (re-exported)
 from .data import ItemList, RecQuery
 from .pipeline import Component
 
-_MASK64 = (1 << 64) - 1
+
+def rank_panel(panel, streams, n: int, *, transform, scale: float, seed: int, excl=None,
+               samples: int = 1, first_sample: int = 0, device_output: bool = False):
+    """
+    ``samples`` sampled rankings of every row of ``panel`` (device f32 [B x items]; non-finite
+    and ``excl``-uded entries take no part) under the given transform, scale and seed: (item
+    numbers int32 [B x S x n] with -1 padding, keys f32 [B x S x n] with NaN padding), sample
+    ``first_sample + s`` at ``[:, s]``; ``n < 0``: every item.  The row statistics are computed
+    once and one key panel is reused by every sample.
+    """
+    import torch
+
+    from . import _device as D
+
+    B, I = panel.shape
+    cols = I if n < 0 else min(n, I)
+    samples = int(samples)
+    idx = torch.full((B, samples, max(n, cols)), -1, dtype=torch.int32, device=panel.device)
+    keys = torch.full(idx.shape, float("nan"), dtype=torch.float32, device=panel.device)
+    if B and cols and samples:
+        d_streams = D._row_streams(streams, B, panel.device)
+        buf = stats = None
+        for s in range(samples):
+            buf, stats = D.stochastic_keys(
+                panel, d_streams, transform=transform, scale=scale, seed=seed,
+                sample=first_sample + s, excl=excl, stats=stats, out=buf)
+            picked = D.argtopn(buf, n)
+            idx[:, s, :cols] = picked
+            keys[:, s, :cols] = D.take_scores(buf, picked)
+    if device_output:
+        return idx, keys
+    return D.to_host(idx), D.to_host(keys)
 
 
 class StochasticTopNConfig(BaseModel, arbitrary_types_allowed=True):
@@ -51,47 +82,7 @@ class StochasticTopNConfig(BaseModel, arbitrary_types_allowed=True):
     scale: float = 1.0  # multiplies the scores before the transform (the softmax's beta)
 
 
-def _bytes_stream(key: bytes) -> int:
-    words = np.frombuffer(md5(key).digest(), np.int32)
-    return abs(int(np.bitwise_xor.reduce(words)))
-
-
-def user_stream(user_id) -> int | None:
-    "The stream of a user id (module docstring); None for an id that cannot give one."
-    if isinstance(user_id, (int, np.integer)):
-        return int(user_id) & _MASK64
-    if isinstance(user_id, str):
-        return _bytes_stream(user_id.encode("utf8"))
-    if isinstance(user_id, (bytes, np.bytes_)):
-        return _bytes_stream(bytes(user_id))
-    return None
-
-
-def _seed_state(seed) -> int:
-    "64 bits of a seed: SeedSequence(seed).generate_state(1, uint64)"
-    if isinstance(seed, np.random.Generator):
-        seed = seed.bit_generator
-    if isinstance(seed, np.random.BitGenerator):
-        return int(seed.random_raw()) & _MASK64
-    if not isinstance(seed, np.random.SeedSequence):
-        seed = np.random.SeedSequence(seed)
-    return int(seed.generate_state(1, np.uint64)[0])
-
-
-def parse_rng(spec) -> tuple[int, bool]:
-    "An ``rng`` spec (random.py:315-349) -> (64-bit seed, streams by user id?)"
-    if isinstance(spec, str):
-        if spec != "user":
-            raise ValueError(f"unrecognized rng specification {spec!r}")
-        return _seed_state(None), True
-    if isinstance(spec, tuple):
-        if len(spec) != 2 or spec[1] != "user":
-            raise ValueError(f"unrecognized key in rng specification {spec!r}")
-        return _seed_state(spec[0]), True
-    return _seed_state(spec), False
-
-
-class StochasticTopNRanker(Component):
+class StochasticTopNRanker(RowStreams, Component):
     """
     Stochastic top-N ranking with an optional weight transformation (``StochasticTopNRanker``,
     _ranker.py:59-156).  ``__call__`` ranks one scored list; :meth:`rank_panel` ranks every row of
@@ -104,30 +95,7 @@ class StochasticTopNRanker(Component):
         if isinstance(config, dict) and isinstance(config.get("rng"), list):
             config = {**config, "rng": tuple(config["rng"])}  # (a TOML / JSON [seed, "user"])
         super().__init__(config, **kwargs)
-        self.seed, self.by_user = parse_rng(self.config.rng)
-        self.calls = 0
-
-    # -- streams ------------------------------------------------------------------------------
-    def streams(self, user_ids, count: int | None = None) -> np.ndarray:
-        """
-        The uint64 streams of one call's rows: ``user_ids`` per row (None: ``count`` rows without
-        ids).  Counts as one call.
-        """
-        n = len(user_ids) if user_ids is not None else int(count)
-        out = (np.uint64(self.calls << 32) | np.arange(n, dtype=np.uint64))
-        self.calls = (self.calls + 1) & 0xFFFFFFFF
-        if self.by_user and user_ids is not None:
-            if isinstance(user_ids, np.ndarray) and user_ids.dtype.kind in "iu":
-                out = user_ids.astype(np.int64).view(np.uint64) if user_ids.dtype.kind == "i" \
-                    else user_ids.astype(np.uint64)
-            else:  # id by id: strings, bytes, a list of mixed ids
-                ids = user_ids.tolist() if isinstance(user_ids, np.ndarray) and \
-                    user_ids.dtype.kind != "O" else user_ids
-                for i, u in enumerate(ids):
-                    s = None if u is None else user_stream(u)
-                    if s is not None:
-                        out[i] = s
-        return np.ascontiguousarray(out, dtype=np.uint64)
+        self._init_streams(self.config.rng)
 
     def _length(self, n: int | None) -> int:
         if n is None or n < 0:
@@ -143,29 +111,9 @@ class StochasticTopNRanker(Component):
         keys f32 [B x S x n] with NaN padding), sample ``first_sample + s`` at ``[:, s]``.  The row
         statistics are computed once and one key panel is reused by every sample.
         """
-        import torch
-
-        from . import _device as D
-
-        n = self._length(n)
-        B, I = panel.shape
-        cols = I if n < 0 else min(n, I)
-        samples = int(samples)
-        idx = torch.full((B, samples, max(n, cols)), -1, dtype=torch.int32, device=panel.device)
-        keys = torch.full(idx.shape, float("nan"), dtype=torch.float32, device=panel.device)
-        if B and cols and samples:
-            d_streams = D._row_streams(streams, B, panel.device)
-            buf = stats = None
-            for s in range(samples):
-                buf, stats = D.stochastic_keys(
-                    panel, d_streams, transform=self.config.transform, scale=self.config.scale,
-                    seed=self.seed, sample=first_sample + s, excl=excl, stats=stats, out=buf)
-                picked = D.argtopn(buf, n)
-                idx[:, s, :cols] = picked
-                keys[:, s, :cols] = D.take_scores(buf, picked)
-        if device_output:
-            return idx, keys
-        return D.to_host(idx), D.to_host(keys)
+        return rank_panel(panel, streams, self._length(n), transform=self.config.transform,
+                          scale=self.config.scale, seed=self.seed, excl=excl, samples=samples,
+                          first_sample=first_sample, device_output=device_output)
 
     # -- one list -------------------------------------------------------------------------------
     def sample(self, items: ItemList, query=None, n: int | None = None, *, samples: int = 1,
