@@ -534,9 +534,10 @@ int als_cg_half_epoch(const lk_als_plan *p, const void *indptr, int is64, const 
         const int rc =
             p->KP > 64 ? als_blk_half_epoch(p, indptr, is64, indices, values, n_rows, 0, k, this_,
                                             other, otor, ld_otor, ws, out_frob, st, false, 0.f)
-                       : als_chol_half_epoch(p, indptr, is64, indices, values, n_rows, k, this_,
-                                             ld_this, other, ld_other, otor, ld_otor, ws, out_frob,
-                                             st, false, 0.f);
+                       : als_chol_half_epoch(p, indptr, is64, indices, values, n_rows,
+                                             /*n_cols unknown here*/ -1, k, this_, ld_this, other,
+                                             ld_other, otor, ld_otor, ws, out_frob, st, false,
+                                             0.f);
         p->dense_limit = -1;
         if (rc != LK_OK) return rc;
         t_begin = t_exact;

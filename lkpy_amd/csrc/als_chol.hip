@@ -303,23 +303,39 @@ __device__ __forceinline__ void wait_vm_upto(const int n)
 }
 
 // group g of the staged batch -> ring slot `slot_idx` (compile-time)
+// WIDE = false: the gathered table is smaller than 4 GiB (decided on the host, per launch), so a
+// lane's source is the table's base in an SGPR pair plus ONE 32-bit offset, column * 256 + 16 *
+// (lane & 15): a v_lshl_or_b32 where the 64-bit form needs a v_lshlrev_b64 and a v_lshl_add_u64.
+// (`other` is a kernel argument: the SGPR pair comes from an s_load, no VALU write precedes its
+// use as the base.)
+template <bool WIDE>
 __device__ __forceinline__ void dma_issue(const unsigned ring_lds, const int slot_idx, const int g,
                                           const float *stage_slot,
                                           const float *__restrict__ other)
 {
     const int lane = lane_id();
     const unsigned col = __builtin_bit_cast(unsigned, stage_slot[g * 4]);
-    // one v_mad_u64_u32: (this lane's 16 bytes of row 0) + col * 256
-    const uint64_t lane_base = (uint64_t)(uintptr_t)(other + (lane & 15) * 4);
-    const float *src = reinterpret_cast<const float *>(lane_base + (uint64_t)col * 256ull);
     const unsigned dst = ring_lds + slot_idx * 1024;
     unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(src), "s"(dst)
-        : "memory");
+    if constexpr (WIDE) {
+        // one v_mad_u64_u32: (this lane's 16 bytes of row 0) + col * 256
+        const uint64_t lane_base = (uint64_t)(uintptr_t)(other + (lane & 15) * 4);
+        const float *src = reinterpret_cast<const float *>(lane_base + (uint64_t)col * 256ull);
+        asm volatile(
+            "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+            "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+            : "=&s"(keep)
+            : "v"(src), "s"(dst)
+            : "memory");
+    } else {
+        const unsigned off = col * 256u + (unsigned)(lane & 15) * 16u;
+        asm volatile(
+            "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+            "global_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
+            : "=&s"(keep)
+            : "v"(off), "s"(dst), "s"(other)
+            : "memory");
+    }
 }
 
 struct DmaOperand {
@@ -336,22 +352,65 @@ __device__ __forceinline__ DmaOperand dma_fetch(const float *ring, const int slo
     return o;
 }
 
+// SEQY on the DMA path: the reference's y chain WITHOUT the 4 x 4 transposition of y_chain_step.
+// The group's four gathered rows still sit in the wave's ring slot when the group is consumed, so
+// lane (t, sub) -- which owns the chain of feature sub * 4 + t -- reads that feature's four values
+// straight out of them (`rows` = slot + sub * 4 + t, row stride 64 words: the lanes read 64
+// consecutive words of a row; two ds_read2st64_b32) and the four multipliers v + 1 (`v1g`: staged
+// per batch by gram_accumulate_dma, one broadcast ds_read_b128).  Two packed products and the chain's
+// four additions: the same products (each half of a v_pk_mul_f32 is rounded as by v_mul_f32),
+// added in the same order, for 6 vector instructions where the transposition took 13.
+// MASKED: entries past the row's end are zeros times the multiplier of the row's last entry, as
+// in y_chain_step.
+template <bool MASKED>
+__device__ __forceinline__ void y_chain_lds(float &yc, const float *rows, const float *v1g,
+                                            const int g, const int nb)
+{
+    float q[4] = {rows[0], rows[64], rows[128], rows[192]};
+    const f32x4 v1 = *reinterpret_cast<const f32x4 *>(v1g);
+    if constexpr (MASKED) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) q[e] = (g * 4 + e) < nb ? q[e] : 0.f;
+    }
+    f32x2 lo = f32x2{q[0], q[1]} * f32x2{v1.x, v1.y};
+    f32x2 hi = f32x2{q[2], q[3]} * f32x2{v1.z, v1.w};
+    // (product and sum are rounded separately: nothing may be contracted across this point)
+    asm volatile("" : "+v"(lo), "+v"(hi));
+    yc = __fadd_rn(yc, lo.x);
+    yc = __fadd_rn(yc, lo.y);
+    yc = __fadd_rn(yc, hi.x);
+    yc = __fadd_rn(yc, hi.y);
+}
+
+// the y-chain operands of dma_apply (SEQY): this lane's word of ring slot 0's first row and
+// the staged multipliers of the current batch
+struct DmaChain {
+    const float *rows = nullptr;
+    const float *v1 = nullptr;
+};
+
 // WITH_Y = false (the chunk kernel of plans whose chunked rows all take y from the reference-order
 // chains): no v + 1, no y arithmetic -- the slab's y words are never read
 template <bool MASKED, bool SEQY = false, bool WITH_Y = true>
 __device__ __forceinline__ void dma_apply(Gram<4> &G, const DmaOperand &o, const int g,
-                                          const int nb, const bool expl)
+                                          const int nb, const bool expl, const int slot_idx = 0,
+                                          const DmaChain ch = DmaChain{})
 {
     const int lane = lane_id();
     const bool live = !MASKED || (g * 4 + (lane >> 4)) < nb;
     const float v = o.v;
     const float va = expl ? 1.0f : v;
-    float q[4] = {o.q.x, o.q.y, o.q.z, o.q.w}, a[4];
+    float q[4] = {o.q.x, o.q.y, o.q.z, o.q.w};
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        q[t] = live ? q[t] : 0.f;
-        a[t] = q[t] * va;
-    }
+    for (int t = 0; t < 4; ++t) q[t] = live ? q[t] : 0.f;
+    // (a[t] stays four scalar products: written as two packed ones with the multiplier
+    // broadcast, hipcc packs only where `va` sits in an even register, names its odd neighbour --
+    // often the destination of a load in flight -- as the unused half and waits vmcnt(0) for it
+    // in front of the MFMAs; with the multiplier in a pair of its own it unpacks most of them
+    // again behind the MFMAs and the pair costs a move per group: DESIGN.md section 4.1d)
+    float a[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) a[t] = q[t] * va;
 #pragma unroll
     for (int tj = 0; tj < 4; ++tj)
 #pragma unroll
@@ -359,10 +418,10 @@ __device__ __forceinline__ void dma_apply(Gram<4> &G, const DmaOperand &o, const
             G.t[tidx(ti, tj)] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ti], q[tj],
                                                                      G.t[tidx(ti, tj)], 0, 0, 0);
     if constexpr (WITH_Y) {
-        const float v1 = expl ? v : v + 1.0f;
         if constexpr (SEQY) {
-            y_chain_step<4>(G.yc, q, v1);
+            y_chain_lds<MASKED>(G.yc, ch.rows + slot_idx * 256, ch.v1 + g * 4, g, nb);
         } else {
+            const float v1 = expl ? v : v + 1.0f;
 #pragma unroll
             for (int t = 0; t < 4; ++t) G.y[t] = fmaf(q[t], v1, G.y[t]);
         }
@@ -372,9 +431,10 @@ __device__ __forceinline__ void dma_apply(Gram<4> &G, const DmaOperand &o, const
 template <bool MASKED, bool SEQY = false, bool WITH_Y = true>
 __device__ __forceinline__ void dma_consume(Gram<4> &G, const float *ring, const int slot_idx,
                                             const int g, const int nb, const float *stage_slot,
-                                            const bool expl)
+                                            const bool expl, const DmaChain ch = DmaChain{})
 {
-    dma_apply<MASKED, SEQY, WITH_Y>(G, dma_fetch(ring, slot_idx, g, stage_slot), g, nb, expl);
+    dma_apply<MASKED, SEQY, WITH_Y>(G, dma_fetch(ring, slot_idx, g, stage_slot), g, nb, expl,
+                                    slot_idx, ch);
 }
 
 template <int NT>
@@ -392,12 +452,16 @@ __device__ __forceinline__ void gram_zero(Gram<NT> &G);
 // slab stores count in vmcnt like the loads: the first waits after a boundary are a little more
 // conservative than needed, never less.)  The last block of the range is left in G.
 // RING: groups in flight (ring: RING * 256 floats); the solve kernel's 8, the chunk kernel's own
-template <bool SEQY = false, bool WITH_Y = true, int RING = DMA_RING>
+// SEQY: `v1s` (2 x 64 floats, wave-private) takes the multipliers v + 1 of the two staged batches
+// for y_chain_lds
+// WIDE: 64-bit gather addresses (dma_issue)
+template <bool SEQY = false, bool WITH_Y = true, int RING = DMA_RING, bool WIDE = true>
 __device__ __forceinline__ void gram_accumulate_dma(Gram<4> &G, const int32_t *__restrict__ cols,
                                                     const float *__restrict__ vals, int64_t beg,
                                                     int64_t end, const float *__restrict__ other,
                                                     const bool expl, float *ring, float *stage,
-                                                    float *__restrict__ slab = nullptr)
+                                                    float *__restrict__ slab = nullptr,
+                                                    float *v1s = nullptr)
 {
     static_assert(RING == 8 || RING == 4, "DMA ring: 4 or 8 groups");
     const int lane = lane_id();
@@ -407,16 +471,23 @@ __device__ __forceinline__ void gram_accumulate_dma(Gram<4> &G, const int32_t *_
 
     float *wr_cur = stage + lane, *wr_nxt = stage + 128 + lane;
     const float *rd_cur = stage + (lane >> 4), *rd_nxt = stage + 128 + (lane >> 4);
+    // (SEQY) the chain's view of the ring -- lane (t, sub): word sub * 4 + t of a row -- and the
+    // multiplier buffer of the current batch (wave-uniform; the other one is `yb ^ 64` words on)
+    DmaChain ch;
+    unsigned yb = 0;
+    if constexpr (SEQY && WITH_Y) ch.rows = ring + (lane & 15) * 4 + (lane >> 4);
     {
         const int64_t e = (beg + lane < end) ? beg + lane : last;
+        const float v = vals[e];
         wr_cur[0] = __builtin_bit_cast(float, cols[e]);
-        wr_cur[64] = vals[e];
+        wr_cur[64] = v;
+        if constexpr (SEQY && WITH_Y) v1s[lane] = expl ? v : v + 1.0f;  // `vals += 1.0`
     }
     // groups of the whole row; group gg lives in batch gg / 16
     const int total = (int)((end - beg + 3) >> 2);
 #pragma unroll
     for (int g = 0; g < RING; ++g)
-        if (g < total) dma_issue(ring_lds, g, g, rd_cur, other);
+        if (g < total) dma_issue<WIDE>(ring_lds, g, g, rd_cur, other);
 
     int64_t base = beg;
     int g0 = 0;  // first group of the current batch
@@ -435,6 +506,7 @@ __device__ __forceinline__ void gram_accumulate_dma(Gram<4> &G, const int32_t *_
         // batch's first iteration: the pipeline restarts at batch boundaries.)
         wait_vm<RING - 1>();
         DmaOperand cur = dma_fetch(ring, 0, 0, rd_cur);
+        if constexpr (SEQY && WITH_Y) ch.v1 = v1s + yb;
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
             DmaOperand nxt = cur;
@@ -442,15 +514,21 @@ __device__ __forceinline__ void gram_accumulate_dma(Gram<4> &G, const int32_t *_
                 wait_vm<RING - 2>();
                 nxt = dma_fetch(ring, (g + 1) % RING, g + 1, rd_cur);
             }
-            dma_apply<false, SEQY, WITH_Y>(G, cur, g, 64, expl);
+            dma_apply<false, SEQY, WITH_Y>(G, cur, g, 64, expl, g % RING, ch);
             if (g == 16 - RING - 2) {
                 wr_nxt[0] = __builtin_bit_cast(float, nxt_col);
                 wr_nxt[64] = nxt_val;
+                if constexpr (SEQY && WITH_Y) {
+                    // (the value is waited for HERE, with the writes above: hoisted, the addition
+                    // would drain the memory queue groups earlier)
+                    asm volatile("" : "+v"(nxt_val));
+                    v1s[(yb ^ 64) + lane] = expl ? nxt_val : nxt_val + 1.0f;
+                }
             }
             if (g < 16 - RING)
-                dma_issue(ring_lds, g % RING, g + RING, rd_cur, other);
+                dma_issue<WIDE>(ring_lds, g % RING, g + RING, rd_cur, other);
             else
-                dma_issue(ring_lds, g % RING, g + RING - 16, rd_nxt, other);
+                dma_issue<WIDE>(ring_lds, g % RING, g + RING - 16, rd_nxt, other);
             cur = nxt;
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -465,6 +543,7 @@ __device__ __forceinline__ void gram_accumulate_dma(Gram<4> &G, const int32_t *_
         const float *tr = rd_cur;
         rd_cur = rd_nxt;
         rd_nxt = tr;
+        yb ^= 64;
     }
     // the last batches: wave-uniform guards, waits that shrink towards the end of the row
     for (; g0 < total; base += 64, g0 += 16) {
@@ -477,23 +556,30 @@ __device__ __forceinline__ void gram_accumulate_dma(Gram<4> &G, const int32_t *_
             nxt_col = cols[e];
             nxt_val = vals[e];
         }
+        if constexpr (SEQY && WITH_Y) ch.v1 = v1s + yb;
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
             const int gg = g0 + g;
             if (gg < total) {
                 const int later = total - 1 - gg;  // groups issued after this one
                 wait_vm_upto(later < RING - 1 ? later : RING - 1);
-                dma_consume<true, SEQY, WITH_Y>(G, ring, g % RING, g, nb, rd_cur, expl);
+                dma_consume<true, SEQY, WITH_Y>(G, ring, g % RING, g, nb, rd_cur, expl, ch);
             }
             if (g == 16 - RING - 2 && more) {
                 wr_nxt[0] = __builtin_bit_cast(float, nxt_col);
                 wr_nxt[64] = nxt_val;
+                if constexpr (SEQY && WITH_Y) {
+                    // (the value is waited for HERE, with the writes above: hoisted, the addition
+                    // would drain the memory queue groups earlier)
+                    asm volatile("" : "+v"(nxt_val));
+                    v1s[(yb ^ 64) + lane] = expl ? nxt_val : nxt_val + 1.0f;
+                }
             }
             if (gg + RING < total) {
                 if (g < 16 - RING)
-                    dma_issue(ring_lds, g % RING, g + RING, rd_cur, other);
+                    dma_issue<WIDE>(ring_lds, g % RING, g + RING, rd_cur, other);
                 else
-                    dma_issue(ring_lds, g % RING, g + RING - 16, rd_nxt, other);
+                    dma_issue<WIDE>(ring_lds, g % RING, g + RING - 16, rd_nxt, other);
             }
         }
         if (slab && ((g0 + 16) & 63) == 0 && g0 + 16 < total) {  // a block boundary, more follows
@@ -507,6 +593,7 @@ __device__ __forceinline__ void gram_accumulate_dma(Gram<4> &G, const int32_t *_
         const float *tr = rd_cur;
         rd_cur = rd_nxt;
         rd_nxt = tr;
+        yb ^= 64;
     }
 }
 
@@ -517,7 +604,7 @@ __device__ __forceinline__ void gram_accumulate_dma(Gram<4> &G, const int32_t *_
 // shrink); for a 256-entry chunk that is a quarter of the work.  Here the batch loop is unrolled
 // over the four batches, so every guard and every wait count is a compile-time constant.  Same
 // operations in the same order: bit-identical to gram_accumulate_dma on the same range.
-template <bool WITH_Y = true, int RING = DMA_RING>
+template <bool WITH_Y = true, int RING = DMA_RING, bool WIDE = true>
 __device__ __forceinline__ void gram_accumulate_dma_256(Gram<4> &G, const int32_t *__restrict__ cols,
                                                         const float *__restrict__ vals, int64_t beg,
                                                         const float *__restrict__ other,
@@ -532,7 +619,7 @@ __device__ __forceinline__ void gram_accumulate_dma_256(Gram<4> &G, const int32_
     wr0[0] = __builtin_bit_cast(float, cols[beg + lane]);
     wr0[64] = vals[beg + lane];
 #pragma unroll
-    for (int g = 0; g < RING; ++g) dma_issue(ring_lds, g, g, rd0, other);
+    for (int g = 0; g < RING; ++g) dma_issue<WIDE>(ring_lds, g, g, rd0, other);
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
         float *const wr_nxt = (b & 1) ? wr0 : wr1;
@@ -566,9 +653,9 @@ __device__ __forceinline__ void gram_accumulate_dma_256(Gram<4> &G, const int32_
             }
             if (gg + RING < TOTAL) {
                 if (g < 16 - RING)
-                    dma_issue(ring_lds, g % RING, g + RING, rd_cur, other);
+                    dma_issue<WIDE>(ring_lds, g % RING, g + RING, rd_cur, other);
                 else
-                    dma_issue(ring_lds, g % RING, g + RING - 16, rd_nxt, other);
+                    dma_issue<WIDE>(ring_lds, g % RING, g + RING - 16, rd_nxt, other);
             }
             cur = nxt;
             __builtin_amdgcn_sched_barrier(0);
@@ -697,7 +784,8 @@ int als_chol_chunk_wgs_per_cu()
 }
 
 // WITH_Y = false: the slabs carry the tiles only (chol_front)
-template <int NT, bool EXPL, bool WITH_Y>
+// WIDE (padded k = 64 only): 64-bit gather addresses, for tables of 4 GiB and more (dma_issue)
+template <int NT, bool EXPL, bool WITH_Y, bool WIDE>
 __device__ __forceinline__ void als_chunk_body(
     const int32_t *__restrict__ indices, const float *__restrict__ values,
     const int64_t *__restrict__ chunk_beg, const int32_t *__restrict__ chunk_len,
@@ -719,16 +807,16 @@ __device__ __forceinline__ void als_chunk_body(
     if constexpr (DMA) {
         const int len = chunk_len[c];
         if (block_len == 256 && len > 256) {  // (wave-uniform) a reference-order work unit
-            gram_accumulate_dma<false, WITH_Y, CHUNK_RING>(
+            gram_accumulate_dma<false, WITH_Y, CHUNK_RING, WIDE>(
                 G, indices, values, beg, beg + len, other, EXPL,
                 stage_all[wave] + GRAM_STAGE_WORDS, stage_all[wave], slab);
             slab += (size_t)((len - 1) >> 8) * slab_floats<NT>();  // the last block is still in G
         } else if (len == 256)  // a full reference-order block
-            gram_accumulate_dma_256<WITH_Y, CHUNK_RING>(
+            gram_accumulate_dma_256<WITH_Y, CHUNK_RING, WIDE>(
                 G, indices, values, beg, other, EXPL, stage_all[wave] + GRAM_STAGE_WORDS,
                 stage_all[wave]);
         else
-            gram_accumulate_dma<false, WITH_Y, CHUNK_RING>(
+            gram_accumulate_dma<false, WITH_Y, CHUNK_RING, WIDE>(
                 G, indices, values, beg, beg + len, other, EXPL,
                 stage_all[wave] + GRAM_STAGE_WORDS, stage_all[wave]);
     } else
@@ -737,7 +825,7 @@ __device__ __forceinline__ void als_chunk_body(
     slab_store<NT, WITH_Y>(G, slab);
 }
 
-template <int NT, bool EXPL, bool WITH_Y>
+template <int NT, bool EXPL, bool WITH_Y, bool WIDE = false>
 __global__ __launch_bounds__(256) void als_chunk_kernel(
     const int32_t *__restrict__ indices, const float *__restrict__ values,
     const int64_t *__restrict__ chunk_beg, const int32_t *__restrict__ chunk_len,
@@ -745,24 +833,41 @@ __global__ __launch_bounds__(256) void als_chunk_kernel(
     const int32_t *__restrict__ chunk_slab, int block_len)
 {
     __shared__ __attribute__((aligned(16))) float lds_flat[4 * chunk_lds_floats<NT>()];
-    als_chunk_body<NT, EXPL, WITH_Y>(indices, values, chunk_beg, chunk_len, n_chunks, other, ld,
+    als_chunk_body<NT, EXPL, WITH_Y, WIDE>(indices, values, chunk_beg, chunk_len, n_chunks, other, ld,
                                      slabs, (int64_t)blockIdx.x, lds_flat, chunk_slab, block_len);
 }
 
 // ---- solve: the packed L image ---------------------------------------------------------------
 //
-// Packed strictly-lower image: column j holds rows c in [c0(j), KP), c0 = (j+1)&~3
-// (16-byte aligned segments); off(j) = 4*KP*m - 8m^2 + 4m + r*(KP - 4m), j = 4m + r.
+// The solver's LDS: KP reciprocal pivots | extraction scratch (64 lanes x 4) | L image.
+// Packed strictly-lower image: column j holds rows c in [c0(j), KP), c0 = (j+1)&~3 (16-byte
+// aligned segments), the columns at DESCENDING addresses: column 0 ends the image, column j + 1
+// lies directly below column j.  off(j) is the word of row c0(j) of column j.
+// Why descending: at KP = 64 every lane stores its lj of column j at off(j) - c0(j) + lane -- one
+// address register plus an immediate, no per-column address select.  The lanes below the stored
+// segment (rows < c0(j)) land on the words right below it: the segments of the columns j + 1 ..,
+// which are stored later, or -- for the last columns -- up to 60 words of the extraction scratch
+// in front of the image, which is dead between a panel's extraction and the next one.
 template <int KP>
 struct LPack {
     __host__ __device__ static constexpr int c0(int j) { return (j + 1) & ~3; }
-    __host__ __device__ static constexpr int off(int j)
+    // words of the columns 0 .. j-1: 4*KP*m - 8m^2 + 4m + r*(KP - 4m), j = 4m + r
+    __host__ __device__ static constexpr int before(int j)
     {
         const int m = j >> 2, r = j & 3;
         return 4 * KP * m - 8 * m * m + 4 * m + r * (KP - 4 * m);
     }
-    static constexpr int SIZE = KP * KP / 2 + KP;
+    static constexpr int SIZE = KP * KP / 2 + KP;  // words of the image
+    static constexpr int RINV = 0, SCR = KP, IMG = KP + 256;
+    __host__ __device__ static constexpr int off(int j)
+    {
+        return IMG + SIZE - before(j) - (KP - c0(j));
+    }
 };
+static_assert(LPack<64>::off(62) - LPack<64>::c0(62) >= LPack<64>::SCR &&
+                  LPack<64>::off(0) + 64 == LPack<64>::IMG + LPack<64>::SIZE &&
+                  LPack<64>::off(63) == LPack<64>::IMG,
+              "L image: the stores of all 64 lanes stay between the scratch and the image's end");
 
 // ---- hybrid Cholesky ---------------------------------------------------------------------------
 //
@@ -782,7 +887,7 @@ struct LPack {
 template <int NT>
 __host__ __device__ constexpr int hybrid_lds_floats()
 {
-    // L image | KP reciprocal pivots | extraction scratch (64 lanes x 4)
+    // KP reciprocal pivots | extraction scratch (64 lanes x 4) | L image (LPack)
     return LPack<NT * 16>::SIZE + NT * 16 + 256;
 }
 
@@ -793,14 +898,17 @@ __device__ __forceinline__ void hybrid_step(Gram<NT> &G, float &b, float &minpiv
     constexpr int KP = NT * 16, J = 4 * M, TJ = M >> 2, MG = M & 3;
     using P = LPack<KP>;
     const int slot = lane >> 4;
-    float *rinvarr = lds + P::SIZE;
-    float *scr = rinvarr + KP;
+    float *rinvarr = lds + P::RINV;
+    float *scr = lds + P::SCR;
 
     // E. extraction
 #pragma unroll
     for (int t = TJ; t < NT; ++t)
         if (slot == MG)
             *reinterpret_cast<f32x4 *>(&scr[(t * 16 + (lane & 15)) * 4]) = G.t[tidx(TJ, t)];
+    // (the zeroed quad and the masked read stay: with every lane reading -- the lanes left of the
+    // panel would get stale words that `lane > j` discards below -- the half-epoch no longer
+    // reproduced its recorded bits, for a reason not found: DESIGN.md section 4.1d)
     f32x4 pv = f32x4{0.f, 0.f, 0.f, 0.f};
     if (slot >= TJ && lane < KP) pv = *reinterpret_cast<const f32x4 *>(&scr[lane * 4]);
     float pr[4] = {pv.x, pv.y, pv.z, pv.w};
@@ -814,14 +922,20 @@ __device__ __forceinline__ void hybrid_step(Gram<NT> &G, float &b, float &minpiv
         minpiv = fminf(minpiv, piv);
         const float rinv = __builtin_amdgcn_rsqf(piv);
         // (no exec-mask round trips in the column loop: rinv is wave-uniform, every lane stores
-        // the same value to the same word; lanes outside the stored segment of column j aim at
-        // their own word of the extraction scratch, which is dead until the next panel)
+        // the same value to the same word; at KP = 64 every lane stores its lj at the column's
+        // base + lane -- LPack says where the lanes outside the stored segment land; narrower
+        // systems leave lanes past KP, which aim at their own word of the extraction scratch,
+        // dead until the next panel)
         rinvarr[j] = rinv;
         const float lj = (lane > j) ? pr[s0] * rinv : 0.f;  // strictly-lower column j
         if (j + 1 < KP) {
-            const bool in = lane >= P::c0(j) && lane < KP;
-            float *dst = in ? &lds[P::off(j) + lane - P::c0(j)] : &scr[lane];
-            *dst = lj;
+            if constexpr (KP == 64) {
+                lds[P::off(j) - P::c0(j) + lane] = lj;
+            } else {
+                const bool in = lane >= P::c0(j) && lane < KP;
+                float *dst = in ? &lds[P::off(j) + lane - P::c0(j)] : &scr[lane];
+                *dst = lj;
+            }
         }
         // forward substitution: z_j = y_j / L_jj, y -= L[:, j] z_j
         const float zj = bcast(b, j) * rinv;
@@ -884,7 +998,7 @@ __device__ __forceinline__ float hybrid_solve(Gram<NT> &G, float &b, float *__re
     *tmid = __builtin_amdgcn_s_memtime();
 #endif
     // backward: L^T x = z, lane = primed row (z = b / L_jj after the folded forward pass)
-    const float dinv = (lane < KP) ? lds[P::SIZE + lane] : 0.f;
+    const float dinv = (lane < KP) ? lds[P::RINV + lane] : 0.f;
     b *= dinv;
     const int my_c0 = (lane + 1) & ~3;
     const float *mycol = lds + P::off(lane) - my_c0;
@@ -917,7 +1031,8 @@ __device__ __forceinline__ float hybrid_solve(Gram<NT> &G, float &b, float *__re
 // SEQY: rows that form their own right-hand side do it in the reference's order (y_chain_step); a
 // template parameter so that LK_ALS_RHS_ORDER=accurate keeps round 4's kernel instruction for
 // instruction
-template <int NT, bool IS64, bool EXPL, bool CTL, bool YREF = false, bool SEQY = false>
+// WIDE (padded k = 64 only): 64-bit gather addresses, for tables of 4 GiB and more (dma_issue)
+template <int NT, bool IS64, bool EXPL, bool CTL, bool YREF, bool SEQY, bool WIDE>
 __device__ __forceinline__ void als_solve_body(
     const typename IndPtr<IS64>::type *__restrict__ indptr, const int32_t *__restrict__ indices,
     const float *__restrict__ values, const int32_t *__restrict__ order, int64_t n_rows,
@@ -989,9 +1104,14 @@ __device__ __forceinline__ void als_solve_body(
     } else {
         // (the solver's LDS is idle while the normal matrix is built: it stages the CSR
         // batches and, for k = 64, holds the ring of prefetched factor rows)
-        if constexpr (NT == 4)
-            gram_accumulate_dma<SEQY && !YREF>(G, indices, values, beg, end, other, EXPL, lds,
-                                               lds + LPack<KP>::SIZE + KP);
+        // (ring: words 0 .. 2047, staged batches: the last 256; the 128 words between them are
+        // idle as well and take the y chain's multipliers)
+        if constexpr (NT == 4) {
+            static_assert(NT != 4 || DMA_RING * 256 + 128 <= LPack<KP>::SIZE + KP, "v + 1 staging");
+            gram_accumulate_dma<SEQY && !YREF, true, DMA_RING, WIDE>(
+                G, indices, values, beg, end, other, EXPL, lds, lds + LPack<KP>::SIZE + KP,
+                nullptr, lds + DMA_RING * 256);
+        }
         else
             gram_accumulate<NT, SEQY && !YREF>(G, indices, values, beg, end, other, ld_other,
                                                EXPL, lds);
@@ -1067,7 +1187,8 @@ __device__ __forceinline__ void als_solve_body(
 }
 
 // the hybrid solver keeps the matrix in its 40 accumulator registers: 4 waves per SIMD
-template <int NT, bool IS64, bool EXPL, bool CTL, bool YREF = false, bool SEQY = false>
+template <int NT, bool IS64, bool EXPL, bool CTL, bool YREF = false, bool SEQY = false,
+          bool WIDE = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void als_solve_kernel(
     const typename IndPtr<IS64>::type *__restrict__ indptr, const int32_t *__restrict__ indices,
     const float *__restrict__ values, const int32_t *__restrict__ order, int64_t n_rows,
@@ -1078,7 +1199,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void a
     int chunk_rt = 0)
 {
     __shared__ __attribute__((aligned(16))) float lds_flat[4 * hybrid_lds_floats<NT>()];
-    als_solve_body<NT, IS64, EXPL, CTL, YREF, SEQY>(indptr, indices, values, order, n_rows,
+    als_solve_body<NT, IS64, EXPL, CTL, YREF, SEQY, WIDE>(indptr, indices, values, order, n_rows,
                                                     row_slab, other, ld_other, this_, ld_this,
                                                     otor_p, slabs, row_delta, status, k, reg, ctl,
                                                     y_ref, chunk_rt, (int64_t)blockIdx.x, lds_flat);
@@ -1383,6 +1504,15 @@ struct CholHalf {
     float *yref = nullptr;
     bool tm = false;
     bool forked = false;
+    // rows of `other` (the gathered table); negative: unknown
+    int64_t n_cols = -1;
+
+    // 64-bit gather addresses in the k = 64 Gram loops (dma_issue): unless the table is known to
+    // be smaller than 4 GiB, so that every byte offset into it fits 32 bits
+    bool wide() const
+    {
+        return n_cols < 0 || (uint64_t)n_cols * (uint64_t)ld_other * sizeof(float) >= (1ull << 32);
+    }
 
     int *status() const { return reinterpret_cast<int *>(ws + p->off_status); }
     float *otor_p() const { return reinterpret_cast<float *>(ws + p->off_otor); }
@@ -1451,17 +1581,26 @@ static int chol_front(CholHalf &h, CholKind<NT, IS64, EXPL>)
     // kernel forms no right-hand side, the slabs' y words stay unwritten and nobody reads them
     // (the YREF solve skips them, the slab sums below stop in front of them)
     const bool chunk_y = !(h.yref != nullptr && h.n_y >= p->n_long);
+    constexpr bool CAN_WIDE = NT == 4;  // (only the k = 64 loops gather by DMA)
+    const bool wide = CAN_WIDE && h.wide();
     if (p->n_chunks > 0) {
 #define LK_CHUNK_LAUNCH(WITHY)                                                                  \
-    hipLaunchKernelGGL((als_chunk_kernel<NT, EXPL, WITHY>),                                    \
+    if (wide)                                                                                  \
+        LK_CHUNK_LAUNCH_W(WITHY, CAN_WIDE);                                                    \
+    else                                                                                       \
+        LK_CHUNK_LAUNCH_W(WITHY, false)
+#define LK_CHUNK_LAUNCH_W(WITHY, WIDEV)                                                         \
+    hipLaunchKernelGGL((als_chunk_kernel<NT, EXPL, WITHY, WIDEV>),                             \
                        dim3((unsigned)((p->n_chunks + 3) / 4)), dim3(256), 0, st, h.indices,   \
                        h.values, p->d_chunk_beg, p->d_chunk_len, p->n_chunks, h.other,         \
                        h.ld_other, slabs, p->d_chunk_slab, p->unit > p->chunk ? (int)p->chunk : 0)
-        if (chunk_y)
+        if (chunk_y) {
             LK_CHUNK_LAUNCH(true);
-        else
+        } else {
             LK_CHUNK_LAUNCH(false);
+        }
 #undef LK_CHUNK_LAUNCH
+#undef LK_CHUNK_LAUNCH_W
     }
     if (h.n_y > 0) {
         int rc = launch_rhs_reference(p, h.indptr, IS64 ? 1 : 0, h.indices, h.values, p->d_order,
@@ -1498,11 +1637,20 @@ static int chol_solve(CholHalf &h, CholKind<NT, IS64, EXPL>, hipEvent_t otor_rea
     const int ref_chunk = (p->ref_order || p->hybrid) ? p->chunk : 0;
     const int64_t n_y = h.n_y, n_solve = h.n_solve;
     float *yref = h.yref;
+    constexpr bool CAN_WIDE = NT == 4;
+    const bool wide = CAN_WIDE && h.wide();
     if (otor_ready) LK_HIP_CHECK(hipStreamWaitEvent(st, otor_ready, 0));
 #define LK_SOLVE_LAUNCH(CTLV, YREFV, T0, NTASKS, YPTR, STREAM)                                \
     LK_SOLVE_LAUNCH_S(CTLV, YREFV, false, T0, NTASKS, YPTR, STREAM)
 #define LK_SOLVE_LAUNCH_S(CTLV, YREFV, SEQV, T0, NTASKS, YPTR, STREAM)                        \
-    hipLaunchKernelGGL((als_solve_kernel<NT, IS64, EXPL, CTLV, YREFV, SEQV>),                  \
+    do {                                                                                       \
+        if (wide)                                                                              \
+            LK_SOLVE_LAUNCH_W(CTLV, YREFV, SEQV, CAN_WIDE, T0, NTASKS, YPTR, STREAM);          \
+        else                                                                                   \
+            LK_SOLVE_LAUNCH_W(CTLV, YREFV, SEQV, false, T0, NTASKS, YPTR, STREAM);             \
+    } while (0)
+#define LK_SOLVE_LAUNCH_W(CTLV, YREFV, SEQV, WIDEV, T0, NTASKS, YPTR, STREAM)                 \
+    hipLaunchKernelGGL((als_solve_kernel<NT, IS64, EXPL, CTLV, YREFV, SEQV, WIDEV>),           \
                        dim3((unsigned)(((NTASKS) + 3) / 4)), dim3(256), 0, (STREAM), ip,       \
                        h.indices, h.values, p->d_order + (T0), (NTASKS), p->d_row_slab,        \
                        h.other, h.ld_other, h.this_, h.ld_this, h.otor_p(), h.slabs(),         \
@@ -1546,6 +1694,7 @@ static int chol_solve(CholHalf &h, CholKind<NT, IS64, EXPL>, hipEvent_t otor_rea
     }
 #undef LK_SOLVE_LAUNCH
 #undef LK_SOLVE_LAUNCH_S
+#undef LK_SOLVE_LAUNCH_W
     if (h.tm) {
         LK_HIP_CHECK(hipEventRecord(p->ev[p->timing_n][2], st));
         p->timing_n++;
@@ -1594,13 +1743,15 @@ static int half_solve(CholHalf &h, bool expl, hipEvent_t otor_ready)
 size_t als_chol_slab_floats(int NT) { return (size_t)(als_tiles(NT) * 4 + NT) * 64; }
 
 // Exact half-epoch for padded k <= 64 (dispatch target of lk_als_implicit_half_epoch /
-// lk_als_explicit_half_epoch); `otor` null = explicit model.
+// lk_als_explicit_half_epoch); `otor` null = explicit model.  `n_cols`: rows of `other`, or
+// negative if the caller does not know (the gathers then use 64-bit addresses).
 int als_chol_half_epoch(const lk_als_plan *p, const void *indptr, int is64, const int32_t *indices,
-                        const float *values, int64_t n_rows, int k, float *this_, int ld_this,
-                        const float *other, int ld_other, const float *otor, int ld_otor, char *ws,
-                        float *out_frob, hipStream_t st, bool expl, float reg)
+                        const float *values, int64_t n_rows, int64_t n_cols, int k, float *this_,
+                        int ld_this, const float *other, int ld_other, const float *otor,
+                        int ld_otor, char *ws, float *out_frob, hipStream_t st, bool expl, float reg)
 {
     CholHalf h{p, indptr, is64 != 0, indices, values, n_rows, k, this_, ld_this, other, ld_other, ws, reg, st};
+    h.n_cols = n_cols;
     int rc = half_prep(h, expl, otor, ld_otor);
     if (rc == LK_OK) rc = half_front(h, expl);
     if (rc == LK_OK) rc = half_solve(h, expl, nullptr);
@@ -1628,6 +1779,8 @@ int als_chol_epoch(const lk_als_plan *pu, const lk_als_plan *pi, const void *u_i
     const int k = pu->k, KP = pu->KP;
     CholHalf hu{pu, u_indptr, pu->is64 != 0, u_indices, u_values, pu->n_rows, k, P, KP, Q, KP, ws_u, 0.f, st};
     CholHalf hi{pi, i_indptr, pi->is64 != 0, i_indices, i_values, pi->n_rows, k, Q, KP, P, KP, ws_i, 0.f, st};
+    hu.n_cols = pi->n_rows;  // (each half gathers the rows the other one solves)
+    hi.n_cols = pu->n_rows;
     int rc = half_prep(hu, false, qtq, ld_qtq);
     if (rc == LK_OK) rc = half_front(hu, false);
     if (rc == LK_OK) rc = half_solve(hu, false, nullptr);

@@ -143,9 +143,9 @@ namespace lk {
 // exact half-epoch for padded k <= 64: one wave per row (als_chol.hip)
 size_t als_chol_slab_floats(int NT);
 int als_chol_half_epoch(const lk_als_plan *p, const void *indptr, int is64, const int32_t *indices,
-                        const float *values, int64_t n_rows, int k, float *this_, int ld_this,
-                        const float *other, int ld_other, const float *otor, int ld_otor, char *ws,
-                        float *out_frob, hipStream_t st, bool expl, float reg);
+                        const float *values, int64_t n_rows, int64_t n_cols, int k, float *this_,
+                        int ld_this, const float *other, int ld_other, const float *otor,
+                        int ld_otor, char *ws, float *out_frob, hipStream_t st, bool expl, float reg);
 // exact half-epoch for padded k = 128 / 256: one workgroup per row (als_blk.hip)
 size_t als_blk_slab_floats(int NT);
 int als_blk_half_epoch(const lk_als_plan *p, const void *indptr, int is64, const int32_t *indices,

@@ -671,8 +671,8 @@ extern "C" int lk_als_implicit_half_epoch(const lk_als_plan *plan, const void *d
         return lk::als_blk_half_epoch(plan, d_indptr, plan->is64, d_indices, d_values, n_rows,
                                       n_cols, k, d_this, d_other, d_otor, ld_otor, ws, d_out_frob,
                                       st, false, 0.f);
-    return lk::als_chol_half_epoch(plan, d_indptr, plan->is64, d_indices, d_values, n_rows, k,
-                                   d_this, ld_this, d_other, ld_other, d_otor, ld_otor, ws,
+    return lk::als_chol_half_epoch(plan, d_indptr, plan->is64, d_indices, d_values, n_rows, n_cols,
+                                   k, d_this, ld_this, d_other, ld_other, d_otor, ld_otor, ws,
                                    d_out_frob, st, false, 0.f);
 }
 
@@ -736,9 +736,9 @@ extern "C" int lk_als_explicit_half_epoch(const lk_als_plan *plan, const void *d
         return lk::als_blk_half_epoch(plan, d_indptr, plan->is64, d_indices, d_values, n_rows,
                                       n_cols, k, d_this, d_other, nullptr, 0, ws, d_out_frob, st,
                                       true, reg);
-    return lk::als_chol_half_epoch(plan, d_indptr, plan->is64, d_indices, d_values, n_rows, k,
-                                   d_this, ld_this, d_other, ld_other, nullptr, 0, ws, d_out_frob,
-                                   st, true, reg);
+    return lk::als_chol_half_epoch(plan, d_indptr, plan->is64, d_indices, d_values, n_rows, n_cols,
+                                   k, d_this, ld_this, d_other, ld_other, nullptr, 0, ws,
+                                   d_out_frob, st, true, reg);
 }
 
 extern "C" int lk_als_check_status(const lk_als_plan *plan, void *d_ws, void *stream)

@@ -53,8 +53,10 @@ def main(path: str) -> int:
     # the three statements
     chunks = [r for r in ep if r["name"].startswith("als_chunk_kernel")]
     solves = [r for r in ep if r["name"].startswith("als_solve_kernel")]
-    long_ = [r for r in solves if r["name"].endswith("true, false>")]   # YREF launches
-    short_ = [r for r in solves if r["name"].endswith("false, true>")]  # SEQY launches
+    # als_solve_kernel<NT, IS64, EXPL, CTL, YREF, SEQY, ...>
+    targs = lambda r: [a.strip() for a in r["name"][r["name"].index("<") + 1:-1].split(",")]  # noqa: E731
+    long_ = [r for r in solves if targs(r)[4:6] == ["true", "false"]]   # YREF launches
+    short_ = [r for r in solves if targs(r)[4:6] == ["false", "true"]]  # SEQY launches
     gfin = [r for r in ep if r["name"].startswith("gramian_finish_kernel")]
     print()
     if len(chunks) == 2 and len(long_) == 2 and len(short_) == 2 and len(gfin) == 2:
