@@ -428,15 +428,6 @@ __device__ __forceinline__ void dma_apply(Gram<4> &G, const DmaOperand &o, const
     }
 }
 
-template <bool MASKED, bool SEQY = false, bool WITH_Y = true>
-__device__ __forceinline__ void dma_consume(Gram<4> &G, const float *ring, const int slot_idx,
-                                            const int g, const int nb, const float *stage_slot,
-                                            const bool expl, const DmaChain ch = DmaChain{})
-{
-    dma_apply<MASKED, SEQY, WITH_Y>(G, dma_fetch(ring, slot_idx, g, stage_slot), g, nb, expl,
-                                    slot_idx, ch);
-}
-
 template <int NT>
 __host__ __device__ constexpr int slab_floats();
 template <int NT, bool WITH_Y = true>
@@ -545,10 +536,14 @@ __device__ __forceinline__ void gram_accumulate_dma(Gram<4> &G, const int32_t *_
         rd_nxt = tr;
         yb ^= 64;
     }
-    // the last batches: wave-uniform guards, waits that shrink towards the end of the row
+    // the last batches: the same body -- no masks, operands one group ahead -- under wave-uniform
+    // guards (scalar compares and branches only), with waits that shrink towards the end of the
+    // row.  Only the row's LAST group can hold entries past the row's end: it alone is consumed
+    // masked, where its batch ends, its ring slot and staged words found by a run-time index.
     for (; g0 < total; base += 64, g0 += 16) {
         const int nb = (int)((end - base < 64) ? end - base : 64);
-        const bool more = g0 + 16 < total;  // another batch follows
+        const int rem = total - 1 - g0;     // groups of this batch in front of the row's last one
+        const bool more = g0 + 16 < total;  // another batch follows (then rem >= 16)
         int nxt_col = 0;
         float nxt_val = 0.f;
         if (more) {
@@ -557,30 +552,52 @@ __device__ __forceinline__ void gram_accumulate_dma(Gram<4> &G, const int32_t *_
             nxt_val = vals[e];
         }
         if constexpr (SEQY && WITH_Y) ch.v1 = v1s + yb;
+        DmaOperand cur{};
+        if (rem > 0) {
+            // group g0 has landed when only the groups issued after it are in flight
+            wait_vm_upto(rem < RING - 1 ? rem : RING - 1);
+            cur = dma_fetch(ring, 0, 0, rd_cur);
+        }
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
-            const int gg = g0 + g;
-            if (gg < total) {
-                const int later = total - 1 - gg;  // groups issued after this one
-                wait_vm_upto(later < RING - 1 ? later : RING - 1);
-                dma_consume<true, SEQY, WITH_Y>(G, ring, g % RING, g, nb, rd_cur, expl, ch);
-            }
-            if (g == 16 - RING - 2 && more) {
-                wr_nxt[0] = __builtin_bit_cast(float, nxt_col);
-                wr_nxt[64] = nxt_val;
-                if constexpr (SEQY && WITH_Y) {
-                    // (the value is waited for HERE, with the writes above: hoisted, the addition
-                    // would drain the memory queue groups earlier)
-                    asm volatile("" : "+v"(nxt_val));
-                    v1s[(yb ^ 64) + lane] = expl ? nxt_val : nxt_val + 1.0f;
+            if (g < rem) {
+                DmaOperand nxt = cur;
+                if (g + 1 < 16) {
+                    // (only the wait is guarded: where group g + 1 is the row's last one, which
+                    // is fetched again below, its slot is read for nothing -- one ds_read per
+                    // row against the five moves per group of a conditional `nxt`)
+                    if (g + 1 < rem) {
+                        const int later = rem - 1 - g;  // groups issued after group g + 1
+                        wait_vm_upto(later < RING - 2 ? later : RING - 2);
+                    }
+                    nxt = dma_fetch(ring, (g + 1) % RING, g + 1, rd_cur);
                 }
+                dma_apply<false, SEQY, WITH_Y>(G, cur, g, 64, expl, g % RING, ch);
+                if (g == 16 - RING - 2 && more) {
+                    wr_nxt[0] = __builtin_bit_cast(float, nxt_col);
+                    wr_nxt[64] = nxt_val;
+                    if constexpr (SEQY && WITH_Y) {
+                        // (the value is waited for HERE, with the writes above: hoisted, the
+                        // addition would drain the memory queue groups earlier)
+                        asm volatile("" : "+v"(nxt_val));
+                        v1s[(yb ^ 64) + lane] = expl ? nxt_val : nxt_val + 1.0f;
+                    }
+                }
+                if (g + RING <= rem) {  // group g0 + g + RING exists
+                    if (g < 16 - RING)
+                        dma_issue<WIDE>(ring_lds, g % RING, g + RING, rd_cur, other);
+                    else
+                        dma_issue<WIDE>(ring_lds, g % RING, g + RING - 16, rd_nxt, other);
+                }
+                cur = nxt;
+                __builtin_amdgcn_sched_barrier(0);
             }
-            if (gg + RING < total) {
-                if (g < 16 - RING)
-                    dma_issue<WIDE>(ring_lds, g % RING, g + RING, rd_cur, other);
-                else
-                    dma_issue<WIDE>(ring_lds, g % RING, g + RING - 16, rd_nxt, other);
-            }
+        }
+        if (rem < 16) {  // the row ends in this batch: nothing is in flight behind its last group
+            const int slot_idx = rem & (RING - 1);
+            wait_vm<0>();
+            dma_apply<true, SEQY, WITH_Y>(G, dma_fetch(ring, slot_idx, rem, rd_cur), rem, nb, expl,
+                                          slot_idx, ch);
         }
         if (slab && ((g0 + 16) & 63) == 0 && g0 + 16 < total) {  // a block boundary, more follows
             slab_store<4, WITH_Y>(G, slab);
@@ -601,7 +618,8 @@ __device__ __forceinline__ void gram_accumulate_dma(Gram<4> &G, const int32_t *_
 // Reference-order rows are cut into matrixmultiply's KC = 256 blocks (als_plan.h): every chunk of
 // such a row but its last has exactly 256 entries = 64 groups = 4 batches.  The general routine
 // above sends the last batch of any range down its guarded path (wave-uniform tests, waits that
-// shrink); for a 256-entry chunk that is a quarter of the work.  Here the batch loop is unrolled
+// shrink, the last group masked); for a 256-entry chunk that is a quarter of the work.  Here the
+// batch loop is unrolled
 // over the four batches, so every guard and every wait count is a compile-time constant.  Same
 // operations in the same order: bit-identical to gram_accumulate_dma on the same range.
 template <bool WITH_Y = true, int RING = DMA_RING, bool WIDE = true>
