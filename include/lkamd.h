@@ -693,6 +693,41 @@ int lk_uknn_score_panel(const int64_t *d_t_indptr, const int32_t *d_t_users,
                         const int32_t *d_hist_items, int mark_history, void *d_ws, float *d_out,
                         int64_t ld_out, void *stream);
 
+/* ------------------------------------------------------------------------
+ * User-kNN scores for the (query, target) PAIRS of a predict call (csrc/uknn_predict.hip).
+ * Replaces, for a whole batch, `UserKNNScorer.__call__`'s scoring of the items it is asked for
+ * (src/lenskit/knn/user.py:171-262), `user_score_items_explicit / _implicit`
+ * (src/accel/knn/user_score.rs:21-98) and their `ScoreAccumulator` (src/accel/knn/accum.rs).
+ * Query q of n_queries asks for the items d_tgt_items[d_tgt_ptr[q] .. d_tgt_ptr[q + 1]) (int64
+ * offsets, ABSOLUTE entry numbers: d_tgt_ptr may be a slice of a longer array; a negative item
+ * or one >= n_items is unknown); only entries in [first_entry, first_entry + n_entries) are read
+ * and written.  d_out[entry] is what lk_uknn_score_panel writes into cell (q, item), bit for
+ * bit: the item's row of the TRANSPOSED centred ratings (items x users, int64 offsets, users
+ * ascending; d_t_values NULL = implicit feedback) walked in stored order, every rater u with
+ * d_sims[q][u] >= thr (a NaN fails) offering (similarity, rating) to the cell's own accumulator
+ * of max_nbrs entries, then sum(w * v) / sum(w) + d_offset[q] (explicit; d_offset NULL = 0) or
+ * sum(w) (implicit), sequential f32 sums in the accumulator's final array order, the product
+ * rounded before it is added; fewer than min_nbrs entries, none, or an unknown item: NaN.
+ * d_sims: sims_user_major != 0: [n_users x ld_sims], ld_sims >= n_queries (lk_uknn_sims_panel's
+ * output); 0: [n_queries x ld_sims], ld_sims >= n_users (lk_csr_rows_dot's).  d_self_user (may be
+ * NULL) [n_queries]: the query's own user, -1 = none; that rater never passes (user.py:192-194
+ * zeroes its similarity, and min_sim is positive), so the panel need not be touched.  max_col_len as for lk_uknn_score_panel.  Workspace:
+ * lk_uknn_score_pairs_workspace_bytes(max_nbrs, max_col_len) -- 0 (d_ws may be NULL) while
+ * min(max_nbrs, max_col_len) <= lk_uknn_score_pairs_lds_max_nbrs(), the accumulators then live
+ * in LDS; above, in per-wave slabs of the workspace.  Every max_nbrs >= 1 is taken.  No atomics:
+ * the same inputs give the same bits.  Asynchronous on `stream`.
+ * ---------------------------------------------------------------------- */
+int32_t lk_uknn_score_pairs_lds_max_nbrs(void);
+size_t lk_uknn_score_pairs_workspace_bytes(int32_t max_nbrs, int64_t max_col_len);
+int lk_uknn_score_pairs(const int64_t *d_t_indptr, const int32_t *d_t_users,
+                        const float *d_t_values, int64_t n_items, int64_t n_users,
+                        int64_t max_col_len, const float *d_sims, int64_t ld_sims,
+                        int sims_user_major, int64_t n_queries, const int32_t *d_self_user,
+                        const int64_t *d_tgt_ptr,
+                        const int32_t *d_tgt_items, int64_t first_entry, int64_t n_entries,
+                        float thr, int32_t max_nbrs, int32_t min_nbrs, const float *d_offset,
+                        void *d_ws, float *d_out, void *stream);
+
 /* Device -> pageable host memory at PCIe speed: chunks through a ring of pinned staging slots,
  * a team of `n_threads` host threads (<= 14; 0 = 8) copies the landed chunks to `h_dst` in
  * parallel (first-touching its pages on many cores).  Used for results the reference hands

@@ -1260,6 +1260,78 @@ def uknn_score_panel(ratings_t: DeviceCSR, sims: torch.Tensor, queries: int, thr
     return out
 
 
+def uknn_pairs_lds_max_nbrs() -> int:
+    "The largest ``max_nbrs`` whose accumulators ``lk_uknn_score_pairs`` keeps in LDS."
+    return int(_native.load().lk_uknn_score_pairs_lds_max_nbrs())
+
+
+def uknn_score_pairs(ratings_t: DeviceCSR, sims: torch.Tensor, tgt_ptr: torch.Tensor,
+                     tgt_items: torch.Tensor, thr: float, max_nbrs: int, min_nbrs: int,
+                     offset: torch.Tensor | None = None, *,
+                     self_user: torch.Tensor | None = None, user_major: bool = False,
+                     entries: tuple[int, int] | None = None, max_col: int | None = None,
+                     out: torch.Tensor | None = None) -> torch.Tensor:
+    """
+    User-kNN scores of ragged (query, target) pairs (lk_uknn_score_pairs): what
+    :func:`uknn_score_panel` writes into those cells, bit for bit.  ``ratings_t``: the transposed
+    centred ratings (items x users, int64 offsets, users ascending; ``values`` None = implicit
+    feedback); ``sims``: the query-major similarities [P x users] of :func:`csr_rows_dot`, or
+    with ``user_major`` the panel [users x ld] of :func:`uknn_sims_panel` (its first P columns);
+    ``tgt_ptr``: device int64 [P + 1], ABSOLUTE offsets into ``tgt_items`` (device int32, -1 =
+    unknown item) -- a slice of a longer offset array is fine; ``thr``: the float32 ``min_sim``;
+    ``offset``: device f32 per query, added to explicit scores; ``self_user``: device int32 per
+    query (-1 = none), the rater that never passes.  ``entries = (lo, hi)``: the entries the
+    ``P`` queries cover, when the caller knows them (else all of ``tgt_items``: only the launch
+    is sized by it).  ``max_col``: the longest column (read from the device when not given).
+    Returns ``out`` (f32, one score per entry of ``tgt_items``; NaN = cannot be scored); only
+    the entries of the ``P`` queries are written.
+    """
+    lib = _native.require_gpu()
+    n_items, n_users = ratings_t.shape
+    dev = sims.device
+    P = int(tgt_ptr.shape[0]) - 1
+    total = int(tgt_items.shape[0])
+    assert ratings_t.indptr.dtype == torch.int64 and ratings_t.indptr.is_contiguous()
+    assert ratings_t.indices.dtype == torch.int32 and ratings_t.indices.device == dev
+    assert ratings_t.values is None or (ratings_t.values.dtype == torch.float32 and
+                                        ratings_t.values.is_contiguous())
+    assert sims.dtype == torch.float32 and sims.is_contiguous() and sims.dim() == 2
+    if user_major:
+        assert P >= 0 and sims.shape[0] == n_users and sims.shape[1] >= P
+    else:
+        assert P >= 0 and sims.shape[0] >= P and sims.shape[1] >= n_users
+    assert tgt_ptr.dtype == torch.int64 and tgt_ptr.is_contiguous() and tgt_ptr.device == dev
+    assert tgt_items.dtype == torch.int32 and tgt_items.is_contiguous()
+    assert tgt_items.device == dev
+    if offset is not None:
+        assert offset.dtype == torch.float32 and offset.is_contiguous() and offset.numel() == P
+        assert offset.device == dev
+    if self_user is not None:
+        assert self_user.dtype == torch.int32 and self_user.is_contiguous()
+        assert self_user.numel() == P and self_user.device == dev
+    lo, hi = (0, total) if entries is None else (int(entries[0]), int(entries[1]))
+    assert 0 <= lo <= hi <= total
+    if out is None:
+        out = torch.empty(total, dtype=torch.float32, device=dev)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == total
+    assert out.device == dev
+    if max_col is None:
+        max_col = int(torch.diff(ratings_t.indptr).max()) if n_items else 0
+    wb = lib.lk_uknn_score_pairs_workspace_bytes(int(max_nbrs), int(max_col))
+    ws = torch.empty(wb, dtype=torch.uint8, device=dev) if wb else None
+    check(
+        lib.lk_uknn_score_pairs(_ptr(ratings_t.indptr), _ptr(ratings_t.indices),
+                                _ptr(ratings_t.values), n_items, n_users, int(max_col),
+                                _ptr(sims), int(sims.shape[1]), 1 if user_major else 0, P,
+                                _ptr(self_user),
+                                _ptr(tgt_ptr), _ptr(tgt_items), lo, hi - lo, float(thr),
+                                int(max_nbrs), int(min_nbrs), _ptr(offset), _ptr(ws), _ptr(out),
+                                _stream()),
+        "lk_uknn_score_pairs",
+    )
+    return out
+
+
 def ease_gram(cooc: DeviceCSR, item_counts: torch.Tensor, reg: float) -> torch.Tensor:
     """
     ``X^T X + reg I`` as a dense [n x n] f32 device matrix (lk_ease_gram) from the off-diagonal

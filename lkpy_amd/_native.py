@@ -210,6 +210,13 @@ def _declare(lib):
             [vp, vp, vp, c_int64, c_int64, c_int64, vp, vp, c_int64, c_int64, c_float, c_int32,
              c_int32, vp, vp, vp, c_int, vp, vp, c_int64, vp],
         ),
+        "lk_uknn_score_pairs_lds_max_nbrs": (c_int32, []),
+        "lk_uknn_score_pairs_workspace_bytes": (c_size_t, [c_int32, c_int64]),
+        "lk_uknn_score_pairs": (
+            c_int,
+            [vp, vp, vp, c_int64, c_int64, c_int64, vp, c_int64, c_int, c_int64, vp, vp, vp,
+             c_int64, c_int64, c_float, c_int32, c_int32, vp, vp, vp, vp],
+        ),
         "lk_download": (c_int, [vp, vp, c_size_t, c_int32, vp]),
         "lk_download_warmup": (c_int, []),
         "lk_download_i32_narrow": (c_int, [vp, vp, c_int64, vp, c_int32, vp]),

@@ -290,11 +290,11 @@ def predict(pipe: Pipeline, pairs, *, batch_size: int = 16384) -> ItemListCollec
     columns (users in order of first appearance, rows in order within a user; the other columns
     become fields of the lists).
 
-    An item-kNN or a biased-MF (``BiasedMFScorer``) pipeline (``std:topn-predict`` with its
-    ``BiasScorer`` fallback, or without a fallback) whose vocabularies agree is run as whole
-    batches by user number (:func:`_predict_batched`): the lists are the per-query composition's
-    bit for bit (float32 of it where the biased-MF scorer alone hands out float64).  Every other
-    pipeline runs query by query.
+    An item-kNN, a user-kNN or a biased-MF (``BiasedMFScorer``) pipeline (``std:topn-predict``
+    with its ``BiasScorer`` fallback, or without a fallback) whose vocabularies agree is run as
+    whole batches by user number (:func:`_predict_batched`): the lists are the per-query
+    composition's bit for bit (float32 of it where the biased-MF scorer alone hands out float64).
+    Every other pipeline runs query by query.
     """
     keys, offsets, item_ids, fields, lists = _ragged_pairs(pairs)
     parts = _batched_predict_parts(pipe)
@@ -354,16 +354,20 @@ def _ragged_pairs(pairs):
 
 def _batched_predict_parts(pipe: Pipeline):
     """(scorer, lookup, BiasScorer or None) when ``rating-predictor`` can run by user number:
-    an ``ItemKNNScorer`` or a ``BiasedMFScorer``, a lookup with ``batch``, no merger or a
-    ``FallbackScorer`` over a ``BiasScorer``, and one item (and user) vocabulary throughout; None
-    otherwise."""
+    an ``ItemKNNScorer``, a ``UserKNNScorer`` or a ``BiasedMFScorer``, a lookup with ``batch``, no
+    merger or a ``FallbackScorer`` over a ``BiasScorer``, and one item (and user) vocabulary
+    throughout; None otherwise.  A ``UserKNNScorer`` must share the lookup's USER vocabulary too
+    (a known user is then always scored from the looked-up history, never from the stored
+    vector), and with explicit feedback the dataset must have ratings (without, the per-query
+    path answers NaN, and goes on doing so through the loop)."""
     from .als import BiasedMFScorer
     from .basic import BiasScorer, FallbackScorer
-    from .knn import ItemKNNScorer
+    from .knn import ItemKNNScorer, UserKNNScorer
 
     scorer = pipe.node("scorer").component
     lookup = pipe.node("history-lookup").component
-    if not isinstance(scorer, (ItemKNNScorer, BiasedMFScorer)) or not hasattr(lookup, "batch") \
+    if not isinstance(scorer, (ItemKNNScorer, UserKNNScorer, BiasedMFScorer)) \
+            or not hasattr(lookup, "batch") \
             or getattr(lookup, "interactions", None) is None:
         return None
     ds = lookup.interactions._ds
@@ -377,6 +381,12 @@ def _batched_predict_parts(pipe: Pipeline):
                 rating is None or not same(scorer.items, ds.items) or \
                 (scorer.users is not None and not same(scorer.users, ds.users)):
             return None
+    elif isinstance(scorer, UserKNNScorer):
+        if not scorer.is_trained() or not same(scorer.items, ds.items) or \
+                not same(scorer.users, ds.users):
+            return None
+        if scorer.config.explicit and rating is None:
+            return None  # (the per-query path answers NaN)
     else:
         if not scorer.is_trained() or not same(scorer.items, ds.items):
             return None
@@ -411,7 +421,10 @@ def _predict_batched(parts, keys, offsets, item_ids, fields, batch_size: int):
 
     A ``BiasedMFScorer`` scores by ``predict_history_batch`` (fold-in, ``lk_score_dense``,
     ``lk_bmf_finish_pairs``), has no item means to add back and no ``nbr_counts``; its fallback
-    is the same merge.
+    is the same merge.  So does a ``UserKNNScorer`` (``lk_uknn_query_panel``,
+    ``lk_uknn_sims_panel``, ``lk_uknn_score_pairs``): its scores carry the history's centre
+    already, the per-query lists have no ``nbr_counts``, and without a fallback there is no merge
+    call.
     """
     import torch
 
@@ -426,7 +439,7 @@ def _predict_batched(parts, keys, offsets, item_ids, fields, batch_size: int):
     nums = scorer.items.numbers(item_ids, missing="negative") if len(item_ids) else \
         np.zeros(0, np.int32)
     total = int(offsets[-1])
-    knn = hasattr(scorer, "score_history_batch")  # (else: BiasedMFScorer)
+    knn = hasattr(scorer, "score_history_batch")  # (else: BiasedMFScorer, UserKNNScorer)
     scores = np.empty(total, np.float32)
     counts = np.empty(total, np.int32) if knn else None
     fb = np.empty(total, np.bool_) if bias is not None else None

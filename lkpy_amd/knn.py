@@ -15,6 +15,8 @@ User-based k-NN scores candidate lists through ``lk_csr_rows_dot`` + ``lk_uknn_s
 (``recommend_batch`` / ``dense_scores_batch``, the loops of :class:`_PanelScorer`): the query
 vectors built on the device, the neighbour similarities user-major, and each (query, item) cell a
 gather from the transposed ratings into the reference's accumulator.
+``batch.predict`` scores its ragged (query, target) cells by the same gather
+(``predict_history_batch``, csrc/uknn_predict.hip).
 ``batch.recommend`` takes that path, as it takes item-kNN's, SLIM's, the association rules' and
 EASE's (``lk_ease_score_panel``; EASE's training can invert its Gramian with this package's blocked
 Cholesky, ``lk_spd_inverse_blocked``: DESIGN.md section 4.25).
@@ -408,6 +410,8 @@ class UserKNNScorer(_PanelScorer, Component):
     (``lk_uknn_query_panel``), the similarities come user-major (``lk_uknn_sims_panel``), and
     each (query, item) cell gathers the item's raters from the transposed ratings into its own
     accumulator (``lk_uknn_score_panel``) -- the bits ``score_batch`` gives the same query.
+    ``predict_history_batch`` scores the ragged targets of ``batch.predict`` the same way, only
+    the (query, target) cells that are asked for (``lk_uknn_score_pairs``, csrc/uknn_predict.hip).
     """
 
     PANEL_BYTES = 1 << 30  # the query, similarity and score panels of one step, together
@@ -669,6 +673,39 @@ class UserKNNScorer(_PanelScorer, Component):
         ranked.  Returns (item numbers [B x n] with -1 padding, scores [B x n] with NaN padding).
         """
         return super().recommend_batch(queries, n, exclude_history=exclude_history)
+
+    def predict_history_batch(self, hb, d_tgt_ptr, d_tgt_items, *, h_tgt_ptr=None):
+        """
+        Scores for the ragged targets of a :class:`lkpy_amd.basic.HistoryBatch` -- what
+        ``batch.predict`` asks for -- left on the device: float32, one per entry of
+        ``d_tgt_items`` (device int32 item numbers, -1 = unknown; ``d_tgt_ptr`` device int64
+        offsets per query), the history's centre added back for explicit feedback, NaN where
+        :meth:`__call__` answers NaN (unknown item, fewer than ``min_nbrs`` passing raters, a
+        query without history).  Nothing is done per query on the host: the query vectors are
+        built on the device (``lk_uknn_query_panel``), the similarities as a user-major panel
+        (``lk_uknn_sims_panel``) and ``lk_uknn_score_pairs`` gathers each (query, target) cell from
+        the transposed ratings -- the cell ``lk_uknn_score_panel`` would write, only those asked
+        for.  The batch goes through in steps of :meth:`_panel_rows` queries.  ``h_tgt_ptr``: the
+        host copy of the offsets, if the caller has one (it sizes each step's launch).
+        """
+        st, tr = self._device_state(), self._device_transposed()
+        hist = self._batch_csr(hb)
+        B = hist.shape[0]
+        out = torch.empty(int(d_tgt_items.shape[0]), dtype=torch.float32, device=st["device"])
+        thr = float(np.float32(self.config.min_sim))
+        step = self._panel_rows()
+        for lo in range(0, B, step):
+            hi = min(B, lo + step)
+            x = D.uknn_query_panel(hist, hist.centre, rows=(lo, hi))
+            sims = D.uknn_sims_panel(st["vectors"], x, hist.self_user[lo:hi])
+            del x
+            D.uknn_score_pairs(
+                tr["ratings_t"], sims, d_tgt_ptr[lo:hi + 1], d_tgt_items, thr,
+                self.config.max_nbrs, self.config.min_nbrs,
+                None if hist.centre is None else hist.centre[lo:hi],
+                self_user=hist.self_user[lo:hi], user_major=True, max_col=tr["max_col"], out=out,
+                entries=None if h_tgt_ptr is None else (int(h_tgt_ptr[lo]), int(h_tgt_ptr[hi])))
+        return out
 
     def dense_scores_batch(self, queries):
         """
