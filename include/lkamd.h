@@ -1238,6 +1238,51 @@ int lk_mf_score_pairs(const float *d_users, int32_t ld_users, int64_t n_users,
                       const int32_t *d_tgt_items, int64_t total, float *d_out, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Per-query candidate lists (csrc/candidates.hip): scoring and ranking "these items for this
+ * query" for a batch -- `BatchRecRequest.candidates` (src/lenskit/batch/_queries.py:50-78),
+ * `pipe.run("recommender", query=, items=, n=)` and `BatchPipelineRunner.score`
+ * (src/lenskit/batch/_runner.py:114-124).  One ragged layout throughout: d_tgt_ptr int64
+ * [n_queries + 1] ascending from 0 to total, d_tgt_items int32 [total]; the caller validates the
+ * offsets on the host, the kernels clamp them and range-check every item number and user row
+ * before it becomes an address.  No atomics; a result depends on its own query alone.
+ *
+ * lk_score_candidates: the signature and operands of lk_mf_score_pairs (leading dimensions
+ *   multiples of 4 floats covering k rounded up to 4, bases 16-byte aligned, k in 1..1024), but
+ *   d_out[t] is the SINGLE chain acc = 0; for f = 0 .. k-1: acc = fmaf(u[f], q[f], acc) -- the
+ *   chain of lk_score_dense / lk_score_topk, so d_out[t] has the bits of that panel's entry
+ *   (user row, item) for every k.  A user row or an item outside its table (-1: unknown) gives
+ *   NaN.  total = 0 returns without a launch.
+ * lk_panel_take_ragged: d_out[t] = d_panel[q * ld + d_tgt_items[t]] for t in query q's range (NaN
+ *   for an item outside [0, n_items)): lk_take_scores for ragged targets, the bridge from any
+ *   [n_queries x ld] score panel.
+ * lk_ragged_topn: lk_argtopn applied to every segment of d_scores f32 [total]: entries with a NaN
+ *   score or a negative item number are dropped, the rest descend in the order of the selection
+ *   kernel's keys (-0.0 ties with +0.0, +-inf are valid), ties go to the lower position in the
+ *   segment; repeated item numbers are separate entries.  d_out_idx int32 / d_out_score f32
+ *   [n_queries x width]: item NUMBERS and the input scores' own bits, padded with -1 / NaN.
+ *   width = n, or with n < 0 width = max_len and every valid entry is ranked.  max_len: the
+ *   longest segment, from the caller's host copy of the offsets (a segment longer than that is
+ *   not ranked).  Segments of at most lk_ragged_topn_wave_max() (64) entries take one wave, up to
+ *   lk_ragged_topn_block_max() (1024) one workgroup with the keys in LDS; when max_len is larger
+ *   the batch is sorted once (stable radix sort of (query, key)) and the long segments are
+ *   emitted from that -- d_ws then needs lk_ragged_topn_workspace_bytes(total, max_len) bytes
+ *   (0 otherwise).  total < 2^31 per call; no other limit on n or the segment length.
+ * ---------------------------------------------------------------------- */
+int lk_score_candidates(const float *d_users, int32_t ld_users, int64_t n_users,
+                        const float *d_items, int32_t ld_items, int64_t n_items, int32_t k,
+                        const int32_t *d_user_rows, int64_t n_queries, const int64_t *d_tgt_ptr,
+                        const int32_t *d_tgt_items, int64_t total, float *d_out, void *stream);
+int lk_panel_take_ragged(const float *d_panel, int64_t n_queries, int64_t n_items, int64_t ld,
+                         const int64_t *d_tgt_ptr, const int32_t *d_tgt_items, int64_t total,
+                         float *d_out, void *stream);
+int32_t lk_ragged_topn_wave_max(void);
+int32_t lk_ragged_topn_block_max(void);
+size_t lk_ragged_topn_workspace_bytes(int64_t total, int64_t max_len);
+int lk_ragged_topn(int64_t n_queries, const int64_t *d_tgt_ptr, const int32_t *d_tgt_items,
+                   const float *d_scores, int64_t total, int32_t n, int64_t max_len, void *d_ws,
+                   int32_t *d_out_idx, float *d_out_score, void *stream);
+
+/* ------------------------------------------------------------------------
  * Stochastic top-N ranking (csrc/stochastic.hip): the sort keys of
  * `StochasticTopNRanker._compute_keys` (src/lenskit/stochastic/_ranker.py:119-156) for a panel
  * of score rows; lk_argtopn of a key row is one Plackett-Luce sample, lk_take_scores its keys

@@ -863,6 +863,9 @@ def iknn_score_batch(sims: DeviceCSR, ref_ptr, ref_items, ref_rates, tgt_ptr, tg
     nq = int(ref_ptr.shape[0]) - 1
     dev = sims.indices.device
     assert sims.indptr.dtype == torch.int64
+    if int(tgt_items.shape[0]) == 0:  # (empty target lists only: an empty tensor has no address)
+        return (torch.empty(0, dtype=torch.float32, device=dev),
+                torch.empty(0, dtype=torch.int32, device=dev))
     ws = torch.empty(lib.lk_iknn_score_workspace_bytes(n_items, nq, int(max_nbrs)),
                      dtype=torch.uint8, device=dev)
     out_s = torch.empty(int(tgt_items.shape[0]), dtype=torch.float32, device=dev)
@@ -2517,6 +2520,119 @@ def mf_score_pairs(users: torch.Tensor, items: torch.Tensor, k: int, user_rows: 
                                 user_rows.numel(), _ptr(tgt_ptr), _ptr(tgt_items),
                                 tgt_items.numel(), _ptr(out), _stream()), "lk_mf_score_pairs")
     return out
+
+
+# ---- per-query candidate lists (csrc/candidates.hip) ----------------------------------------
+def check_ragged(h_tgt_ptr, n_queries: int, total: int) -> np.ndarray:
+    """
+    The host copy of a batch's target offsets, validated before anything is launched: int64, one
+    per query and one more, ascending from 0 to ``total``.  Raises ``ValueError`` otherwise.
+    """
+    ptr = np.ascontiguousarray(h_tgt_ptr, dtype=np.int64).reshape(-1)
+    if len(ptr) != n_queries + 1 or ptr[0] != 0 or ptr[-1] != total or (np.diff(ptr) < 0).any():
+        raise ValueError("tgt_ptr must ascend from 0 to len(tgt_items), one entry per query and "
+                         "one more")
+    return ptr
+
+
+def upload_targets(h_tgt_ptr: np.ndarray, item_nums: np.ndarray, dev):
+    """
+    The ragged targets of a batch in ONE upload: (device int64 offsets [B + 1], device int32 item
+    numbers [total]), views of one packed tensor.  ``h_tgt_ptr`` is validated first.
+    """
+    item_nums = np.ascontiguousarray(item_nums, dtype=np.int32).reshape(-1)
+    n = len(item_nums)
+    ptr = check_ragged(h_tgt_ptr, len(np.reshape(h_tgt_ptr, -1)) - 1, n)
+    head = 2 * len(ptr)
+    packed = np.empty(head + n, np.int32)
+    packed[:head] = ptr.view(np.int32)
+    packed[head:] = item_nums
+    d_packed = torch.from_numpy(packed).to(dev)
+    return d_packed[:head].view(torch.int64), d_packed[head:]
+
+
+def _ragged_args(h_tgt_ptr, tgt_ptr: torch.Tensor, tgt_items: torch.Tensor) -> np.ndarray:
+    assert tgt_ptr.dtype == torch.int64 and tgt_ptr.is_contiguous() and tgt_ptr.dim() == 1
+    assert tgt_items.dtype == torch.int32 and tgt_items.is_contiguous() and tgt_items.dim() == 1
+    if tgt_items.numel() >= 2 ** 31:
+        raise ValueError("more than 2^31 targets in one call")
+    return check_ragged(h_tgt_ptr, tgt_ptr.numel() - 1, tgt_items.numel())
+
+
+def score_candidates(users: torch.Tensor, items: torch.Tensor, k: int, user_rows: torch.Tensor,
+                     tgt_ptr: torch.Tensor, tgt_items: torch.Tensor, h_tgt_ptr) -> torch.Tensor:
+    """
+    Ragged pair scores as the k-ordered chain of :func:`score_dense` (lk_score_candidates): the
+    arguments of :func:`mf_score_pairs` plus ``h_tgt_ptr``, the host copy of the offsets, which is
+    validated before the launch.  Returns f32 [len(tgt_items)] on the device: entry t has the bits
+    of ``score_dense(users, items, k)[user_rows[q], tgt_items[t]]``, NaN where the user row or the
+    item is outside its table.
+    """
+    lib = _native.require_gpu()
+    assert users.dtype == torch.float32 and users.is_contiguous() and users.dim() == 2
+    assert items.dtype == torch.float32 and items.is_contiguous() and items.dim() == 2
+    assert user_rows.dtype == torch.int32 and user_rows.is_contiguous()
+    assert tgt_ptr.numel() == user_rows.numel() + 1
+    _ragged_args(h_tgt_ptr, tgt_ptr, tgt_items)
+    out = torch.empty(tgt_items.numel(), dtype=torch.float32, device=users.device)
+    check(lib.lk_score_candidates(_ptr(users), users.shape[1], users.shape[0], _ptr(items),
+                                  items.shape[1], items.shape[0], int(k), _ptr(user_rows),
+                                  user_rows.numel(), _ptr(tgt_ptr), _ptr(tgt_items),
+                                  tgt_items.numel(), _ptr(out), _stream()), "lk_score_candidates")
+    return out
+
+
+def panel_take_ragged(panel: torch.Tensor, n_items: int, tgt_ptr: torch.Tensor,
+                      tgt_items: torch.Tensor, h_tgt_ptr) -> torch.Tensor:
+    """
+    ``panel[q, tgt_items[t]]`` for every t of query q's range (lk_panel_take_ragged): ``panel`` a
+    device f32 [queries x ld] score panel of which ``n_items`` columns are items.  Returns f32
+    [len(tgt_items)] on the device, NaN for an item outside ``[0, n_items)``.
+    """
+    lib = _native.require_gpu()
+    assert panel.dtype == torch.float32 and panel.dim() == 2 and panel.stride(1) == 1
+    assert panel.shape[0] == tgt_ptr.numel() - 1 and panel.shape[1] >= n_items
+    _ragged_args(h_tgt_ptr, tgt_ptr, tgt_items)
+    out = torch.empty(tgt_items.numel(), dtype=torch.float32, device=panel.device)
+    check(lib.lk_panel_take_ragged(_ptr(panel), panel.shape[0], int(n_items), panel.stride(0),
+                                   _ptr(tgt_ptr), _ptr(tgt_items), tgt_items.numel(), _ptr(out),
+                                   _stream()), "lk_panel_take_ragged")
+    return out
+
+
+def ragged_topn_classes() -> tuple[int, int]:
+    """The longest segment :func:`ragged_topn` ranks in one wave, and in one workgroup
+    (lk_ragged_topn_wave_max, lk_ragged_topn_block_max); longer ones are sorted."""
+    lib = _native.load()
+    return int(lib.lk_ragged_topn_wave_max()), int(lib.lk_ragged_topn_block_max())
+
+
+def ragged_topn(tgt_ptr: torch.Tensor, tgt_items: torch.Tensor, scores: torch.Tensor, n: int,
+                h_tgt_ptr):
+    """
+    :func:`argtopn` per segment of ragged scores (lk_ragged_topn): (item numbers int32
+    [queries x width] padded with -1, scores f32 [queries x width] padded with NaN) on the
+    device, ``width = n`` or, with ``n < 0``, the longest segment.  NaN scores and negative item
+    numbers are dropped; ties go to the lower position; the scores are the input's own bits.
+    """
+    lib = _native.require_gpu()
+    assert scores.dtype == torch.float32 and scores.is_contiguous()
+    assert scores.numel() == tgt_items.numel()
+    ptr = _ragged_args(h_tgt_ptr, tgt_ptr, tgt_items)
+    nq, total = len(ptr) - 1, tgt_items.numel()
+    max_len = int(np.diff(ptr).max()) if nq else 0
+    n = int(n)
+    width = max_len if n < 0 else n
+    idx = torch.empty((nq, width), dtype=torch.int32, device=scores.device)
+    out = torch.empty((nq, width), dtype=torch.float32, device=scores.device)
+    if nq == 0 or width == 0:
+        return idx, out
+    wb = lib.lk_ragged_topn_workspace_bytes(total, max_len)
+    ws = torch.empty(wb, dtype=torch.uint8, device=scores.device) if wb else None
+    check(lib.lk_ragged_topn(nq, _ptr(tgt_ptr), _ptr(tgt_items), _ptr(scores), total,
+                             n if n >= 0 else -1, max_len, _ptr(ws), _ptr(idx), _ptr(out),
+                             _stream()), "lk_ragged_topn")
+    return idx, out
 
 
 # ---- randomized truncated SVD (csrc/svd.hip) ------------------------------------------------

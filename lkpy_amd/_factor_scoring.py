@@ -108,6 +108,24 @@ class BiasedFactorScoring:
         D.blank_panel_rows(panel, valid)
         return panel, valid, hist
 
+    def score_candidates_batch(self, queries, tgt_ptr, item_nums, *, d_targets=None):
+        """
+        The scores of each query's OWN items, left on the device: f32 [total], entry t the score
+        ``__call__`` gives item ``item_nums[t]`` for the query q with ``tgt_ptr[q] <= t <
+        tgt_ptr[q + 1]`` -- the same bits, from :meth:`_query_rows` and the dense chain evaluated
+        at the targets only (``lk_score_candidates``): no panel is formed.  ``queries``: a list of
+        queries or a :class:`lkpy_amd.basic.HistoryBatch`; ``tgt_ptr`` int64 [B + 1] and
+        ``item_nums`` int32 (-1: unknown item) are host arrays, ``d_targets`` their device copies
+        ``(offsets, numbers)`` where the caller has uploaded them already.  NaN for an unknown
+        item and for an unknown user.
+        """
+        u, valid = self._query_rows(resolve_queries(queries, self.items))
+        st = self._device_state()
+        d_ptr, d_nums = d_targets or D.upload_targets(tgt_ptr, item_nums, st["device"])
+        rows = np.where(valid, np.arange(len(valid)), -1).astype(np.int32)
+        return D.score_candidates(u, st["Q"], self._score_k,
+                                  torch.from_numpy(rows).to(st["device"]), d_ptr, d_nums, tgt_ptr)
+
 
 class GlobalBiasPairScoring(BiasedFactorScoring):
     """
@@ -155,6 +173,20 @@ class GlobalBiasPairScoring(BiasedFactorScoring):
                                d_packed[:2 * (nq + 1)].view(torch.int64),
                                d_packed[2 * (nq + 1) + nq:])
         return out if device_output else out.cpu().numpy()
+
+    def score_candidates_batch(self, queries, tgt_ptr, item_nums, *, d_targets=None):
+        """
+        The scores of each query's OWN items, left on the device (f32 [total]; the contract of
+        ``BiasedFactorScoring.score_candidates_batch``).  ``__call__`` is defined by
+        ``lk_mf_score_pairs`` here, so this is ``_score_rows(device_output=True)`` on the operand
+        rows ``__call__`` takes (:meth:`_query_rows`): a candidate ranking made from these scores
+        carries the bits of ``__call__``, which are NOT those of ``lk_score_topk`` (the whole-
+        catalogue ``recommend_batch``: the k-ordered chain, not per-lane partial sums).
+        ``_score_rows`` packs and uploads the targets itself; ``d_targets`` is not used.
+        """
+        u, valid = self._query_rows(resolve_queries(queries, self.items))
+        return self._score_rows(u, np.where(valid, np.arange(len(valid)), -1), tgt_ptr, item_nums,
+                                True)
 
     def score_pairs(self, user_nums, tgt_ptr, item_nums, *, device_output: bool = False):
         "Scores by number: ``_score_rows`` with the users' stored operand rows."

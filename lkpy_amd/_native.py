@@ -328,6 +328,17 @@ def _declare(lib):
             c_int, [vp, c_int32, c_int64, vp, c_int32, c_int64, c_int32, vp, c_int64, vp, vp,
                     c_int64, vp, vp]
         ),
+        "lk_score_candidates": (
+            c_int, [vp, c_int32, c_int64, vp, c_int32, c_int64, c_int32, vp, c_int64, vp, vp,
+                    c_int64, vp, vp]
+        ),
+        "lk_panel_take_ragged": (c_int, [vp, c_int64, c_int64, c_int64, vp, vp, c_int64, vp, vp]),
+        "lk_ragged_topn_wave_max": (c_int32, []),
+        "lk_ragged_topn_block_max": (c_int32, []),
+        "lk_ragged_topn_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+        "lk_ragged_topn": (
+            c_int, [c_int64, vp, vp, vp, c_int64, c_int32, c_int64, vp, vp, vp, vp]
+        ),
         "lk_stochastic_row_stats": (
             c_int, [vp, c_int64, c_int64, c_int64, vp, vp, c_int32, c_float, vp, vp]
         ),

@@ -333,6 +333,27 @@ class ImplicitMFScorer(UsesTrainer, Component):
         D.blank_panel_rows(panel, valid)
         return panel, valid, hist
 
+    def score_candidates_batch(self, queries, tgt_ptr, item_nums, *, d_targets=None):
+        """
+        The scores of each query's OWN items, left on the device: f32 [total], entry t the score
+        ``__call__`` gives item ``item_nums[t]`` for the query q with ``tgt_ptr[q] <= t <
+        tgt_ptr[q + 1]`` -- the same bits, from ``recommend_batch``'s operands and the dense
+        chain evaluated at the targets only (``lk_score_candidates``): no panel is formed.
+        ``queries``: a list of queries or a :class:`lkpy_amd.basic.HistoryBatch`; ``tgt_ptr`` int64
+        [B + 1] and ``item_nums`` int32 (-1: unknown item) are host arrays, ``d_targets`` their
+        device copies ``(offsets, numbers)`` where the caller has uploaded them already.  NaN for
+        an unknown item and for a query that cannot be scored.
+        """
+        u, valid, _hist, pending = self._batch_operands(queries)
+        st = self._device_state()
+        d_ptr, d_nums = d_targets or D.upload_targets(tgt_ptr, item_nums, st["device"])
+        rows = np.where(valid, np.arange(len(valid)), -1).astype(np.int32)
+        out = D.score_candidates(u, st["Q"], self.config.embedding_size,
+                                 torch.from_numpy(rows).to(st["device"]), d_ptr, d_nums, tgt_ptr)
+        for plan in pending:
+            plan.check_status()  # RuntimeError("ALS solve error: ...") like the fold-in alone
+        return out
+
 
 class ImplicitMFTrainer(ModelTrainer):
     "``ALSTrainerBase`` + ``ImplicitMFTrainer`` (_common.py:195-356, _implicit.py:133-175)."

@@ -14,7 +14,7 @@ from .data import ItemList, ItemListCollection, RecQuery
 from .pipeline import Pipeline
 
 
-def recommend(pipe: Pipeline, users, n: int, *, batch_size: int = 16384,
+def recommend(pipe: Pipeline, users, n: int, *, candidates=None, batch_size: int = 16384,
               rerank_depth: int | None = None) -> ItemListCollection:
     """Ordered lists of ``n`` recommendations as an ``ItemListCollection`` keyed by ``user_id``
     (what ``BatchResults.output("recommendations")`` is in the reference,
@@ -33,7 +33,15 @@ def recommend(pipe: Pipeline, users, n: int, *, batch_size: int = 16384,
     the scorer's lists are taken at that depth and reranked down to ``n``.  That departs from the
     reference's wiring, where the reranker sees the ranker's ``n`` items and can only reorder
     them (``pipe.run`` keeps that); it gives a fairness reranker items to promote.  Not with a
-    stochastic ranker."""
+    stochastic ranker.
+
+    ``candidates`` (a dict of user -> ``ItemList`` or item ids, an ``ItemListCollection`` keyed by
+    ``user_id``, or a frame with ``user_id`` and ``item_id``): every user's OWN items are ranked
+    instead of the catalogue -- ``pipe.run("recommender", query=u, items=candidates[u], n=n)``,
+    the reference's ``BatchRecRequest.candidates`` -- see :func:`_recommend_candidates`.
+    ``users=None`` then means the candidates' keys in their order."""
+    if candidates is not None:
+        return _recommend_candidates(pipe, users, n, candidates, batch_size, rerank_depth)
     scorer = pipe.node("scorer").component
     lookup = pipe.node("history-lookup").component
     reranker = _reranker(pipe)
@@ -43,14 +51,7 @@ def recommend(pipe: Pipeline, users, n: int, *, batch_size: int = 16384,
                 raise ValueError("rerank_depth does not apply to a random selection")
             return _recommend_loop(pipe, users, n)
         return _recommend_random(pipe, users, n, batch_size)
-    batched = _reranks_batches(reranker, scorer)
-    if rerank_depth is not None:
-        if not batched:
-            raise ValueError("rerank_depth needs a pipeline whose reranker has rerank_batch")
-        if _stochastic_ranker(pipe) is not None:
-            raise ValueError("rerank_depth does not apply to a stochastic ranker")
-        if rerank_depth < n:
-            raise ValueError(f"rerank_depth = {rerank_depth} is below n = {n}")
+    batched = _check_rerank_depth(pipe, reranker, scorer, n, rerank_depth)
     if reranker is not None and not batched:
         return _recommend_loop(pipe, users, n)
     depth = n if rerank_depth is None else int(rerank_depth)
@@ -102,6 +103,20 @@ def recommend(pipe: Pipeline, users, n: int, *, batch_size: int = 16384,
             out[u] = ItemList(item_nums=i[keep], vocabulary=scorer.items, scores=v[keep],
                               ordered=True)
     return ItemListCollection.from_dict(out, key=("user_id",))
+
+
+def _check_rerank_depth(pipe: Pipeline, reranker, scorer, n, rerank_depth) -> bool:
+    """Does the reranker take whole batches (``_reranks_batches``)?  Raises ``ValueError`` for a
+    ``rerank_depth`` the pipeline cannot honour -- before anything is computed."""
+    batched = _reranks_batches(reranker, scorer)
+    if rerank_depth is not None:
+        if not batched:
+            raise ValueError("rerank_depth needs a pipeline whose reranker has rerank_batch")
+        if _stochastic_ranker(pipe) is not None:
+            raise ValueError("rerank_depth does not apply to a stochastic ranker")
+        if rerank_depth < n:
+            raise ValueError(f"rerank_depth = {rerank_depth} is below n = {n}")
+    return batched
 
 
 def _recommend_loop(pipe: Pipeline, users, n) -> ItemListCollection:
@@ -352,6 +367,31 @@ def _ragged_pairs(pairs):
     return keys, offsets, item_ids, fields, lists
 
 
+def _same(a, b) -> bool:
+    return a is b or a == b
+
+
+def _numbered_dataset(scorer, lookup):
+    """The dataset behind ``lookup`` when a batch can go by ITS numbers: the lookup hands out
+    ``HistoryBatch`` es over a training matrix and the scorer's item vocabulary is that matrix's;
+    None otherwise (an untrained scorer has no vocabulary)."""
+    if not hasattr(lookup, "batch") or getattr(lookup, "interactions", None) is None:
+        return None
+    ds = lookup.interactions._ds
+    items = getattr(scorer, "items", None)
+    if items is None or not _same(items, ds.items):
+        return None
+    return ds
+
+
+def _users_agree(scorer, ds, *, required: bool) -> bool:
+    "the scorer's user vocabulary is the dataset's (``required``: and it has one)"
+    users = getattr(scorer, "users", None)
+    if users is None:
+        return not required
+    return _same(users, ds.users)
+
+
 def _batched_predict_parts(pipe: Pipeline):
     """(scorer, lookup, BiasScorer or None) when ``rating-predictor`` can run by user number:
     an ``ItemKNNScorer``, a ``UserKNNScorer`` or a ``BiasedMFScorer``, a lookup with ``batch``, no
@@ -366,29 +406,27 @@ def _batched_predict_parts(pipe: Pipeline):
 
     scorer = pipe.node("scorer").component
     lookup = pipe.node("history-lookup").component
-    if not isinstance(scorer, (ItemKNNScorer, UserKNNScorer, BiasedMFScorer)) \
-            or not hasattr(lookup, "batch") \
-            or getattr(lookup, "interactions", None) is None:
+    if not isinstance(scorer, (ItemKNNScorer, UserKNNScorer, BiasedMFScorer)):
         return None
-    ds = lookup.interactions._ds
-    same = lambda a, b: a is b or a == b  # noqa: E731
+    ds = _numbered_dataset(scorer, lookup)
+    if ds is None:
+        return None
+    same = _same
     rating = ds._attrs.get("rating")
     if isinstance(scorer, BiasedMFScorer):
         # trained, a bias model with both terms, ratings to fold in (the per-query path raises
         # without), and the lookup's users where stored rows are taken by user number
         if getattr(scorer, "item_embeddings", None) is None or \
                 getattr(scorer, "bias", None) is None or not scorer._batch_ready() or \
-                rating is None or not same(scorer.items, ds.items) or \
-                (scorer.users is not None and not same(scorer.users, ds.users)):
+                rating is None or not _users_agree(scorer, ds, required=False):
             return None
     elif isinstance(scorer, UserKNNScorer):
-        if not scorer.is_trained() or not same(scorer.items, ds.items) or \
-                not same(scorer.users, ds.users):
+        if not scorer.is_trained() or not _users_agree(scorer, ds, required=True):
             return None
         if scorer.config.explicit and rating is None:
             return None  # (the per-query path answers NaN)
     else:
-        if not scorer.is_trained() or not same(scorer.items, ds.items):
+        if not scorer.is_trained():
             return None
         if scorer.config.explicit and rating is None:
             return None  # (the per-query path raises)
@@ -514,3 +552,251 @@ def _predict_loop(pipe: Pipeline, pairs: dict) -> ItemListCollection:
     return ItemListCollection.from_dict(
         {u: pipe.run("rating-predictor", query=u, items=il) for u, il in zip(users, lists)},
         key=("user_id",))
+
+
+# ---- per-query candidate lists: recommend(candidates=...) and score ---------------------------
+def _candidate_route(pipe: Pipeline):
+    """
+    (scorer, lookup, route) when the scorer's output for each query's OWN items can be computed
+    for whole batches by user number, None when it takes the per-query loop.  ``route``:
+    ``"own"`` -- the scorer has ``score_candidates_batch`` (``ImplicitMFScorer``, the
+    ``BiasedFactorScoring`` family: ``FlexMFImplicitScorer``, ``HPFScorer``, ``LightGCNScorer``;
+    ``GlobalBiasPairScoring``: ``FlexMFExplicitScorer``, ``BiasedSVDScorer``; ``ItemKNNScorer``);
+    ``"panel"`` -- ``dense_scores_batch`` read at the targets by ``lk_panel_take_ragged``
+    (``EASEScorer``, ``UserKNNScorer``: the two whose panel is shown bit-equal to ``__call__``).
+    The pipeline must be wired as ``std:topn`` wires it (the scorer scores ``items`` when given),
+    the lookup must hand out ``HistoryBatch`` es and every vocabulary must agree
+    (``_numbered_dataset``, ``_users_agree``: the checks of ``_batched_predict_parts``).
+
+    Follow-up work, today through the loop: ``BiasedMFScorer`` (its ``__call__`` is float64 on the
+    host), ``SLIMScorer``, ``AssociationScorer``, ``PopScorer`` and the random and stochastic
+    rankers.
+    """
+    from .knn import EASEScorer, ItemKNNScorer, UserKNNScorer
+
+    node = pipe.nodes.get(pipe.aliases.get("scorer", "scorer"))
+    scorer = None if node is None else node.component
+    lookup_node = pipe.nodes.get("history-lookup")
+    if scorer is None or lookup_node is None:
+        return None
+    cand = pipe.nodes.get(node.wiring.get("items"))
+    if node.wiring.get("query") != "history-lookup" or cand is None or \
+            cand.kind != "first-of" or cand.wiring["sources"][:1] != ["items"]:
+        return None
+    lookup = lookup_node.component
+    ds = _numbered_dataset(scorer, lookup)
+    if ds is None or not _users_agree(scorer, ds, required=False):
+        return None
+    if hasattr(scorer, "is_trained") and not scorer.is_trained():
+        return None
+    if isinstance(scorer, (ItemKNNScorer, UserKNNScorer)) and scorer.config.explicit and \
+            ds._attrs.get("rating") is None:
+        return None  # (the per-query path raises / answers NaN: it goes on doing so)
+    if hasattr(scorer, "score_candidates_batch"):
+        return scorer, lookup, "own"
+    if isinstance(scorer, (EASEScorer, UserKNNScorer)) and hasattr(scorer, "dense_scores_batch"):
+        return scorer, lookup, "panel"
+    return None
+
+
+def _scored_batches(plan, key_arr, offsets, nums, batch_size: int, *, with_counts: bool = False):
+    """
+    The batches of a candidate call, scored: per batch of at most ``batch_size`` queries (a panel
+    scorer: at most its ``_panel_rows()``, 2048 without one) the histories by user number, ONE
+    packed upload of the target offsets and item numbers, and the scorer's scores of the targets
+    left on the device.  Yields (s0, s1, lo, hi, HistoryBatch, host offsets from 0, device
+    offsets, device item numbers, device scores, device neighbour counts | None); a batch without
+    targets is yielded with ``None`` s for the device values.
+    """
+    from . import _device as D
+
+    scorer, lookup, route = plan
+    B = len(key_arr)
+    if route == "panel":
+        rows = scorer._panel_rows() if hasattr(scorer, "_panel_rows") else 2048
+        batch_size = max(1, min(batch_size, rows))
+    dev = D.device()
+    for s0 in range(0, B, batch_size):
+        s1 = min(B, s0 + batch_size)
+        lo, hi = int(offsets[s0]), int(offsets[s1])
+        hb = lookup.batch(key_arr[s0:s1])
+        h_ptr = offsets[s0:s1 + 1] - lo
+        if hi == lo:
+            yield s0, s1, lo, hi, hb, h_ptr, None, None, None, None
+            continue
+        d_ptr, d_nums = D.upload_targets(h_ptr, nums[lo:hi], dev)
+        counts = None
+        if route == "panel":
+            panel, _valid, _hist = scorer.dense_scores_batch(hb)  # (the history is not struck)
+            s_dev = D.panel_take_ragged(panel, len(scorer.items), d_ptr, d_nums, h_ptr)
+            del panel
+        elif with_counts:
+            s_dev, counts = scorer.score_candidates_batch(hb, h_ptr, nums[lo:hi],
+                                                          d_targets=(d_ptr, d_nums),
+                                                          with_counts=True)
+        else:
+            s_dev = scorer.score_candidates_batch(hb, h_ptr, nums[lo:hi],
+                                                  d_targets=(d_ptr, d_nums))
+        yield s0, s1, lo, hi, hb, h_ptr, d_ptr, d_nums, s_dev, counts
+
+
+def _item_numbers(scorer, item_ids) -> np.ndarray:
+    if len(item_ids) == 0:
+        return np.zeros(0, np.int32)
+    return np.ascontiguousarray(scorer.items.numbers(item_ids, missing="negative"), np.int32)
+
+
+def _ranks_scores(pipe: Pipeline):
+    "the pipeline's ranker when it is a plain ``TopNRanker`` over the scorer's output, else None"
+    from .basic import TopNRanker
+
+    node = pipe.nodes.get(pipe.aliases.get("ranker", "ranker"))
+    if node is None or type(node.component) is not TopNRanker or \
+            node.wiring.get("items") != pipe.aliases.get("scorer", "scorer"):
+        return None
+    return node.component
+
+
+def _recommend_candidates(pipe: Pipeline, users, n, candidates, batch_size: int,
+                          rerank_depth) -> ItemListCollection:
+    """
+    ``recommend`` over each user's own candidate list: user ``u``'s result is
+    ``pipe.run("recommender", query=u, items=candidates[u], n=n)``.  The candidate selector is
+    bypassed exactly as in the reference pipeline, so the user's history is NOT excluded; items
+    the scorer does not know never appear; an unknown user and an empty candidate list give an
+    empty list that is present in the output.  ``users=None``: the candidates' keys in their
+    order; otherwise every user must have an entry (``ValueError`` naming the first without) and
+    the output follows ``users``.  ``n`` None or negative ranks every candidate.
+
+    Whole batches on the device where :func:`_candidate_route` has a route and the ranker is a
+    plain ``TopNRanker``: per batch one packed upload, the scorer's scores of the targets,
+    ``lk_ragged_topn`` (the order of ``lk_argtopn`` per list), one download; a reranker with
+    ``rerank_batch`` and ``rerank_depth`` then apply to the [B x n] arrays as in ``recommend``.
+    The lists are the per-query ones bit for bit.  Through ``pipe.run`` query by query instead:
+    candidate lists that carry fields of their own (a ``score`` among them: the per-query lists
+    keep them), a stochastic or random ranker, a reranker without ``rerank_batch``, a scorer
+    without a route, vocabularies that disagree.
+    """
+    keys, offsets, item_ids, fields, lists = _ragged_pairs(candidates)
+    keys = _key_list(keys)
+    if users is not None:
+        users = _key_list(users if isinstance(users, np.ndarray) else list(users))
+        pos = {k: i for i, k in enumerate(keys)}
+        for u in users:
+            if u not in pos:
+                raise ValueError(f"recommend: no candidates for user {u!r}")
+        sel = np.fromiter((pos[u] for u in users), np.int64, len(users))
+        lens = np.diff(offsets)[sel]
+        new_off = np.zeros(len(sel) + 1, np.int64)
+        np.cumsum(lens, out=new_off[1:])
+        take = np.repeat(offsets[:-1][sel] - new_off[:-1], lens) + np.arange(int(new_off[-1]))
+        item_ids = item_ids[take]
+        if fields is not None:
+            fields = {f: v[take] for f, v in fields.items()}
+        if lists is not None:
+            lists = [lists[i] for i in sel]
+        keys, offsets = users, new_off
+    node = pipe.nodes.get(pipe.aliases.get("scorer", "scorer"))
+    scorer = None if node is None else node.component
+    reranker = _reranker(pipe)
+    if scorer is None and rerank_depth is not None:
+        raise ValueError("rerank_depth does not apply to a random selection")
+    batched = _check_rerank_depth(pipe, reranker, scorer, n, rerank_depth)
+    ranker = _ranks_scores(pipe)
+    plan = _candidate_route(pipe)
+    if plan is None or ranker is None or fields is None or fields or \
+            (reranker is not None and not batched):
+        if lists is None:
+            lists = [ItemList(item_ids=item_ids[offsets[i]:offsets[i + 1]],
+                              **{f: v[offsets[i]:offsets[i + 1]] for f, v in (fields or {}).items()})
+                     for i in range(len(keys))]
+        return ItemListCollection.from_dict(
+            {u: pipe.run("recommender", query=u, items=il, n=n) for u, il in zip(keys, lists)},
+            key=("user_id",))
+
+    from . import _device as D
+
+    B = len(keys)
+    if B == 0:
+        return ItemListCollection(("user_id",))
+    length = n if n is not None else (ranker.config.n or -1)  # (``TopNRanker.__call__``)
+    length = -1 if length < 0 else int(length)
+    depth = length if rerank_depth is None else int(rerank_depth)
+    width = int(np.diff(offsets).max()) if depth < 0 else depth
+    key_arr = np.asarray(keys)
+    nums = _item_numbers(scorer, item_ids)
+    idx = np.full((B, width), -1, np.int32)
+    sc = np.full((B, width), np.nan, np.float32)
+    if width:
+        for s0, s1, _lo, _hi, _hb, h_ptr, d_ptr, d_nums, s_dev, _c in _scored_batches(
+                plan, key_arr, offsets, nums, batch_size):
+            if s_dev is None:
+                continue
+            i_dev, v_dev = D.ragged_topn(d_ptr, d_nums, s_dev, depth, h_ptr)
+            if i_dev.shape[1]:
+                i, v = D.lists_to_host(i_dev, v_dev)
+                idx[s0:s1, :i.shape[1]] = i
+                sc[s0:s1, :i.shape[1]] = v
+    if batched:
+        idx, sc = reranker.rerank_batch(idx, sc, _rerank_length(n))
+    return ItemListCollection.from_arrays(key_arr, idx, sc, scorer.items, key=("user_id",))
+
+
+def score(pipe: Pipeline, test, *, batch_size: int = 16384) -> ItemListCollection:
+    """
+    The scorer's scores for each query's own items -- ``pipe.run("scorer", query=u, items=il)`` for
+    every list of ``test`` -- as an ``ItemListCollection`` keyed by ``user_id``
+    (``BatchPipelineRunner.score``, src/lenskit/batch/_runner.py:114-124).  ``test``: what
+    :func:`predict` takes.  No fallback is merged in and there is no ``is_fallback``: an item the
+    scorer cannot score is NaN.
+
+    Where :func:`_candidate_route` has a route the batch runs on the device like
+    :func:`_predict_batched`: one packed upload and one download per batch, the lists carry the
+    caller's ids and fields plus ``score`` (an ``ItemKNNScorer``: ``nbr_counts`` before it, absent
+    for a query without history), bit for bit the per-query lists.  Lists that already carry a
+    ``score`` or ``nbr_counts``, lists with differing fields, a scorer without a route and
+    vocabularies that disagree go through ``pipe.run`` query by query.
+    """
+    keys, offsets, item_ids, fields, lists = _ragged_pairs(test)
+    plan = _candidate_route(pipe)
+    if plan is None or fields is None or set(fields) & {"score", "nbr_counts"}:
+        if lists is None:
+            lists = [ItemList(item_ids=item_ids[offsets[i]:offsets[i + 1]],
+                              **{f: v[offsets[i]:offsets[i + 1]] for f, v in fields.items()})
+                     for i in range(len(keys))]
+        return ItemListCollection.from_dict(
+            {u: pipe.run("scorer", query=u, items=il) for u, il in zip(_key_list(keys), lists)},
+            key=("user_id",))
+
+    import torch
+
+    from .knn import ItemKNNScorer
+
+    scorer = plan[0]
+    B = len(keys)
+    if B == 0:
+        return ItemListCollection(("user_id",))
+    key_arr = keys if isinstance(keys, np.ndarray) else np.asarray(_key_list(keys))
+    nums = _item_numbers(scorer, item_ids)
+    total = int(offsets[-1])
+    knn = isinstance(scorer, ItemKNNScorer)
+    scores = np.empty(total, np.float32)
+    counts = np.empty(total, np.int32) if knn else None
+    nohist = np.empty(B, np.bool_)
+    for s0, s1, lo, hi, hb, _h_ptr, _d_ptr, _d_nums, s_dev, c_dev in _scored_batches(
+            plan, key_arr, offsets, nums, batch_size, with_counts=knn):
+        nohist[s0:s1] = hb.lengths == 0
+        if s_dev is None:
+            continue
+        if knn:  # one download: scores | counts
+            host = torch.cat([s_dev.view(torch.int32), c_dev]).cpu().numpy()
+            scores[lo:hi] = host[:hi - lo].view(np.float32)
+            counts[lo:hi] = host[hi - lo:]
+        else:
+            scores[lo:hi] = s_dev.cpu().numpy()
+    out_fields = dict(fields)
+    if knn:
+        out_fields["nbr_counts"] = counts
+    out_fields["score"] = scores
+    return ItemListCollection.from_ragged(keys, offsets, item_ids, out_fields, key=("user_id",),
+                                          absent={"nbr_counts": nohist} if knn else None)

@@ -223,6 +223,32 @@ class ItemKNNScorer(Component):
             tgt_nums = torch.from_numpy(np.ascontiguousarray(tgt_nums, dtype=np.int32)).to(d)
         return self._score(self._batch_csr(batch), tgt_ptr, tgt_nums)
 
+    def score_candidates_batch(self, queries, tgt_ptr, item_nums, *, d_targets=None,
+                               with_counts: bool = False):
+        """
+        The scores of each query's OWN items, left on the device: f32 [total], entry t the score
+        ``__call__`` gives item ``item_nums[t]`` for the query q with ``tgt_ptr[q] <= t <
+        tgt_ptr[q + 1]`` -- the same bits: one ``lk_iknn_score_batch`` call and the item means
+        added back by ``lk_predict_merge`` (item.py:282).  ``queries``: a list of queries or a
+        :class:`lkpy_amd.basic.HistoryBatch`; ``tgt_ptr`` int64 [B + 1] and ``item_nums`` int32
+        (-1: unknown item) are host arrays, ``d_targets`` their device copies ``(offsets,
+        numbers)`` where the caller has uploaded them already.  NaN for an unknown item, for an
+        item with fewer than ``min_nbrs`` neighbours and for a query without history.
+        ``with_counts``: (scores, neighbour counts int32) -- ``__call__``'s ``nbr_counts``.
+        """
+        queries = resolve_queries(queries, self.items)
+        d = self._device_sims()["device"]
+        d_ptr, d_nums = d_targets or D.upload_targets(tgt_ptr, item_nums, d)
+        if isinstance(queries, HistoryBatch):
+            hist = self._batch_csr(queries)
+        else:
+            hist = self._query_csr(queries)
+        scores, counts = self._score(hist, d_ptr, d_nums)
+        means = self._device_means()
+        if means is not None and d_nums.numel():
+            D.predict_merge(d_ptr, d_nums, len(self.items), scores, means)
+        return (scores, counts) if with_counts else scores
+
     # -- top-n --------------------------------------------------------------------------------
     accepts_history_batch = True  # recommend_batch takes a lkpy_amd.basic.HistoryBatch
 
