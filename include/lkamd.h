@@ -1283,6 +1283,40 @@ int lk_ragged_topn(int64_t n_queries, const int64_t *d_tgt_ptr, const int32_t *d
                    int32_t *d_out_idx, float *d_out_score, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Per-query candidate lists over a sparse item-item model (csrc/sparse_candidates.hip): the
+ * entries of the lk_slim_score_batch / lk_assoc_score_batch panel at ragged targets, computed
+ * without the panel.
+ *   history  d_hist_ptr int64 [n_hist_rows + 1], d_hist_items int32 [hist_nnz] (-1: unknown item).
+ *            d_rows int32 [n_queries]: query q reads history row d_rows[q] (a row number outside
+ *            [0, n_hist_rows), -1 say, is a query without history); NULL: query q reads row q.
+ *   model    d_m_indptr int64 [n_items + 1], d_m_indices int32 [model_nnz] ascending and without
+ *            repeats inside a row, d_m_values f32 [model_nnz].
+ *   targets  the ragged layout of lk_score_candidates.
+ * d_out[t], for target column c = d_tgt_items[t] of query q: walk q's history in the order
+ * stored, skip the items outside [0, n_items), count every other one in m (repeats included), and
+ * where the item's model row holds column c fold its value v into an accumulator that starts at
+ * 0.f -- one plain float32 operation per history item, in history order:
+ *   LK_SPARSE_SUM   acc = acc + v; NaN for a history without entries, else acc (0.0 for a
+ *                   non-empty history without a known item) -- the cell of lk_slim_score_batch
+ *   LK_SPARSE_MEAN  acc = acc + v; NaN for m = 0, else float32(double(acc) / double(m))
+ *   LK_SPARSE_MAX   acc = fmaxf(acc, v): absent cells count as 0; NaN for m = 0
+ *                   (both: the cell of lk_assoc_score_batch)
+ * A target outside [0, n_items) gives NaN.  Every offset is clamped to its array and every row
+ * and item number range-checked before it becomes an address.  total = 0 returns without a
+ * launch.  No atomics; a result depends on its own query's history and its own target alone.
+ * ---------------------------------------------------------------------- */
+#define LK_SPARSE_SUM 0
+#define LK_SPARSE_MEAN 1
+#define LK_SPARSE_MAX 2
+int lk_sparse_score_candidates(const int64_t *d_hist_ptr, const int32_t *d_hist_items,
+                               int64_t n_hist_rows, int64_t hist_nnz, const int32_t *d_rows,
+                               int64_t n_queries, const int64_t *d_m_indptr,
+                               const int32_t *d_m_indices, const float *d_m_values,
+                               int64_t n_items, int64_t model_nnz, const int64_t *d_tgt_ptr,
+                               const int32_t *d_tgt_items, int64_t total, int reduce,
+                               float *d_out, void *stream);
+
+/* ------------------------------------------------------------------------
  * Stochastic top-N ranking (csrc/stochastic.hip): the sort keys of
  * `StochasticTopNRanker._compute_keys` (src/lenskit/stochastic/_ranker.py:119-156) for a panel
  * of score rows; lk_argtopn of a key row is one Plackett-Luce sample, lk_take_scores its keys

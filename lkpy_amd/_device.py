@@ -2600,6 +2600,44 @@ def panel_take_ragged(panel: torch.Tensor, n_items: int, tgt_ptr: torch.Tensor,
     return out
 
 
+def sparse_score_candidates(hist: DeviceCSR, model: DeviceCSR, reduce: str,
+                            tgt_ptr: torch.Tensor, tgt_items: torch.Tensor, h_tgt_ptr, *,
+                            rows: torch.Tensor | None = None) -> torch.Tensor:
+    """
+    The entries of the :func:`slim_score_batch` (``reduce="sum"``) or :func:`assoc_score_batch`
+    (``"mean"``, ``"max"``) panel at ragged targets, without the panel
+    (lk_sparse_score_candidates): per target a chain over the query's history rows of the sparse
+    ``model`` (int64 offsets, columns ascending inside a row), in history order.  ``hist``: the
+    histories (int64 offsets, -1 = unknown item); query q reads row ``rows[q]`` (device int32,
+    outside the CSR -- -1 -- = no history) or, without ``rows``, row q.  Returns f32
+    [len(tgt_items)] on the device: NaN for a target outside the model's columns, for a query
+    without history (``"sum"``) / without a known history item (``"mean"``, ``"max"``).
+    """
+    lib = _native.require_gpu()
+    if reduce not in _native.SPARSE_REDUCTIONS:
+        raise ValueError(f"sparse_score_candidates: unknown reduction {reduce!r}")
+    n = int(model.shape[1])
+    assert model.shape[0] == n and model.indptr.dtype == torch.int64
+    assert model.indptr.numel() == n + 1 and model.indices.dtype == torch.int32
+    assert model.values is not None and model.values.dtype == torch.float32
+    assert model.values.numel() == model.indices.numel()
+    assert hist.indptr.dtype == torch.int64 and hist.indices.dtype == torch.int32
+    n_hist = int(hist.indptr.numel()) - 1
+    nq = tgt_ptr.numel() - 1
+    if rows is not None:
+        assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.shape == (nq,)
+    else:
+        assert n_hist >= nq
+    _ragged_args(h_tgt_ptr, tgt_ptr, tgt_items)
+    out = torch.empty(tgt_items.numel(), dtype=torch.float32, device=model.indices.device)
+    check(lib.lk_sparse_score_candidates(
+        _ptr(hist.indptr), _ptr(hist.indices), n_hist, hist.nnz, _ptr(rows), nq,
+        _ptr(model.indptr), _ptr(model.indices), _ptr(model.values), n, model.nnz,
+        _ptr(tgt_ptr), _ptr(tgt_items), tgt_items.numel(), _native.SPARSE_REDUCTIONS[reduce],
+        _ptr(out), _stream()), "lk_sparse_score_candidates")
+    return out
+
+
 def ragged_topn_classes() -> tuple[int, int]:
     """The longest segment :func:`ragged_topn` ranks in one wave, and in one workgroup
     (lk_ragged_topn_wave_max, lk_ragged_topn_block_max); longer ones are sorted."""

@@ -46,6 +46,7 @@ BMF_INVALID, BMF_FOLD, BMF_STORED = 0, 1, 2  # LK_BMF_*: a query's branch of Bia
 
 ASSOC_METHODS = {"probability": 0, "lift": 1}  # LK_ASSOC_PROBABILITY / LK_ASSOC_LIFT
 ASSOC_REDUCTIONS = {"mean": 0, "max": 1}  # LK_ASSOC_MEAN / LK_ASSOC_MAX
+SPARSE_REDUCTIONS = {"sum": 0, "mean": 1, "max": 2}  # LK_SPARSE_SUM / _MEAN / _MAX
 # lk_gemm_f32's tile mask: LK_GEMM_LOWER / LK_GEMM_K_FROM_COL / LK_GEMM_K_FROM_ROW
 GEMM_LOWER = 1
 GEMM_K_FROM_COL = 2
@@ -338,6 +339,10 @@ def _declare(lib):
         "lk_ragged_topn_workspace_bytes": (c_size_t, [c_int64, c_int64]),
         "lk_ragged_topn": (
             c_int, [c_int64, vp, vp, vp, c_int64, c_int32, c_int64, vp, vp, vp, vp]
+        ),
+        "lk_sparse_score_candidates": (
+            c_int, [vp, vp, c_int64, c_int64, vp, c_int64, vp, vp, vp, c_int64, c_int64, vp, vp,
+                    c_int64, c_int, vp, vp]
         ),
         "lk_stochastic_row_stats": (
             c_int, [vp, c_int64, c_int64, c_int64, vp, vp, c_int32, c_float, vp, vp]

@@ -164,6 +164,23 @@ class HistoryBatch:
         self._cache[key] = out
         return out
 
+    def matrix_rows(self):
+        """(the HBM-resident training matrix itself as a structure-only device CSR with int64
+        offsets, device int32 row numbers [B] into it, -1 = unknown user): the histories by user
+        number for the kernels that take row numbers -- no row gather.  Row ``r`` holds
+        ``ds._cols[s:e]``, the items ``row_items`` attaches per query, in that order.  The int64
+        offsets are made once per uploaded matrix and kept with it."""
+        import torch
+
+        from . import _device as D
+
+        st = self.lookup._device_matrix()
+        if "rows_csr" not in st:
+            src = st["csr"]
+            st["rows_csr"] = D.DeviceCSR(src.indptr.long(), src.indices, None, src.shape,
+                                         src.h_indptr)
+        return st["rows_csr"], torch.from_numpy(self.user_nums).to(st["device"])
+
     def subset(self, mask: np.ndarray) -> "HistoryBatch":
         return HistoryBatch(self.lookup, self.user_ids[mask], self.user_nums[mask])
 
@@ -507,6 +524,27 @@ class PopScorer(Component, Trainable):
         if device_output:
             return idx, sc
         return D.lists_to_host(idx, sc)
+
+    ignores_query = True  # ``__call__`` takes no query: the scorer node need not be wired to one
+
+    def score_candidates_batch(self, queries, tgt_ptr, item_nums, *, d_targets=None):
+        """
+        The scores of each query's OWN items, left on the device: f32 [total], entry t is
+        ``item_scores[item_nums[t]]`` (the bits ``__call__`` gives), NaN for an unknown item --
+        the cached device score row read at the targets as a one-row panel
+        (``lk_panel_take_ragged`` with the offsets ``[0, total]``).  ``queries`` is not looked at:
+        an unknown user is scored like any other, as in ``pipe.run``.  ``tgt_ptr`` int64 [B + 1]
+        and ``item_nums`` int32 are host arrays, ``d_targets`` their device copies.
+        """
+        import torch
+
+        from . import _device as D
+
+        st = self._device_order()
+        _d_ptr, d_nums = d_targets or D.upload_targets(tgt_ptr, item_nums, st["device"])
+        ends = np.array([0, d_nums.numel()], np.int64)
+        return D.panel_take_ragged(st["scores"][None], len(self.items),
+                                   torch.from_numpy(ends).to(st["device"]), d_nums, ends)
 
     def dense_scores_batch(self, queries):
         """

@@ -39,7 +39,10 @@ def recommend(pipe: Pipeline, users, n: int, *, candidates=None, batch_size: int
     ``user_id``, or a frame with ``user_id`` and ``item_id``): every user's OWN items are ranked
     instead of the catalogue -- ``pipe.run("recommender", query=u, items=candidates[u], n=n)``,
     the reference's ``BatchRecRequest.candidates`` -- see :func:`_recommend_candidates`.
-    ``users=None`` then means the candidates' keys in their order."""
+    ``users=None`` then means the candidates' keys in their order.  Whole batches on the device
+    for every scorer :func:`_candidate_route` has a route for -- the factor models, the k-NN
+    scorers, EASE, SLIM, association rules and popularity; only ``BiasedMFScorer`` goes query by
+    query."""
     if candidates is not None:
         return _recommend_candidates(pipe, users, n, candidates, batch_size, rerank_depth)
     scorer = pipe.node("scorer").component
@@ -561,16 +564,19 @@ def _candidate_route(pipe: Pipeline):
     for whole batches by user number, None when it takes the per-query loop.  ``route``:
     ``"own"`` -- the scorer has ``score_candidates_batch`` (``ImplicitMFScorer``, the
     ``BiasedFactorScoring`` family: ``FlexMFImplicitScorer``, ``HPFScorer``, ``LightGCNScorer``;
-    ``GlobalBiasPairScoring``: ``FlexMFExplicitScorer``, ``BiasedSVDScorer``; ``ItemKNNScorer``);
+    ``GlobalBiasPairScoring``: ``FlexMFExplicitScorer``, ``BiasedSVDScorer``; ``ItemKNNScorer``;
+    ``SLIMScorer`` and ``AssociationScorer``: the chain of their panel cell at the targets only,
+    ``lk_sparse_score_candidates``; ``PopScorer`` / ``TimeBoundedPopScore``: the score row read at
+    the targets);
     ``"panel"`` -- ``dense_scores_batch`` read at the targets by ``lk_panel_take_ragged``
     (``EASEScorer``, ``UserKNNScorer``: the two whose panel is shown bit-equal to ``__call__``).
-    The pipeline must be wired as ``std:topn`` wires it (the scorer scores ``items`` when given),
+    The pipeline must be wired as ``std:topn`` wires it (the scorer scores ``items`` when given;
+    a scorer that declares ``ignores_query`` may have no ``query`` input at all),
     the lookup must hand out ``HistoryBatch`` es and every vocabulary must agree
     (``_numbered_dataset``, ``_users_agree``: the checks of ``_batched_predict_parts``).
 
     Follow-up work, today through the loop: ``BiasedMFScorer`` (its ``__call__`` is float64 on the
-    host), ``SLIMScorer``, ``AssociationScorer``, ``PopScorer`` and the random and stochastic
-    rankers.
+    host) and the random and stochastic rankers.
     """
     from .knn import EASEScorer, ItemKNNScorer, UserKNNScorer
 
@@ -580,7 +586,8 @@ def _candidate_route(pipe: Pipeline):
     if scorer is None or lookup_node is None:
         return None
     cand = pipe.nodes.get(node.wiring.get("items"))
-    if node.wiring.get("query") != "history-lookup" or cand is None or \
+    unwired = "query" not in node.wiring and getattr(scorer, "ignores_query", False)
+    if (node.wiring.get("query") != "history-lookup" and not unwired) or cand is None or \
             cand.kind != "first-of" or cand.wiring["sources"][:1] != ["items"]:
         return None
     lookup = lookup_node.component
@@ -753,7 +760,9 @@ def score(pipe: Pipeline, test, *, batch_size: int = 16384) -> ItemListCollectio
     Where :func:`_candidate_route` has a route the batch runs on the device like
     :func:`_predict_batched`: one packed upload and one download per batch, the lists carry the
     caller's ids and fields plus ``score`` (an ``ItemKNNScorer``: ``nbr_counts`` before it, absent
-    for a query without history), bit for bit the per-query lists.  Lists that already carry a
+    for a query without history), bit for bit the per-query lists.  ``SLIMScorer`` and
+    ``AssociationScorer`` score the targets alone (``lk_sparse_score_candidates``: no [1 x items]
+    panel per query), ``PopScorer`` reads its score row at them.  Lists that already carry a
     ``score`` or ``nbr_counts``, lists with differing fields, a scorer without a route and
     vocabularies that disagree go through ``pipe.run`` query by query.
     """

@@ -42,6 +42,7 @@
 // No atomics; a result depends on its own segment alone.
 #include "common.h"
 #include "radix_sort.h"
+#include "ragged.h"
 
 namespace lk {
 namespace cand {
@@ -54,23 +55,8 @@ constexpr int BLOCK_MAX = 1024;   // longest segment ranked by one workgroup in 
 constexpr int BLOCK_T = 256;
 constexpr int PER_T = BLOCK_MAX / BLOCK_T;
 
-__device__ __forceinline__ int64_t clampi(int64_t v, int64_t lo, int64_t hi)
-{
-    return v < lo ? lo : (v > hi ? hi : v);
-}
-
-// the query q with ptr[q] <= pos < ptr[q + 1] (offsets ascending from 0, pos < ptr[n]); always in
-// [0, n - 1], whatever the offsets hold
-__device__ __forceinline__ int64_t query_of(const int64_t *__restrict__ ptr, int64_t n, int64_t pos)
-{
-    int64_t lo = 0, hi = n;  // ptr[lo] <= pos < ptr[hi]
-    while (hi - lo > 1) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (ptr[mid] <= pos) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
+using ragged::clampi;
+using ragged::query_of;
 
 __global__ __launch_bounds__(64 * WPB) void score_candidates_kernel(
     const float *__restrict__ U, int ld_u, int64_t n_users, const float *__restrict__ Q, int ld_q,

@@ -368,6 +368,24 @@ class _PanelScorer:
     def __call__(self, query, items: ItemList) -> ItemList:
         return self.score_batch([query], [items])[0]
 
+    def _sparse_candidates(self, queries, model: D.DeviceCSR, reduce: str, tgt_ptr, item_nums,
+                           d_targets):
+        """
+        ``score_candidates_batch`` of the scorers whose model is a sparse item-item matrix
+        (``model``: columns ascending inside a row): the panel's cells at the targets by
+        ``lk_sparse_score_candidates``, no panel formed.  A :class:`HistoryBatch` is read out of
+        the HBM-resident training matrix by user number (no row gather); a list of queries is
+        packed like ``score_batch`` packs it (:meth:`_query_csr`).
+        """
+        queries = resolve_queries(queries, self.items)
+        d = model.indices.device
+        d_ptr, d_nums = d_targets or D.upload_targets(tgt_ptr, item_nums, d)
+        if isinstance(queries, HistoryBatch):
+            hist, rows = queries.matrix_rows()
+        else:
+            hist, rows = self._query_csr(queries), None
+        return D.sparse_score_candidates(hist, model, reduce, d_ptr, d_nums, tgt_ptr, rows=rows)
+
     def recommend_batch(self, queries, n: int | None, *, exclude_history: bool = True):
         """
         Top-``n`` lists for many queries at once -- what the ``recommender`` pipeline computes one
@@ -972,6 +990,39 @@ class SLIMScorer(_PanelScorer, Component):
         # no / empty history: every score NaN, told by the row's length (slim.py:125-130)
         return self._score_lists(hist, item_lists, nan_empty=False)
 
+    def _device_weights_ascending(self) -> D.DeviceCSR:
+        "``_device_weights`` with ascending columns inside a row: a sorted COPY where they are not."
+        w = self.weights
+        if w.has_sorted_indices:
+            return self._device_weights()
+
+        def upload():
+            s = w.copy()
+            s.sort_indices()
+            return D.DeviceCSR.from_host(s.indptr, s.indices, s.data, s.shape, D.device())
+
+        return self._device_cache("weights_ascending", upload, self.weights)
+
+    def score_candidates_batch(self, queries, tgt_ptr, item_nums, *, d_targets=None):
+        """
+        The scores of each query's OWN items, left on the device: f32 [total], entry t the score
+        ``__call__`` gives item ``item_nums[t]`` for the query q with ``tgt_ptr[q] <= t <
+        tgt_ptr[q + 1]`` -- the same bits, without the [1 x items] panel ``__call__`` forms:
+        ``lk_sparse_score_candidates`` adds, per target, the weights of the history items whose
+        row holds the target, in history order, which is the panel cell's own chain
+        (``lk_slim_score_batch``: ``row[c] += v`` once per history item).  The arguments are those
+        of ``ItemKNNScorer.score_candidates_batch``.  NaN for an unknown item and for a query
+        without history (an unknown user); 0.0 where no history item reaches the target.
+
+        The equality rests on the history order: a :class:`HistoryBatch` row is the training
+        matrix's row ``ds._cols[s:e]``, which is what the per-query lookup attaches
+        (``row_items``, data.py) and ``pack_histories`` hands on in that order
+        (``unknown="keep"``, no sort) -- the fact ``recommend_batch``'s equality rests on too.
+        The weight rows are assumed to name a column once, as the trainer leaves them.
+        """
+        return self._sparse_candidates(queries, self._device_weights_ascending(), "sum", tgt_ptr,
+                                       item_nums, d_targets)
+
 
 # ---------------------------------------------------------------------------------------
 # Association rules: conditional probability, lift, biased lift
@@ -1071,6 +1122,25 @@ class AssociationScorer(_PanelScorer, Component):
         "``_PanelScorer.recommend_batch`` (the pipeline of ``biased-lift.toml``) by mean or max."
         self._reduction()  # (an unsupported max_nbrs is refused before anything is uploaded)
         return super().recommend_batch(queries, n, exclude_history=exclude_history)
+
+    def score_candidates_batch(self, queries, tgt_ptr, item_nums, *, d_targets=None):
+        """
+        The scores of each query's OWN items, left on the device: f32 [total], entry t the score
+        ``__call__`` gives item ``item_nums[t]`` for the query q with ``tgt_ptr[q] <= t <
+        tgt_ptr[q + 1]`` -- the same bits, without the [1 x items] panel ``__call__`` forms:
+        ``lk_sparse_score_candidates`` folds, per target, the cells of the reference items' rows
+        in reference-item order and ends as ``lk_assoc_score_batch`` does
+        (``float32(double(sum) / double(m))``, or the maximum over 0).  The arguments are those of
+        ``ItemKNNScorer.score_candidates_batch``.  NaN for an unknown item and for a query
+        without a known reference item (an unknown user).
+
+        The equality rests on the history order, as ``SLIMScorer.score_candidates_batch`` says:
+        a :class:`HistoryBatch` row is the training row the per-query lookup attaches, and
+        ``pack_histories`` keeps its order.
+        """
+        reduce = self._reduction()  # (as in recommend_batch: refused before anything is uploaded)
+        return self._sparse_candidates(queries, self._device_matrix(), reduce, tgt_ptr, item_nums,
+                                       d_targets)
 
     def dense_scores_batch(self, queries):
         """
