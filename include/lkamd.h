@@ -596,6 +596,10 @@ int lk_predict_merge(int64_t n_queries, const int64_t *d_tgt_ptr, const int32_t 
  * lk_bmf_finish_pairs: entries first_entry .. first_entry + n_entries - 1 of the ragged lists
  *   d_tgt_ptr [n_rows + 1] / d_tgt_items (d_tgt_ptr[0] = first_entry; negative or >= n_items: an
  *   unknown item, NaN): d_out[e] = the finish of d_panel[row of e][d_tgt_items[e]].
+ * lk_bmf_finish_ragged: the same finish where the dot products are ragged already: d_dots f32
+ *   [total] holds the lk_score_dense entry of (row of e, d_tgt_items[e]) at e -- what
+ *   lk_score_candidates writes --, d_tgt_ptr [n_rows + 1] ascends from 0 to total.  d_out [total]
+ *   may be d_dots itself.  No panel is read.
  * ---------------------------------------------------------------------- */
 #define LK_BMF_INVALID 0
 #define LK_BMF_FOLD 1
@@ -615,6 +619,10 @@ int lk_bmf_finish_pairs(const float *d_panel, int64_t n_rows, int64_t n_items, i
                         const float *d_item_biases, const int64_t *d_tgt_ptr,
                         const int32_t *d_tgt_items, int64_t first_entry, int64_t n_entries,
                         float *d_out, void *stream);
+int lk_bmf_finish_ragged(const float *d_dots, int64_t n_rows, int64_t n_items,
+                         const uint8_t *d_mode, const double *d_ub, double global_bias,
+                         const float *d_item_biases, const int64_t *d_tgt_ptr,
+                         const int32_t *d_tgt_items, int64_t total, float *d_out, void *stream);
 
 /* ------------------------------------------------------------------------
  * User-kNN scoring for a BATCH of queries.
@@ -1356,6 +1364,31 @@ int lk_stochastic_keys(const float *d_scores, int64_t n_rows, int64_t row_len, i
                        void *stream);
 int lk_stochastic_key_of_bits(const float *d_log_weight, const uint32_t *d_bits, int64_t n,
                               float *d_out, void *stream);
+
+/* ------------------------------------------------------------------------
+ * The same keys for ragged candidate lists (csrc/ragged_stochastic.hip).  Segment s -- the entries
+ * d_ptr[s] .. d_ptr[s + 1] - 1 (int64 [n_segments + 1], ascending from 0 to total) -- is the row of
+ * a [1 x d_width[s]] panel that holds d_scores[t] at column d_addr[t] and NaN everywhere else:
+ *   d_stats [n_segments x 4]  the bits lk_stochastic_row_stats writes for that row;
+ *   d_keys [samples x total]  d_keys[j * total + t] = the bits lk_stochastic_keys writes at column
+ *                             d_addr[t] for sample first_sample + j and stream d_streams[s]; NaN
+ *                             for an entry with a non-finite score.
+ * One statistics pass serves every sample.  CONTRACT: the addresses of a segment ascend strictly
+ * and lie in [0, d_width[s]) -- the float32 sum is added in the panel kernel's tree (entry t
+ * belongs to its thread (d_addr[t] >> 2) % BLK, BLK = 64 for a width <= 2048 and 256 above), which
+ * a walk in address order reproduces.  The caller checks that on its host copy; the kernel uses
+ * no input as a memory address (offsets are clamped to [0, total], an address outside its row
+ * takes no part), so a broken contract gives other bits, never an access out of bounds.
+ * One wave per segment; a segment longer than lk_ragged_stochastic_chunk() (512) entries is
+ * walked in chunks of that many by the same wave.  No atomics: a segment has the same bits alone
+ * and inside any batch.  total < 2^31.
+ * ---------------------------------------------------------------------- */
+int32_t lk_ragged_stochastic_chunk(void);
+int lk_ragged_stochastic_keys(int64_t n_segments, const int64_t *d_ptr, const int32_t *d_addr,
+                              const float *d_scores, int64_t total, const int32_t *d_width,
+                              const uint64_t *d_streams, int32_t transform, float scale,
+                              uint64_t seed, uint32_t first_sample, int32_t samples,
+                              float *d_stats, float *d_keys, void *stream);
 
 /* ------------------------------------------------------------------------
  * FA*IR top-N reranking (csrc/fair.hip): the greedy loop of `FAIRReranker.__call__`

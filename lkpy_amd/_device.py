@@ -2673,6 +2673,104 @@ def ragged_topn(tgt_ptr: torch.Tensor, tgt_items: torch.Tensor, scores: torch.Te
     return idx, out
 
 
+def ragged_stochastic_chunk() -> int:
+    """The entries :func:`ragged_stochastic_keys` stages per wave (lk_ragged_stochastic_chunk): a
+    longer segment is walked in chunks of that many."""
+    return int(_native.load().lk_ragged_stochastic_chunk())
+
+
+def check_ragged_addresses(h_ptr, h_addr, h_widths):
+    """
+    The host copies of a ragged key call, validated before anything is launched: offsets as
+    :func:`check_ragged` takes them, int32 addresses that ascend strictly inside a segment and lie
+    in ``[0, width of the segment)``, one int32 width per segment.  Raises ``ValueError``
+    otherwise.  Returns the three as contiguous arrays.
+    """
+    addr = np.ascontiguousarray(h_addr, dtype=np.int32).reshape(-1)
+    widths = np.ascontiguousarray(h_widths, dtype=np.int32).reshape(-1)
+    if len(addr) >= 2 ** 31:
+        raise ValueError("more than 2^31 entries in one call")
+    ptr = check_ragged(h_ptr, len(widths), len(addr))
+    if len(addr):
+        lens = np.diff(ptr)
+        if (addr < 0).any() or (addr >= np.repeat(widths, lens)).any():
+            raise ValueError("addresses must lie in [0, width) of their segment")
+        inner = np.ones(len(addr), np.bool_)
+        inner[ptr[:-1][lens > 0]] = False  # (a segment's first entry has no predecessor)
+        if (np.diff(addr, prepend=addr[:1])[inner] <= 0).any():
+            raise ValueError("addresses must ascend strictly inside a segment")
+    return ptr, addr, widths
+
+
+def ragged_stochastic_keys(h_ptr, h_addr, scores, h_widths, streams, *, transform, scale: float,
+                           seed: int, samples: int = 1, first_sample: int = 0):
+    """
+    The stochastic ranker's keys for ragged candidate lists (lk_ragged_stochastic_keys): segment
+    s -- the entries ``h_ptr[s]:h_ptr[s + 1]`` -- stands for the row of a [1 x ``h_widths[s]``]
+    panel with ``scores[t]`` (device f32 [total], or a host array) at column ``h_addr[t]`` and NaN
+    elsewhere, and gets the bits :func:`stochastic_keys` gives that row under stream
+    ``streams[s]`` -- without the row.  The host arrays are validated
+    (:func:`check_ragged_addresses`) and go up in ONE packed transfer.  Returns (keys f32
+    [samples x total], sample ``first_sample + j`` in row j, NaN for an entry with a non-finite
+    score; stats f32 [segments x 4]; the device offsets int64; the device addresses int32).
+    """
+    ptr, addr, widths = check_ragged_addresses(h_ptr, h_addr, h_widths)
+    code = _native.STOCHASTIC_TRANSFORMS[transform]
+    samples = int(samples)
+    if samples < 0 or first_sample < 0 or first_sample + samples > 2 ** 32:
+        raise ValueError("samples must be addressable by 32 bits")
+    lib = _native.require_gpu()
+    B, total = len(widths), len(addr)
+    if isinstance(scores, torch.Tensor):
+        dev = scores.device
+    else:
+        dev = device()
+        scores = torch.from_numpy(np.ascontiguousarray(scores, dtype=np.float32)).to(dev)
+    assert scores.dtype == torch.float32 and scores.is_contiguous() and scores.shape == (total,)
+    head = 2 * (B + 1)
+    packed = np.empty(head + total + B, np.int32)
+    packed[:head] = ptr.view(np.int32)
+    packed[head:head + total] = addr
+    packed[head + total:] = widths
+    d_packed = torch.from_numpy(packed).to(dev)
+    d_ptr = d_packed[:head].view(torch.int64)
+    d_addr, d_widths = d_packed[head:head + total], d_packed[head + total:]
+    keys = torch.empty((samples, total), dtype=torch.float32, device=dev)
+    stats = torch.empty((B, 4), dtype=torch.float32, device=dev)
+    if B:
+        check(lib.lk_ragged_stochastic_keys(
+            B, _ptr(d_ptr), _ptr(d_addr), _ptr(scores), total, _ptr(d_widths),
+            _ptr(_row_streams(streams, B, dev)), code, float(scale), int(seed) & (2**64 - 1),
+            int(first_sample), samples, _ptr(stats), _ptr(keys), _stream()),
+            "lk_ragged_stochastic_keys")
+    return keys, stats, d_ptr, d_addr
+
+
+def bmf_finish_ragged(dots: torch.Tensor, mode: torch.Tensor, ub: torch.Tensor,
+                      global_bias: float, item_biases: torch.Tensor, tgt_ptr: torch.Tensor,
+                      tgt_items: torch.Tensor, h_tgt_ptr) -> torch.Tensor:
+    """
+    ``BiasedMFScorer.finalize_scores`` in place on ragged dot products (lk_bmf_finish_ragged):
+    ``dots`` f32 [total] is what :func:`score_candidates` returns for the rows whose lists are
+    ``tgt_ptr`` / ``tgt_items``; per row a mode (uint8, ``_native.BMF_*``) and a float64 user
+    bias.  The arithmetic is :func:`bmf_finish_pairs`'s; an unknown item (-1) is NaN.  Returns
+    ``dots``.
+    """
+    lib = _native.require_gpu()
+    rows = tgt_ptr.numel() - 1
+    assert dots.dtype == torch.float32 and dots.is_contiguous()
+    assert dots.numel() == tgt_items.numel()
+    assert mode.dtype == torch.uint8 and mode.shape == (rows,) and mode.is_contiguous()
+    assert ub.dtype == torch.float64 and ub.shape == (rows,) and ub.is_contiguous()
+    assert item_biases.dtype == torch.float32 and item_biases.is_contiguous()
+    _ragged_args(h_tgt_ptr, tgt_ptr, tgt_items)
+    check(lib.lk_bmf_finish_ragged(_ptr(dots), rows, int(item_biases.shape[0]), _ptr(mode),
+                                   _ptr(ub), float(global_bias), _ptr(item_biases),
+                                   _ptr(tgt_ptr), _ptr(tgt_items), dots.numel(), _ptr(dots),
+                                   _stream()), "lk_bmf_finish_ragged")
+    return dots
+
+
 # ---- randomized truncated SVD (csrc/svd.hip) ------------------------------------------------
 SVD_OVERSAMPLES = 10  # sklearn's ``n_oversamples`` default, which ``TruncatedSVD`` passes on
 

@@ -192,6 +192,10 @@ def _declare(lib):
             [vp, c_int64, c_int64, c_int64, vp, vp, ctypes.c_double, vp, vp, vp, c_int64, c_int64,
              vp, vp],
         ),
+        "lk_bmf_finish_ragged": (
+            c_int,
+            [vp, c_int64, c_int64, vp, vp, ctypes.c_double, vp, vp, vp, c_int64, vp, vp],
+        ),
         "lk_uknn_score_batch": (
             c_int,
             [vp, vp, vp, c_int64, c_int64, c_int64, vp, vp, vp, vp, vp, c_int32, c_int32, vp, vp,
@@ -352,6 +356,11 @@ def _declare(lib):
                     vp, ctypes.c_uint32, vp, c_int64, vp]
         ),
         "lk_stochastic_key_of_bits": (c_int, [vp, vp, c_int64, vp, vp]),
+        "lk_ragged_stochastic_chunk": (c_int32, []),
+        "lk_ragged_stochastic_keys": (
+            c_int, [c_int64, vp, vp, vp, c_int64, vp, vp, c_int32, c_float, ctypes.c_uint64,
+                    ctypes.c_uint32, c_int32, vp, vp, vp]
+        ),
         "lk_fair_max_n": (c_int32, []),
         "lk_fair_rerank": (
             c_int, [vp, c_int64, c_int64, c_int64, vp, vp, vp, c_int64, vp, c_int32, c_int32, vp,

@@ -655,6 +655,25 @@ class RandomSelector(RowStreams, Component):
                           seed=self.seed, excl=excl, samples=samples, first_sample=first_sample,
                           device_output=device_output)
 
+    def rank_ragged(self, ptr, addr, payload, widths, streams, n: int | None, *,
+                    samples: int = 1, first_sample: int = 0, device_output: bool = False):
+        """
+        ``stochastic.rank_ragged`` with no transform over a constant score of 1.0: the selection
+        ``__call__`` makes from each list of a ragged batch, as the ``payload`` numbers of the
+        picked entries ([B x S x n] int32, -1 padding).  The keys are not returned.
+        """
+        import torch
+
+        from . import _device as D
+        from .stochastic import rank_ragged
+
+        total = int(np.asarray(ptr).reshape(-1)[-1])
+        ones = torch.ones(total, dtype=torch.float32, device=D.device())
+        idx, _keys = rank_ragged(ptr, addr, payload, ones, widths, streams, self._length(n),
+                                 transform=None, scale=1.0, seed=self.seed, samples=samples,
+                                 first_sample=first_sample, device_output=device_output)
+        return idx
+
     def __call__(self, items: ItemList, query=None, n: int | None = None) -> ItemList:
         import torch
 

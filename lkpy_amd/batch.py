@@ -42,7 +42,9 @@ def recommend(pipe: Pipeline, users, n: int, *, candidates=None, batch_size: int
     ``users=None`` then means the candidates' keys in their order.  Whole batches on the device
     for every scorer :func:`_candidate_route` has a route for -- the factor models, the k-NN
     scorers, EASE, SLIM, association rules and popularity; only ``BiasedMFScorer`` goes query by
-    query."""
+    query --, under a plain ``TopNRanker``, a ``StochasticTopNRanker`` (the sampled rankings of
+    the lists, ``lk_ragged_stochastic_keys``) and the ``RandomSelector`` of a
+    ``random_pipeline``."""
     if candidates is not None:
         return _recommend_candidates(pipe, users, n, candidates, batch_size, rerank_depth)
     scorer = pipe.node("scorer").component
@@ -254,7 +256,7 @@ def _sample_panels(pipe: Pipeline, users, n: int, samples: int, batch_size: int)
     return ids, idx, keys
 
 
-def recommend_samples(pipe: Pipeline, users, n: int, samples: int, *,
+def recommend_samples(pipe: Pipeline, users, n: int, samples: int, *, candidates=None,
                       batch_size: int = 16384) -> ItemListCollection:
     """
     ``samples`` sampled rankings of ``n`` items per user from a pipeline whose ranker is a
@@ -262,11 +264,19 @@ def recommend_samples(pipe: Pipeline, users, n: int, samples: int, *,
     what ``recommend`` draws.  A scorer without ``dense_scores_batch`` is scored through the
     pipeline user by user and ranked ``samples`` times.  A pipeline's ``reranker`` is applied to
     every sampled list, as ``recommend`` applies it.
+
+    ``candidates``: as in ``recommend(candidates=)`` -- every user's OWN items are ranked
+    ``samples`` times, ``users=None`` means the candidates' keys in their order, sample 0 is
+    what ``recommend(candidates=)`` draws; whole batches on the device where that call has them
+    (:func:`_sample_candidates`: one statistics pass serves every sample of a list).
     """
     ranker = _stochastic_ranker(pipe)
     if ranker is None:
         raise TypeError("recommend_samples needs a pipeline whose ranker is a StochasticTopNRanker")
     samples = int(samples)
+    if candidates is not None:
+        return _recommend_samples_candidates(pipe, ranker, users, n, samples, candidates,
+                                             batch_size)
     scorer = pipe.node("scorer").component
     reranker = _reranker(pipe)
     if reranker is not None and not _reranks_batches(reranker, scorer) and \
@@ -296,6 +306,42 @@ def recommend_samples(pipe: Pipeline, users, n: int, samples: int, *,
     if reranker is not None:
         idx, keys = reranker.rerank_batch(idx, keys, _rerank_length(n))
     return ItemListCollection.from_arrays(pairs, idx, keys, scorer.items,
+                                          key=("user_id", "sample"))
+
+
+def _recommend_samples_candidates(pipe: Pipeline, ranker, users, n, samples: int, candidates,
+                                  batch_size: int) -> ItemListCollection:
+    "``recommend_samples`` over each user's own candidate list (:func:`_recommend_candidates`)"
+    keys, offsets, item_ids, fields, lists = _candidate_lists(users, candidates)
+    node = pipe.nodes.get(pipe.aliases.get("scorer", "scorer"))
+    scorer = None if node is None else node.component
+    reranker = _reranker(pipe)
+    batched = _reranks_batches(reranker, scorer)
+    plan = _candidate_route(pipe)
+    got = None
+    if plan is not None and _samples_scores(pipe) is ranker and fields is not None and \
+            not fields and (reranker is None or batched) and len(keys):
+        got = _sample_candidates(plan, ranker, keys, offsets, item_ids, lists, n, samples,
+                                 batch_size)
+    if got is None:
+        if lists is None:
+            lists = [ItemList(item_ids=item_ids[offsets[i]:offsets[i + 1]],
+                              **{f: v[offsets[i]:offsets[i + 1]] for f, v in (fields or {}).items()})
+                     for i in range(len(keys))]
+        out = {}
+        for u, il in zip(keys, lists):
+            res = pipe.run_all("history-lookup", "scorer", query=u, items=il)
+            drawn = ranker.sample(res["scorer"], res["history-lookup"], n, samples=samples)
+            if reranker is not None:
+                drawn = [reranker(items=d, n=_rerank_length(n)) for d in drawn]
+            out.update({(u, s): d for s, d in enumerate(drawn)})
+        return ItemListCollection.from_dict(out, key=("user_id", "sample"))
+    _key_arr, idx, kk = got
+    pairs = [(u, s) for u in keys for s in range(samples)]
+    idx, kk = idx.reshape(len(pairs), -1), kk.reshape(len(pairs), -1)
+    if reranker is not None:
+        idx, kk = reranker.rerank_batch(idx, kk, _rerank_length(n))
+    return ItemListCollection.from_arrays(pairs, idx, kk, scorer.items,
                                           key=("user_id", "sample"))
 
 
@@ -576,7 +622,8 @@ def _candidate_route(pipe: Pipeline):
     (``_numbered_dataset``, ``_users_agree``: the checks of ``_batched_predict_parts``).
 
     Follow-up work, today through the loop: ``BiasedMFScorer`` (its ``__call__`` is float64 on the
-    host) and the random and stochastic rankers.
+    host; ``lk_bmf_finish_ragged`` is the finish its route will take).  Which RANKERS run batched
+    over a route is :func:`_recommend_candidates`'s matter.
     """
     from .knn import EASEScorer, ItemKNNScorer, UserKNNScorer
 
@@ -664,25 +711,11 @@ def _ranks_scores(pipe: Pipeline):
     return node.component
 
 
-def _recommend_candidates(pipe: Pipeline, users, n, candidates, batch_size: int,
-                          rerank_depth) -> ItemListCollection:
+def _candidate_lists(users, candidates):
     """
-    ``recommend`` over each user's own candidate list: user ``u``'s result is
-    ``pipe.run("recommender", query=u, items=candidates[u], n=n)``.  The candidate selector is
-    bypassed exactly as in the reference pipeline, so the user's history is NOT excluded; items
-    the scorer does not know never appear; an unknown user and an empty candidate list give an
-    empty list that is present in the output.  ``users=None``: the candidates' keys in their
-    order; otherwise every user must have an entry (``ValueError`` naming the first without) and
-    the output follows ``users``.  ``n`` None or negative ranks every candidate.
-
-    Whole batches on the device where :func:`_candidate_route` has a route and the ranker is a
-    plain ``TopNRanker``: per batch one packed upload, the scorer's scores of the targets,
-    ``lk_ragged_topn`` (the order of ``lk_argtopn`` per list), one download; a reranker with
-    ``rerank_batch`` and ``rerank_depth`` then apply to the [B x n] arrays as in ``recommend``.
-    The lists are the per-query ones bit for bit.  Through ``pipe.run`` query by query instead:
-    candidate lists that carry fields of their own (a ``score`` among them: the per-query lists
-    keep them), a stochastic or random ranker, a reranker without ``rerank_batch``, a scorer
-    without a route, vocabularies that disagree.
+    The candidate lists of a call as :func:`_ragged_pairs` gives them, in the order of the
+    output: ``users=None`` -- the candidates' keys in their order; otherwise the lists of
+    ``users`` in that order (``ValueError`` naming the first user without an entry).
     """
     keys, offsets, item_ids, fields, lists = _ragged_pairs(candidates)
     keys = _key_list(keys)
@@ -703,6 +736,213 @@ def _recommend_candidates(pipe: Pipeline, users, n, candidates, batch_size: int,
         if lists is not None:
             lists = [lists[i] for i in sel]
         keys, offsets = users, new_off
+    return keys, offsets, item_ids, fields, lists
+
+
+def _samples_scores(pipe: Pipeline):
+    "the pipeline's ranker when it is a ``StochasticTopNRanker`` over the scorer's output, else None"
+    ranker = _stochastic_ranker(pipe)
+    if ranker is None:
+        return None
+    node = pipe.nodes[pipe.aliases.get("ranker", "ranker")]
+    return ranker if node.wiring.get("items") == pipe.aliases.get("scorer", "scorer") else None
+
+
+def _candidate_addresses(lists, offsets, numbers, vocab):
+    """
+    How the draws of a ragged batch of candidate lists are addressed -- exactly as
+    ``StochasticTopNRanker.sample`` / ``RandomSelector.__call__`` address one list:
+
+    - lists without a vocabulary (``lists`` None: a frame; ids; dicts of arrays): by POSITION, the
+      row is as wide as the list;
+    - lists that all carry ``vocab``: by item NUMBER (``numbers``: each entry's number in
+      ``vocab``), the row is as wide as the vocabulary, and the entries of a list are sorted by
+      number (``lk_ragged_stochastic_keys`` wants ascending addresses).
+
+    Returns (addresses int32 [total], widths int32 [B], order): ``order`` is None by position,
+    else the int64 permutation with ``sorted = original[order]`` -- the entries stay inside their
+    list.  None when the batch has to go query by query: a list with another vocabulary, lists of
+    both kinds, or a list in which an item repeats (``numbers`` equal and not negative: the
+    per-query row keeps the last one).  Empty lists are of either kind.
+    """
+    offsets = np.asarray(offsets, np.int64)
+    numbers = np.asarray(numbers)
+    lens = np.diff(offsets)
+    B, total = len(lens), int(offsets[-1])
+    by_number = False
+    if lists is not None:
+        kinds = set()
+        for il in lists:
+            if len(il) == 0:
+                continue
+            v = il.vocabulary
+            if v is None:
+                kinds.add(0)
+            elif vocab is not None and _same(v, vocab):
+                kinds.add(1)
+            else:
+                return None
+        if len(kinds) > 1:
+            return None
+        by_number = kinds == {1}
+    # one int64 key per entry, (list, number + 1): a sort of it brings a list's repeats together
+    # (an unknown item, negative, is 0 in the low word and never counts) -- ten times cheaper than
+    # a lexsort at a million entries
+    seg = np.repeat(np.arange(B, dtype=np.int64), lens)
+    key = (seg << 32) | (np.maximum(numbers, -1).astype(np.int64) + 1)
+    if not by_number:
+        srt = np.sort(key)
+        if total > 1 and ((srt[1:] == srt[:-1]) & ((srt[1:] & 0xFFFFFFFF) != 0)).any():
+            return None
+        addr = (np.arange(total, dtype=np.int64) - np.repeat(offsets[:-1], lens)).astype(np.int32)
+        return addr, lens.astype(np.int32), None
+    order = np.argsort(key, kind="stable")  # (the lists stay apart: the list is the high word)
+    srt = key[order]
+    if total and ((srt & 0xFFFFFFFF) == 0).any():
+        return None  # (a list that carries the vocabulary holds its items only)
+    if total > 1 and (srt[1:] == srt[:-1]).any():
+        return None
+    return (np.ascontiguousarray((srt & 0xFFFFFFFF) - 1, np.int32),
+            np.full(B, len(vocab), np.int32), order.astype(np.int64))
+
+
+def _sample_candidates(plan, ranker, keys, offsets, item_ids, lists, n, samples: int,
+                       batch_size: int):
+    """
+    ``samples`` sampled rankings of every user's own candidate list, whole batches at a time:
+    :func:`_scored_batches` -> the ranker's ``rank_ragged`` -> one download per batch; no
+    [B x items] panel.  Streams as :func:`_sample_panels` takes them: ONE ``streams`` call over
+    the users as the lookup types them.  Returns (user ids, item numbers [B x S x width], keys
+    [B x S x width]), or None where :func:`_candidate_addresses` sends the batch to the loop
+    (nothing has been drawn then).
+    """
+    from . import _device as D
+
+    scorer, lookup, _route = plan
+    B = len(keys)
+    key_arr = np.asarray(keys)
+    nums = _item_numbers(scorer, item_ids)
+    packed = _candidate_addresses(lists, offsets, nums, scorer.items)
+    if packed is None:
+        return None
+    addr, widths, order = packed
+    if order is not None:
+        nums = nums[order]  # (scored in address order; the lists hold item numbers either way)
+    samples = int(samples)
+    n = ranker._length(n)
+    width = int(np.diff(offsets).max()) if n < 0 else n
+    idx = np.full((B, samples, width), -1, np.int32)
+    kk = np.full((B, samples, width), np.nan, np.float32)
+    if width == 0 or samples == 0:
+        return key_arr, idx, kk
+    streams = ranker.streams(lookup.batch(key_arr).user_ids)
+    for s0, s1, lo, hi, _hb, h_ptr, _d_ptr, d_nums, s_dev, _c in _scored_batches(
+            plan, key_arr, offsets, nums, batch_size):
+        if s_dev is None:
+            continue
+        i_dev, k_dev = ranker.rank_ragged(h_ptr, addr[lo:hi], d_nums, s_dev, widths[s0:s1],
+                                          streams[s0:s1], n, samples=samples, device_output=True)
+        w = i_dev.shape[2]
+        if w:
+            i, k = D.lists_to_host(i_dev.view(-1, w), k_dev.view(-1, w))
+            idx[s0:s1, :, :w] = i.reshape(s1 - s0, samples, w)
+            kk[s0:s1, :, :w] = k.reshape(s1 - s0, samples, w)
+    return key_arr, idx, kk
+
+
+def _item_codes(item_ids) -> np.ndarray:
+    "a non-negative number below 2^31 - 1 per entry, equal for equal ids (no vocabulary needed)"
+    ids = np.asarray(item_ids)
+    if len(ids) and ids.dtype.kind in "iu":
+        lo = int(ids.min())
+        if int(ids.max()) - lo < 2 ** 31 - 1:
+            return (ids - lo).astype(np.int64)
+    return pd.factorize(ids)[0]
+
+
+def _random_candidates(pipe: Pipeline, selector, keys, offsets, item_ids, fields, lists, n,
+                       batch_size: int):
+    """
+    ``recommend(candidates=)`` for a ``random_pipeline``: there is no scorer, the selector's
+    ``rank_ragged`` draws from the candidate lists directly (a constant score, no transform),
+    and the result carries the caller's ids and fields and no score, as
+    ``RandomSelector.__call__`` returns it.  Unknown items are ordinary candidates; an unknown
+    user has a stream like any other.  None where the batch has to go query by query: another
+    wiring than ``random_pipeline``'s, a lookup without ``batch``, or addresses
+    (:func:`_candidate_addresses`: by the vocabulary the lists carry, else by position) that
+    cannot be packed.
+    """
+    node = pipe.nodes[pipe.aliases.get("ranker", "ranker")]
+    cand = pipe.nodes.get(node.wiring.get("items"))
+    lookup_node = pipe.nodes.get("history-lookup")
+    if cand is None or cand.kind != "first-of" or cand.wiring["sources"][:1] != ["items"] or \
+            node.wiring.get("query") != "history-lookup" or lookup_node is None or \
+            not hasattr(lookup_node.component, "batch"):
+        return None
+    vocab = None
+    if lists is not None:
+        vocab = next((il.vocabulary for il in lists if len(il)), None)
+    if vocab is not None:
+        numbers = vocab.numbers(item_ids, missing="negative") if len(item_ids) else \
+            np.zeros(0, np.int32)
+    else:
+        numbers = _item_codes(item_ids)
+    packed = _candidate_addresses(lists, offsets, numbers, vocab)
+    if packed is None:
+        return None
+    addr, widths, order = packed
+    B, total = len(keys), int(offsets[-1])
+    n = selector._length(n)
+    key_arr = np.asarray(keys)
+    streams = selector.streams(lookup_node.component.batch(key_arr).user_ids)
+    # the result carries each picked entry's position in the caller's arrays
+    where = np.arange(total, dtype=np.int32) if order is None else order.astype(np.int32)
+    picked, counts = [], np.zeros(B, np.int64)
+    for s0 in range(0, B, batch_size):
+        s1 = min(B, s0 + batch_size)
+        lo, hi = int(offsets[s0]), int(offsets[s1])
+        if hi == lo or n == 0:
+            continue
+        idx = selector.rank_ragged(offsets[s0:s1 + 1] - lo, addr[lo:hi], where[lo:hi],
+                                   widths[s0:s1], streams[s0:s1], n)[:, 0]
+        keep = idx >= 0
+        counts[s0:s1] = keep.sum(axis=1)
+        picked.append(idx[keep])  # (row-major: list by list, in rank order)
+    take = np.concatenate(picked) if picked else np.zeros(0, np.int32)
+    out_off = np.zeros(B + 1, np.int64)
+    np.cumsum(counts, out=out_off[1:])
+    return ItemListCollection.from_ragged(keys, out_off, item_ids[take],
+                                          {f: v[take] for f, v in fields.items()},
+                                          key=("user_id",))
+
+
+def _recommend_candidates(pipe: Pipeline, users, n, candidates, batch_size: int,
+                          rerank_depth) -> ItemListCollection:
+    """
+    ``recommend`` over each user's own candidate list: user ``u``'s result is
+    ``pipe.run("recommender", query=u, items=candidates[u], n=n)``.  The candidate selector is
+    bypassed exactly as in the reference pipeline, so the user's history is NOT excluded; items
+    the scorer does not know never appear; an unknown user and an empty candidate list give an
+    empty list that is present in the output.  ``users=None``: the candidates' keys in their
+    order; otherwise every user must have an entry (``ValueError`` naming the first without) and
+    the output follows ``users``.  ``n`` None or negative ranks every candidate.
+
+    Whole batches on the device where :func:`_candidate_route` has a route and the ranker is a
+    plain ``TopNRanker``: per batch one packed upload, the scorer's scores of the targets,
+    ``lk_ragged_topn`` (the order of ``lk_argtopn`` per list), one download; a reranker with
+    ``rerank_batch`` and ``rerank_depth`` then apply to the [B x n] arrays as in ``recommend``.
+    A ``StochasticTopNRanker`` over the scorer's output takes the same scores through its
+    ``rank_ragged`` (:func:`_sample_candidates`: the keys of ``lk_ragged_stochastic_keys`` as the
+    lists' scores, as ``sample()`` returns them; ``rerank_depth`` raises), and a
+    ``random_pipeline`` -- no scorer -- draws from the lists directly
+    (:func:`_random_candidates`).  The lists are the per-query ones bit for bit.  Through
+    ``pipe.run`` query by query instead: candidate lists that carry fields of their own under a
+    scorer (a ``score`` among them: the per-query lists keep them), a reranker without
+    ``rerank_batch``, a scorer without a route, vocabularies that disagree, and under the two
+    drawing rankers the lists :func:`_candidate_addresses` cannot pack -- a repeated item,
+    another vocabulary than the scorer's, lists with and without a vocabulary.
+    """
+    keys, offsets, item_ids, fields, lists = _candidate_lists(users, candidates)
     node = pipe.nodes.get(pipe.aliases.get("scorer", "scorer"))
     scorer = None if node is None else node.component
     reranker = _reranker(pipe)
@@ -711,6 +951,26 @@ def _recommend_candidates(pipe: Pipeline, users, n, candidates, batch_size: int,
     batched = _check_rerank_depth(pipe, reranker, scorer, n, rerank_depth)
     ranker = _ranks_scores(pipe)
     plan = _candidate_route(pipe)
+    out = None
+    if scorer is None:
+        selector = _random_selector(pipe)
+        if selector is not None and reranker is None and fields is not None and len(keys):
+            out = _random_candidates(pipe, selector, keys, offsets, item_ids, fields, lists, n,
+                                     batch_size)
+    elif ranker is None and plan is not None and fields is not None and not fields and \
+            (reranker is None or batched) and len(keys):
+        sampler = _samples_scores(pipe)
+        got = None if sampler is None else _sample_candidates(
+            plan, sampler, keys, offsets, item_ids, lists, n, 1, batch_size)
+        if got is not None:
+            key_arr, idx, sc = got
+            idx, sc = idx[:, 0], sc[:, 0]
+            if batched:
+                idx, sc = reranker.rerank_batch(idx, sc, _rerank_length(n))
+            out = ItemListCollection.from_arrays(key_arr, idx, sc, scorer.items,
+                                                 key=("user_id",))
+    if out is not None:
+        return out
     if plan is None or ranker is None or fields is None or fields or \
             (reranker is not None and not batched):
         if lists is None:

@@ -16,6 +16,8 @@
 //                             load).
 //   bmf_finish_pairs_kernel   the same finish for ragged (query, target) lists, the dot product
 //                             gathered from the panel.  One thread per entry.
+//   bmf_finish_ragged_kernel  the same finish where the dot products are a ragged array already
+//                             (lk_score_candidates: no panel).  One thread per entry.
 //
 // The finish arithmetic is `bmf_finish` and nowhere else.  A row's mode says which branch of
 // `__call__` it took, and with it the precision of the sum (include/lkamd.h).
@@ -158,6 +160,27 @@ __global__ __launch_bounds__(256) void bmf_finish_pairs_kernel(
     out[e] = s;
 }
 
+__global__ __launch_bounds__(256) void bmf_finish_ragged_kernel(
+    const float *dots, int64_t n_rows, int64_t n_items, const uint8_t *__restrict__ mode,
+    const double *__restrict__ ub, float g32, const float *__restrict__ item_biases,
+    const int64_t *__restrict__ tgt_ptr, const int32_t *__restrict__ tgt_items, int64_t total,
+    float *out)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    // the entry's row: the last r with tgt_ptr[r] <= e (empty lists hold no entries)
+    int64_t lo = 0, hi = n_rows - 1;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (tgt_ptr[mid] <= e) lo = mid;
+        else hi = mid - 1;
+    }
+    const int32_t t = tgt_items[e];
+    float s = __builtin_nanf("");  // an unknown item: `item_scores` leaves NaN
+    if (t >= 0 && t < n_items) s = bmf_finish(dots[e], g32 + item_biases[t], mode[lo], ub[lo]);
+    out[e] = s;
+}
+
 }  // namespace
 }  // namespace lk
 
@@ -245,6 +268,26 @@ extern "C" int lk_bmf_finish_pairs(const float *d_panel, int64_t n_rows, int64_t
     hipLaunchKernelGGL(lk::bmf_finish_pairs_kernel, dim3((unsigned)nb), dim3(256), 0, st, d_panel,
                        n_rows, n_items, ld, d_mode, d_ub, (float)global_bias, d_item_biases,
                        d_tgt_ptr, d_tgt_items, first_entry, n_entries, d_out);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
+extern "C" int lk_bmf_finish_ragged(const float *d_dots, int64_t n_rows, int64_t n_items,
+                                    const uint8_t *d_mode, const double *d_ub, double global_bias,
+                                    const float *d_item_biases, const int64_t *d_tgt_ptr,
+                                    const int32_t *d_tgt_items, int64_t total, float *d_out,
+                                    void *stream)
+{
+    LK_REQUIRE(n_rows >= 0 && n_items >= 0 && total >= 0, "lk_bmf_finish_ragged: bad shape");
+    if (total == 0) return LK_OK;
+    LK_REQUIRE(n_rows > 0 && d_dots && d_mode && d_ub && d_item_biases && d_tgt_ptr &&
+                   d_tgt_items && d_out,
+               "lk_bmf_finish_ragged: null pointer");
+    const int64_t nb = (total + 255) / 256;
+    LK_REQUIRE(nb <= (int64_t)INT32_MAX, "lk_bmf_finish_ragged: too many entries");
+    hipLaunchKernelGGL(lk::bmf_finish_ragged_kernel, dim3((unsigned)nb), dim3(256), 0,
+                       lk::as_stream(stream), d_dots, n_rows, n_items, d_mode, d_ub,
+                       (float)global_bias, d_item_biases, d_tgt_ptr, d_tgt_items, total, d_out);
     LK_HIP_CHECK(hipGetLastError());
     return LK_OK;
 }

@@ -24,17 +24,13 @@
 //   stoch_bits_kernel   the key function on given random words (the tests reach the ends of u).
 // An item's membership in the sorted exclusion row is a binary search for the group's first item
 // followed by a walk over at most the group's entries.
-#include <float.h>
-#include <math.h>
-
-#include "common.h"
-#include "philox.h"
+#include "stochastic_shared.h"
 
 namespace lk {
 
 namespace {
 
-constexpr float LOG_FLT_MIN = -87.33654475055310898657f;  // log(2^-126)
+using namespace stoch;
 
 struct Quad {
     float v[4];
@@ -80,52 +76,6 @@ __device__ __forceinline__ bool takes_part(float score, unsigned mask, int j)
     return isfinite(score) && !((mask >> j) & 1u);
 }
 
-// log(-log u) for the uniform of the random word `bits`
-__device__ __forceinline__ float log_neg_log_u(uint32_t bits)
-{
-    const float u = (float)(2u * (bits >> 9) + 1u) * 0x1p-24f;  // odd 24-bit integer: exact
-    const float nl = u > 0.5f ? -log1pf(-(1.0f - u)) : -logf(u);
-    return logf(nl);
-}
-
-__device__ __forceinline__ float key_of(float logw, uint32_t bits)
-{
-    return fmaxf(logw, LOG_FLT_MIN) - log_neg_log_u(bits);
-}
-
-__device__ __forceinline__ float log_of_weight(float w)
-{
-    return w >= FLT_MIN ? logf(w) : LOG_FLT_MIN;  // (negative, zero and subnormal: the clamp)
-}
-
-// workgroup reductions with one fixed order: butterfly inside the wave (every lane ends with the
-// same bits), the waves' values in wave order through LDS
-template <int BLK, class Op>
-__device__ __forceinline__ float block_reduce(float v, float *lds, Op op)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_xor(v, off, 64));
-    if constexpr (BLK > WAVE) {
-        __syncthreads();  // (the previous reduction's reads of lds are over)
-        if (lane_id() == 0) lds[threadIdx.x >> 6] = v;
-        __syncthreads();
-        v = lds[0];
-#pragma unroll
-        for (int w = 1; w < BLK / WAVE; ++w) v = op(v, lds[w]);
-    }
-    return v;
-}
-
-struct OpMax {
-    __device__ float operator()(float a, float b) const { return fmaxf(a, b); }
-};
-struct OpMin {
-    __device__ float operator()(float a, float b) const { return fminf(a, b); }
-};
-struct OpAdd {
-    __device__ float operator()(float a, float b) const { return a + b; }
-};
-
 // stats row: max, min, sum (float), count (int32 bits)
 template <int BLK>
 __global__ __launch_bounds__(BLK) void stoch_stats_kernel(
@@ -165,15 +115,14 @@ __global__ __launch_bounds__(BLK) void stoch_stats_kernel(
 
     float sum = 0.f;
     const float range = mx - mn;
-    if (transform == LK_STOCHASTIC_SOFTMAX || (transform == LK_STOCHASTIC_LINEAR && range > 0.f)) {
+    if (has_sum(transform, range)) {
         for (int64_t q = threadIdx.x; q < nq; q += BLK) {
             const Quad s = load_quad(row, q * 4, row_len, aligned);
             const unsigned mask = quad_mask(excl_items, elo, ehi, q * 4);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (takes_part(s.v[j], mask, j)) {
-                    const float x = s.v[j] * scale;
-                    sum += transform == LK_STOCHASTIC_SOFTMAX ? expf(x - mx) : (x - mn) / range;
+                    sum += sum_term(s.v[j], scale, mx, mn, range, transform);
                 }
             }
         }
@@ -207,7 +156,7 @@ __global__ __launch_bounds__(256) void stoch_keys_kernel(
     const float mx = stats[r * 4], mn = stats[r * 4 + 1], sum = stats[r * 4 + 2];
     const int32_t n = __builtin_bit_cast(int32_t, stats[r * 4 + 3]);
     const float range = mx - mn;
-    const bool uniform = !(range > 0.f) || !(sum > 0.f);  // linear: every weight 1/N
+    const bool uniform = uniform_weights(range, sum);
     const float log_sum = transform == LK_STOCHASTIC_SOFTMAX ? logf(sum) : 0.f;
     const float log_unif = -logf((float)n);
 
@@ -218,12 +167,8 @@ __global__ __launch_bounds__(256) void stoch_keys_kernel(
     Quad g;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const float x = s.v[j] * scale;
-        float logw;
-        if (transform == LK_STOCHASTIC_SOFTMAX) logw = (x - mx) - log_sum;
-        else if (transform == LK_STOCHASTIC_LINEAR)
-            logw = uniform ? log_unif : log_of_weight(((x - mn) / range) / sum);
-        else logw = log_of_weight(x);
+        const float logw = log_weight(s.v[j], scale, mx, mn, range, sum, uniform, log_sum,
+                                      log_unif, transform);
         g.v[j] = takes_part(s.v[j], mask, j) ? key_of(logw, c[j]) : NAN;
     }
     if (first + 4 <= row_len && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) {
@@ -242,11 +187,6 @@ __global__ __launch_bounds__(256) void stoch_bits_kernel(const float *__restrict
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) out[i] = key_of(logw[i], bits[i]);
-}
-
-bool bad_transform(int t)
-{
-    return t != LK_STOCHASTIC_NONE && t != LK_STOCHASTIC_SOFTMAX && t != LK_STOCHASTIC_LINEAR;
 }
 
 }  // namespace
@@ -268,7 +208,7 @@ extern "C" int lk_stochastic_row_stats(const float *d_scores, int64_t n_rows, in
     LK_REQUIRE(d_stats && (row_len == 0 || d_scores), "lk_stochastic_row_stats: null pointer");
     // a wave for short rows, a workgroup for long ones: chosen by the row length alone, so a row
     // reduces in the same order in every batch
-    if (row_len <= 2048)
+    if (row_len <= STATS_WAVE_MAX)
         hipLaunchKernelGGL(stoch_stats_kernel<64>, dim3((unsigned)n_rows), dim3(64), 0,
                            as_stream(stream), d_scores, ld, row_len, d_excl_ptr, d_excl_items,
                            transform, scale, d_stats);

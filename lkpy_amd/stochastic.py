@@ -2,7 +2,8 @@
 Stochastic top-N ranking: ``lenskit.stochastic.StochasticTopNRanker``
 (src/lenskit/stochastic/_ranker.py:19-156) -- a ranking sampled from the Plackett-Luce
 distribution over the (transformed) scores by exponential-sort sampling -- on the device, for one
-list and for whole panels of score rows with many samples per row.
+list, for whole panels of score rows and for ragged batches of candidate lists
+(:func:`rank_ragged`, ``lk_ragged_stochastic_keys``), with many samples per row.
 
 The keys come from ``lk_stochastic_row_stats`` / ``lk_stochastic_keys`` (csrc/stochastic.hip), the
 list from ``lk_argtopn`` + ``lk_take_scores``.  The key is ``g = log w~ - log(-log u)``; the
@@ -73,6 +74,51 @@ def rank_panel(panel, streams, n: int, *, transform, scale: float, seed: int, ex
     return D.to_host(idx), D.to_host(keys)
 
 
+def rank_ragged(ptr, addr, payload, scores, widths, streams, n: int, *, transform, scale: float,
+                seed: int, samples: int = 1, first_sample: int = 0, device_output: bool = False):
+    """
+    :func:`rank_panel` for ragged candidate lists, without a panel: list b is the entries
+    ``ptr[b]:ptr[b + 1]`` (host int64 offsets from 0), entry t has the score ``scores[t]`` (device
+    f32 [total], or a host array), the item number ``addr[t]`` that addresses its draw (host int32:
+    strictly ascending inside a list and below ``widths[b]``, the length of the row the list would
+    occupy in a panel) and the number ``payload[t]`` that the result carries for it (int32, host or
+    device; None: the address; a negative one is dropped).  The keys are those of ``rank_panel``
+    on the [1 x widths[b]] row holding the scores at the addresses (``lk_ragged_stochastic_keys``,
+    computed once for every sample), the lists ``lk_ragged_topn`` of them: ties go to the lower
+    position, which is the lower column.  Returns (payload int32 [B x S x n] padded with -1, keys
+    f32 [B x S x n] padded with NaN), sample ``first_sample + s`` at ``[:, s]``; ``n < 0``: every
+    entry, the width of the longest list.
+    """
+    import torch
+
+    from . import _device as D
+
+    samples, n = int(samples), int(n)
+    keys, _stats, d_ptr, d_addr = D.ragged_stochastic_keys(
+        ptr, addr, scores, widths, streams, transform=transform, scale=scale, seed=seed,
+        samples=samples, first_sample=first_sample)
+    h_ptr = np.ascontiguousarray(ptr, dtype=np.int64).reshape(-1)
+    B = len(h_ptr) - 1
+    dev = keys.device
+    if payload is None:
+        d_payload = d_addr
+    elif isinstance(payload, torch.Tensor):
+        d_payload = payload
+    else:
+        d_payload = torch.from_numpy(np.ascontiguousarray(payload, dtype=np.int32)).to(dev)
+    width = (int(np.diff(h_ptr).max()) if B else 0) if n < 0 else n
+    idx = torch.full((B, samples, width), -1, dtype=torch.int32, device=dev)
+    out = torch.full((B, samples, width), float("nan"), dtype=torch.float32, device=dev)
+    if B and width and keys.shape[1]:
+        for s in range(samples):
+            i, k = D.ragged_topn(d_ptr, d_payload, keys[s], n, h_ptr)
+            idx[:, s, :i.shape[1]] = i
+            out[:, s, :i.shape[1]] = k
+    if device_output:
+        return idx, out
+    return D.to_host(idx), D.to_host(out)
+
+
 class StochasticTopNConfig(BaseModel, arbitrary_types_allowed=True):
     "src/lenskit/stochastic/_ranker.py:19-56"
 
@@ -114,6 +160,18 @@ class StochasticTopNRanker(RowStreams, Component):
         return rank_panel(panel, streams, self._length(n), transform=self.config.transform,
                           scale=self.config.scale, seed=self.seed, excl=excl, samples=samples,
                           first_sample=first_sample, device_output=device_output)
+
+    def rank_ragged(self, ptr, addr, payload, scores, widths, streams, n: int | None, *,
+                    samples: int = 1, first_sample: int = 0, device_output: bool = False):
+        """
+        ``samples`` sampled rankings of every list of a ragged batch of scored candidates
+        (:func:`rank_ragged`) under the config's transform, scale and seed: the lists
+        :meth:`sample` draws one by one, without their [1 x items] rows.
+        """
+        return rank_ragged(ptr, addr, payload, scores, widths, streams, self._length(n),
+                           transform=self.config.transform, scale=self.config.scale,
+                           seed=self.seed, samples=samples, first_sample=first_sample,
+                           device_output=device_output)
 
     # -- one list -------------------------------------------------------------------------------
     def sample(self, items: ItemList, query=None, n: int | None = None, *, samples: int = 1,
