@@ -7,11 +7,15 @@ rank 1): the reference's ``batch.recommend`` / ``batch.predict`` loop queries in
 
 from __future__ import annotations
 
+from itertools import repeat
+
 import numpy as np
 import pandas as pd
 
+from .basic import RandomSelector, TopNRanker
 from .data import ItemList, ItemListCollection, RecQuery
 from .pipeline import Pipeline
+from .stochastic import StochasticTopNRanker
 
 
 def recommend(pipe: Pipeline, users, n: int, *, candidates=None, batch_size: int = 16384,
@@ -49,8 +53,8 @@ def recommend(pipe: Pipeline, users, n: int, *, candidates=None, batch_size: int
         return _recommend_candidates(pipe, users, n, candidates, batch_size, rerank_depth)
     scorer = pipe.node("scorer").component
     lookup = pipe.node("history-lookup").component
-    reranker = _reranker(pipe)
-    if scorer is None and _random_selector(pipe) is not None:
+    reranker = _slot(pipe, "reranker")
+    if scorer is None and _ranker(pipe, RandomSelector) is not None:
         if reranker is not None or rerank_depth is not None or not _random_by_panels(pipe):
             if rerank_depth is not None:
                 raise ValueError("rerank_depth does not apply to a random selection")
@@ -60,21 +64,18 @@ def recommend(pipe: Pipeline, users, n: int, *, candidates=None, batch_size: int
     if reranker is not None and not batched:
         return _recommend_loop(pipe, users, n)
     depth = n if rerank_depth is None else int(rerank_depth)
-    if _stochastic_ranker(pipe) is not None:
+    if _ranker(pipe, StochasticTopNRanker) is not None:
         # a sampled ranking is not the scorer's own top-N: the lists come from the ranker, by
         # panels where the scorer has them, else through the pipeline user by user
-        if not _has_panels(scorer, lookup):
+        drawn = _draw_samples(pipe, users, n, 1, batch_size)
+        if drawn is None:
             return _recommend_loop(pipe, users, n)
-        ids, idx, keys = _sample_panels(pipe, users, n, 1, batch_size)
-        i0, k0 = idx[:, 0], keys[:, 0]
-        if batched:
-            i0, k0 = reranker.rerank_batch(i0, k0, _rerank_length(n))
-        return ItemListCollection.from_arrays(ids, i0, k0, scorer.items, key=("user_id",))
+        return _sampled_lists(drawn, scorer.items, reranker, n, key=("user_id",))
     if hasattr(scorer, "recommend_batch") and _takes_history_batches(scorer, lookup):
         # the whole batch by user number: the histories are rows of the HBM-resident training
         # matrix, no per-query host work (an id ARRAY stays an array); the lists are built when
         # somebody looks at them
-        ids = users if isinstance(users, np.ndarray) else np.asarray(list(users))
+        ids = _as_array(users)
         on_device = batched and getattr(scorer, "returns_device_lists", False)
         idx, sc = [], []
         for s in range(0, len(ids), batch_size):
@@ -117,7 +118,7 @@ def _check_rerank_depth(pipe: Pipeline, reranker, scorer, n, rerank_depth) -> bo
     if rerank_depth is not None:
         if not batched:
             raise ValueError("rerank_depth needs a pipeline whose reranker has rerank_batch")
-        if _stochastic_ranker(pipe) is not None:
+        if _ranker(pipe, StochasticTopNRanker) is not None:
             raise ValueError("rerank_depth does not apply to a stochastic ranker")
         if rerank_depth < n:
             raise ValueError(f"rerank_depth = {rerank_depth} is below n = {n}")
@@ -133,12 +134,6 @@ def _recommend_loop(pipe: Pipeline, users, n) -> ItemListCollection:
 def _takes_history_batches(scorer, lookup) -> bool:
     "the lookup hands out ``HistoryBatch`` es and the scorer's batch calls take them"
     return hasattr(lookup, "batch") and getattr(scorer, "accepts_history_batch", False)
-
-
-def _reranker(pipe: Pipeline):
-    "the component of the pipeline's ``reranker`` node, or None"
-    node = pipe.nodes.get("reranker")
-    return None if node is None else node.component
 
 
 def _reranks_batches(reranker, scorer) -> bool:
@@ -158,22 +153,27 @@ def _rerank_length(n):
 STOCHASTIC_PANEL_BYTES = 4 << 30
 
 
-def _stochastic_ranker(pipe: Pipeline):
-    "the pipeline's ranker when it is a ``StochasticTopNRanker``, else None"
-    from .stochastic import StochasticTopNRanker
-
-    node = pipe.nodes.get(pipe.aliases.get("ranker", "ranker"))
-    comp = None if node is None else node.component
-    return comp if isinstance(comp, StochasticTopNRanker) else None
+def _slot(pipe: Pipeline, name: str):
+    "the component of the node that ``name`` names or is an alias of; None without one"
+    node = pipe.nodes.get(pipe.aliases.get(name, name))
+    return None if node is None else node.component
 
 
-def _random_selector(pipe: Pipeline):
-    "the pipeline's ranker when it is a ``RandomSelector``, else None"
-    from .basic import RandomSelector
+def _ranker(pipe: Pipeline, cls, *, exact: bool = False, over_scorer: bool = False):
+    """The pipeline's ranker when it is a ``cls`` (``exact``: of that very class, no subclass) and
+    -- ``over_scorer`` -- ranks the scorer's output; else None."""
+    comp = _slot(pipe, "ranker")
+    if not (type(comp) is cls if exact else isinstance(comp, cls)):
+        return None
+    if not over_scorer:
+        return comp
+    wired_to = pipe.node("ranker").wiring.get("items")
+    return comp if wired_to == pipe.aliases.get("scorer", "scorer") else None
 
-    node = pipe.nodes.get(pipe.aliases.get("ranker", "ranker"))
-    comp = None if node is None else node.component
-    return comp if isinstance(comp, RandomSelector) else None
+
+def _as_array(users) -> np.ndarray:
+    "user keys as an array (an id ARRAY stays the array it is, a list is not copied first)"
+    return np.asarray(users if isinstance(users, (np.ndarray, list)) else list(users))
 
 
 def _random_by_panels(pipe: Pipeline) -> bool:
@@ -181,7 +181,7 @@ def _random_by_panels(pipe: Pipeline) -> bool:
     history -- and the lookup hands out ``HistoryBatch`` es over those items"""
     from .basic import TrainingItemsCandidateSelector
 
-    ranker = pipe.nodes[pipe.aliases.get("ranker", "ranker")]
+    ranker = pipe.node("ranker")
     lookup = pipe.node("history-lookup").component
     cand = pipe.nodes.get("candidate-selector")
     cand = None if cand is None else cand.component
@@ -205,9 +205,9 @@ def _recommend_random(pipe: Pipeline, users, n, batch_size: int) -> ItemListColl
 
     from . import _device as D
 
-    selector = _random_selector(pipe)
+    selector = _ranker(pipe, RandomSelector)
     lookup = pipe.node("history-lookup").component
-    ids = users if isinstance(users, np.ndarray) else np.asarray(list(users))
+    ids = _as_array(users)
     if len(ids) == 0:
         return ItemListCollection(("user_id",))
     hb = lookup.batch(ids)
@@ -237,10 +237,10 @@ def _sample_panels(pipe: Pipeline, users, n: int, samples: int, batch_size: int)
     ``STOCHASTIC_PANEL_BYTES / (8 n_items)`` rows (a float32 score and a float32 key per item).
     Returns (user ids, item numbers [B x S x n], keys [B x S x n]).
     """
-    ranker = _stochastic_ranker(pipe)
+    ranker = _ranker(pipe, StochasticTopNRanker)
     scorer = pipe.node("scorer").component
     lookup = pipe.node("history-lookup").component
-    ids = users if isinstance(users, np.ndarray) else np.asarray(list(users))
+    ids = _as_array(users)
     n = ranker._length(n)
     width = len(scorer.items) if n < 0 else n
     rows = max(1, min(batch_size, STOCHASTIC_PANEL_BYTES // (8 * max(1, len(scorer.items)))))
@@ -270,18 +270,29 @@ def recommend_samples(pipe: Pipeline, users, n: int, samples: int, *, candidates
     what ``recommend(candidates=)`` draws; whole batches on the device where that call has them
     (:func:`_sample_candidates`: one statistics pass serves every sample of a list).
     """
-    ranker = _stochastic_ranker(pipe)
+    ranker = _ranker(pipe, StochasticTopNRanker)
     if ranker is None:
         raise TypeError("recommend_samples needs a pipeline whose ranker is a StochasticTopNRanker")
     samples = int(samples)
-    if candidates is not None:
-        return _recommend_samples_candidates(pipe, ranker, users, n, samples, candidates,
-                                             batch_size)
-    scorer = pipe.node("scorer").component
-    reranker = _reranker(pipe)
-    if reranker is not None and not _reranks_batches(reranker, scorer) and \
-            _has_panels(scorer, pipe.node("history-lookup").component):
-        ids, idx, keys = _sample_panels(pipe, users, n, samples, batch_size)
+    scorer, reranker = _slot(pipe, "scorer"), _slot(pipe, "reranker")
+    lists = None if candidates is None else _candidate_lists(users, candidates)
+    if lists is None:
+        drawn = _draw_samples(pipe, users, n, samples, batch_size)
+    else:
+        users = lists[0]
+        drawn = _draw_samples(pipe, users, n, samples, batch_size, lists,
+                              _candidate_mode(pipe, lists[3], len(users)))
+    if drawn is None:
+        out = {}
+        for u, il in zip(users, repeat(None) if lists is None else _query_lists(lists)):
+            got = pipe.run_all("history-lookup", "scorer", query=u, items=il)
+            drew = ranker.sample(got["scorer"], got["history-lookup"], n, samples=samples)
+            if reranker is not None:
+                drew = [reranker(items=d, n=_rerank_length(n)) for d in drew]
+            out.update({(u, s): d for s, d in enumerate(drew)})
+        return ItemListCollection.from_dict(out, key=("user_id", "sample"))
+    if reranker is not None and not _reranks_batches(reranker, scorer):  # (panels only)
+        ids, idx, keys = drawn
         out = {}
         for b, u in enumerate(ids.tolist()):
             for s in range(samples):
@@ -290,59 +301,41 @@ def recommend_samples(pipe: Pipeline, users, n: int, samples: int, *, candidates
                               scores=keys[b, s][keep], ordered=True)
                 out[(u, s)] = reranker(items=il, n=_rerank_length(n))
         return ItemListCollection.from_dict(out, key=("user_id", "sample"))
-    if not _has_panels(scorer, pipe.node("history-lookup").component):
-        out = {}
-        for u in users:
-            got = pipe.run_all("history-lookup", "scorer", query=u)
-            lists = ranker.sample(got["scorer"], got["history-lookup"], n, samples=samples)
-            if reranker is not None:
-                lists = [reranker(items=il, n=_rerank_length(n)) for il in lists]
-            out.update({(u, s): il for s, il in enumerate(lists)})
-        return ItemListCollection.from_dict(out, key=("user_id", "sample"))
-    ids, idx, keys = _sample_panels(pipe, users, n, samples, batch_size)
-    pairs = [(u, s) for u in ids.tolist() for s in range(samples)]
-    flat = idx.shape[0] * idx.shape[1]
-    idx, keys = idx.reshape(flat, -1), keys.reshape(flat, -1)
-    if reranker is not None:
-        idx, keys = reranker.rerank_batch(idx, keys, _rerank_length(n))
-    return ItemListCollection.from_arrays(pairs, idx, keys, scorer.items,
-                                          key=("user_id", "sample"))
+    return _sampled_lists(drawn, scorer.items, reranker, n, key=("user_id", "sample"))
 
 
-def _recommend_samples_candidates(pipe: Pipeline, ranker, users, n, samples: int, candidates,
-                                  batch_size: int) -> ItemListCollection:
-    "``recommend_samples`` over each user's own candidate list (:func:`_recommend_candidates`)"
-    keys, offsets, item_ids, fields, lists = _candidate_lists(users, candidates)
-    node = pipe.nodes.get(pipe.aliases.get("scorer", "scorer"))
-    scorer = None if node is None else node.component
-    reranker = _reranker(pipe)
-    batched = _reranks_batches(reranker, scorer)
-    plan = _candidate_route(pipe)
-    got = None
-    if plan is not None and _samples_scores(pipe) is ranker and fields is not None and \
-            not fields and (reranker is None or batched) and len(keys):
-        got = _sample_candidates(plan, ranker, keys, offsets, item_ids, lists, n, samples,
-                                 batch_size)
-    if got is None:
-        if lists is None:
-            lists = [ItemList(item_ids=item_ids[offsets[i]:offsets[i + 1]],
-                              **{f: v[offsets[i]:offsets[i + 1]] for f, v in (fields or {}).items()})
-                     for i in range(len(keys))]
-        out = {}
-        for u, il in zip(keys, lists):
-            res = pipe.run_all("history-lookup", "scorer", query=u, items=il)
-            drawn = ranker.sample(res["scorer"], res["history-lookup"], n, samples=samples)
-            if reranker is not None:
-                drawn = [reranker(items=d, n=_rerank_length(n)) for d in drawn]
-            out.update({(u, s): d for s, d in enumerate(drawn)})
-        return ItemListCollection.from_dict(out, key=("user_id", "sample"))
-    _key_arr, idx, kk = got
-    pairs = [(u, s) for u in keys for s in range(samples)]
-    idx, kk = idx.reshape(len(pairs), -1), kk.reshape(len(pairs), -1)
+def _draw_samples(pipe: Pipeline, users, n, samples: int, batch_size: int, cand=None, mode=None):
+    """
+    ``samples`` sampled rankings per user as (user keys, item numbers [B x S x w], keys
+    [B x S x w]): off the scorer's panels (:func:`_sample_panels`), or -- ``cand``: what
+    :func:`_candidate_lists` returned, ``mode``: what :func:`_candidate_mode` says of it -- of
+    every user's own list (:func:`_sample_candidates`).  None where the caller has to go query by
+    query: a scorer without panels, candidates in another mode than ``"sample"``, lists that
+    cannot be addressed.
+    """
+    if cand is None:
+        if not _has_panels(pipe.node("scorer").component, pipe.node("history-lookup").component):
+            return None
+        return _sample_panels(pipe, users, n, samples, batch_size)
+    keys, offsets, item_ids, _fields, lists = cand
+    kind, ranker, plan = mode
+    if kind != "sample":
+        return None
+    return _sample_candidates(plan, ranker, keys, offsets, item_ids, lists, n, samples, batch_size)
+
+
+def _sampled_lists(drawn, vocab, reranker, n, *, key) -> ItemListCollection:
+    """The collection of what :func:`_draw_samples` drew: the [B·S x w] lists, through the
+    ``rerank_batch`` of a reranker (one that has it: the caller's matter), under ``key`` --
+    ``("user_id",)``, of one sample per user, or ``("user_id", "sample")``."""
+    ids, idx, kk = drawn
+    B, S, w = idx.shape
+    idx, kk = idx.reshape(B * S, w), kk.reshape(B * S, w)
     if reranker is not None:
         idx, kk = reranker.rerank_batch(idx, kk, _rerank_length(n))
-    return ItemListCollection.from_arrays(pairs, idx, kk, scorer.items,
-                                          key=("user_id", "sample"))
+    if "sample" in key:
+        ids = [(u, s) for u in ids.tolist() for s in range(S)]
+    return ItemListCollection.from_arrays(ids, idx, kk, vocab, key=key)
 
 
 def predict(pipe: Pipeline, pairs, *, batch_size: int = 16384) -> ItemListCollection:
@@ -360,22 +353,31 @@ def predict(pipe: Pipeline, pairs, *, batch_size: int = 16384) -> ItemListCollec
     composition's bit for bit (float32 of it where the biased-MF scorer alone hands out float64).
     Every other pipeline runs query by query.
     """
-    keys, offsets, item_ids, fields, lists = _ragged_pairs(pairs)
+    ragged = _ragged_pairs(pairs)
+    keys, offsets, item_ids, fields, _lists = ragged
     parts = _batched_predict_parts(pipe)
     if parts is not None and fields is not None and not (
             set(fields) & {"score", "nbr_counts", "is_fallback"}):
         return _predict_batched(parts, keys, offsets, item_ids, fields, batch_size)
     if isinstance(pairs, dict):
         return _predict_loop(pipe, pairs)
-    if lists is None:
-        lists = [ItemList(item_ids=item_ids[offsets[i]:offsets[i + 1]],
-                          **{f: v[offsets[i]:offsets[i + 1]] for f, v in fields.items()})
-                 for i in range(len(keys))]
-    return _predict_loop(pipe, dict(zip(_key_list(keys), lists)))
+    return _predict_loop(pipe, dict(zip(_key_list(keys), _query_lists(ragged))))
 
 
 def _key_list(keys) -> list:
     return [k.item() if isinstance(k, np.generic) else k for k in keys]
+
+
+def _query_lists(ragged) -> list:
+    """One ``ItemList`` per query of what :func:`_ragged_pairs` / :func:`_candidate_lists`
+    returned, for the per-query loops: the caller's own lists where there are any, else (a frame)
+    cut out of the ragged arrays with their fields."""
+    keys, offsets, item_ids, fields, lists = ragged
+    if lists is not None:
+        return lists
+    return [ItemList(item_ids=item_ids[offsets[i]:offsets[i + 1]],
+                     **{f: v[offsets[i]:offsets[i + 1]] for f, v in fields.items()})
+            for i in range(len(keys))]
 
 
 def _ragged_pairs(pairs):
@@ -460,7 +462,6 @@ def _batched_predict_parts(pipe: Pipeline):
     ds = _numbered_dataset(scorer, lookup)
     if ds is None:
         return None
-    same = _same
     rating = ds._attrs.get("rating")
     if isinstance(scorer, BiasedMFScorer):
         # trained, a bias model with both terms, ratings to fold in (the per-query path raises
@@ -488,9 +489,9 @@ def _batched_predict_parts(pipe: Pipeline):
             return None
         bias = fb.component
         model = bias.model
-        if model.items is not None and not same(model.items, ds.items):
+        if model.items is not None and not _same(model.items, ds.items):
             return None
-        if model.users is not None and (not same(model.users, ds.users) or rating is None or
+        if model.users is not None and (not _same(model.users, ds.users) or rating is None or
                                         rating.dtype != np.float32):
             return None  # (the host sums the history's own ratings: float32 in HBM)
     return scorer, lookup, bias
@@ -521,10 +522,9 @@ def _predict_batched(parts, keys, offsets, item_ids, fields, batch_size: int):
     B = len(keys)
     if B == 0:
         return ItemListCollection(("user_id",))
-    key_arr = keys if isinstance(keys, np.ndarray) else np.asarray(_key_list(keys))
+    key_arr = _as_array(keys)
     n_items = len(scorer.items)
-    nums = scorer.items.numbers(item_ids, missing="negative") if len(item_ids) else \
-        np.zeros(0, np.int32)
+    nums = _item_numbers(scorer.items, item_ids)
     total = int(offsets[-1])
     knn = hasattr(scorer, "score_history_batch")  # (else: BiasedMFScorer, UserKNNScorer)
     scores = np.empty(total, np.float32)
@@ -536,25 +536,18 @@ def _predict_batched(parts, keys, offsets, item_ids, fields, batch_size: int):
     item_biases = bias._device_item_biases() if bias is not None else None
     for s0 in range(0, B, batch_size):
         s1 = min(B, s0 + batch_size)
-        nb = s1 - s0
         lo, hi = int(offsets[s0]), int(offsets[s1])
         n = hi - lo
         hb = lookup.batch(key_arr[s0:s1])
         nohist[s0:s1] = hb.lengths == 0
         if n == 0:
             continue  # (empty target lists only: nothing to score)
-        # one upload: target offsets (int64) and item numbers (int32)
-        packed = np.empty(2 * (nb + 1) + n + (n & 1), np.int32)
-        packed[:2 * (nb + 1)] = (offsets[s0:s1 + 1] - lo).view(np.int32)
-        packed[2 * (nb + 1):2 * (nb + 1) + n] = nums[lo:hi]
-        d_packed = torch.from_numpy(packed).to(d)
-        d_ptr = d_packed[:2 * (nb + 1)].view(torch.int64)
-        d_nums = d_packed[2 * (nb + 1):2 * (nb + 1) + n]
+        h_ptr = offsets[s0:s1 + 1] - lo
+        d_ptr, d_nums = D.upload_targets(h_ptr, nums[lo:hi], d)
         if knn:
             s_dev, c_dev = scorer.score_history_batch(hb, d_ptr, d_nums)
         else:
-            s_dev = scorer.predict_history_batch(hb, d_ptr, d_nums,
-                                                 h_tgt_ptr=offsets[s0:s1 + 1] - lo)
+            s_dev = scorer.predict_history_batch(hb, d_ptr, d_nums, h_tgt_ptr=h_ptr)
         out = torch.empty(9 * n, dtype=torch.uint8, device=d)  # scores | counts | flags
         if bias is not None:
             ub, add = bias.user_offsets_batch(hb)
@@ -572,14 +565,23 @@ def _predict_batched(parts, keys, offsets, item_ids, fields, batch_size: int):
             counts[lo:hi] = host[4 * n:8 * n].view(np.int32)
         if fb is not None:
             fb[lo:hi] = host[8 * n:].view(np.bool_)
+    return _scored_lists(keys, offsets, item_ids, fields, scores, counts, nohist, fb)
+
+
+def _scored_lists(keys, offsets, item_ids, fields, scores, counts=None, nohist=None,
+                  is_fallback=None) -> ItemListCollection:
+    """The result of ``predict`` / ``score``: the caller's ids and fields, then ``nbr_counts``
+    (where there are ``counts``; absent from the lists of the queries ``nohist`` flags, those
+    without history), ``score``, and ``is_fallback`` last (where there are flags)."""
     out_fields = dict(fields)
-    if knn:
+    if counts is not None:
         out_fields["nbr_counts"] = counts
     out_fields["score"] = scores
-    if fb is not None:
-        out_fields["is_fallback"] = fb
-    return ItemListCollection.from_ragged(keys, offsets, item_ids, out_fields, key=("user_id",),
-                                          absent={"nbr_counts": nohist} if knn else None)
+    if is_fallback is not None:
+        out_fields["is_fallback"] = is_fallback
+    return ItemListCollection.from_ragged(
+        keys, offsets, item_ids, out_fields, key=("user_id",),
+        absent=None if counts is None else {"nbr_counts": nohist})
 
 
 def _predict_loop(pipe: Pipeline, pairs: dict) -> ItemListCollection:
@@ -623,16 +625,16 @@ def _candidate_route(pipe: Pipeline):
 
     Follow-up work, today through the loop: ``BiasedMFScorer`` (its ``__call__`` is float64 on the
     host; ``lk_bmf_finish_ragged`` is the finish its route will take).  Which RANKERS run batched
-    over a route is :func:`_recommend_candidates`'s matter.
+    over a route is :func:`_candidate_mode`'s matter.
     """
     from .knn import EASEScorer, ItemKNNScorer, UserKNNScorer
 
-    node = pipe.nodes.get(pipe.aliases.get("scorer", "scorer"))
-    scorer = None if node is None else node.component
+    scorer = _slot(pipe, "scorer")
     lookup_node = pipe.nodes.get("history-lookup")
     if scorer is None or lookup_node is None:
         return None
-    cand = pipe.nodes.get(node.wiring.get("items"))
+    node = pipe.node("scorer")
+    cand =pipe.nodes.get(node.wiring.get("items"))
     unwired = "query" not in node.wiring and getattr(scorer, "ignores_query", False)
     if (node.wiring.get("query") != "history-lookup" and not unwired) or cand is None or \
             cand.kind != "first-of" or cand.wiring["sources"][:1] != ["items"]:
@@ -694,21 +696,11 @@ def _scored_batches(plan, key_arr, offsets, nums, batch_size: int, *, with_count
         yield s0, s1, lo, hi, hb, h_ptr, d_ptr, d_nums, s_dev, counts
 
 
-def _item_numbers(scorer, item_ids) -> np.ndarray:
+def _item_numbers(vocab, item_ids) -> np.ndarray:
+    "the ids' numbers in ``vocab`` as int32, negative for an id it does not hold"
     if len(item_ids) == 0:
         return np.zeros(0, np.int32)
-    return np.ascontiguousarray(scorer.items.numbers(item_ids, missing="negative"), np.int32)
-
-
-def _ranks_scores(pipe: Pipeline):
-    "the pipeline's ranker when it is a plain ``TopNRanker`` over the scorer's output, else None"
-    from .basic import TopNRanker
-
-    node = pipe.nodes.get(pipe.aliases.get("ranker", "ranker"))
-    if node is None or type(node.component) is not TopNRanker or \
-            node.wiring.get("items") != pipe.aliases.get("scorer", "scorer"):
-        return None
-    return node.component
+    return np.ascontiguousarray(vocab.numbers(item_ids, missing="negative"), np.int32)
 
 
 def _candidate_lists(users, candidates):
@@ -720,7 +712,7 @@ def _candidate_lists(users, candidates):
     keys, offsets, item_ids, fields, lists = _ragged_pairs(candidates)
     keys = _key_list(keys)
     if users is not None:
-        users = _key_list(users if isinstance(users, np.ndarray) else list(users))
+        users = _key_list(users)
         pos = {k: i for i, k in enumerate(keys)}
         for u in users:
             if u not in pos:
@@ -739,13 +731,40 @@ def _candidate_lists(users, candidates):
     return keys, offsets, item_ids, fields, lists
 
 
-def _samples_scores(pipe: Pipeline):
-    "the pipeline's ranker when it is a ``StochasticTopNRanker`` over the scorer's output, else None"
-    ranker = _stochastic_ranker(pipe)
-    if ranker is None:
-        return None
-    node = pipe.nodes[pipe.aliases.get("ranker", "ranker")]
-    return ranker if node.wiring.get("items") == pipe.aliases.get("scorer", "scorer") else None
+def _candidate_mode(pipe: Pipeline, fields, n_lists: int):
+    """
+    How a call over candidate lists runs, as (mode, ranker, route): ``fields`` is the lists' own
+    fields (None: they differ from list to list), ``n_lists`` how many lists there are.
+
+    - ``"random"``: an empty scorer slot, a ``RandomSelector`` and no reranker, lists with the
+      same fields, at least one -- :func:`_random_candidates` is tried;
+    - ``"topn"``: a route (:func:`_candidate_route`), lists without fields, no reranker or one that
+      takes batches (``_reranks_batches``), and a ranker that is exactly a ``TopNRanker`` over the
+      scorer's output (a subclass may rank otherwise) -- also with no list at all;
+    - ``"sample"``: the same under a ``StochasticTopNRanker`` over the scorer's output, at least
+      one list -- :func:`_sample_candidates` is tried;
+    - ``"loop"``: everything else, query by query (``ranker`` and ``route`` are None).
+
+    ``"random"`` and ``"sample"`` may still end in the loop: for another wiring than
+    ``random_pipeline``'s, or lists :func:`_candidate_addresses` cannot pack.
+    """
+    scorer = _slot(pipe, "scorer")
+    reranker = _slot(pipe, "reranker")
+    if scorer is None:
+        selector = _ranker(pipe, RandomSelector)
+        if selector is not None and reranker is None and fields is not None and n_lists:
+            return "random", selector, None
+        return "loop", None, None
+    plan = _candidate_route(pipe)
+    if plan is not None and fields == {} and \
+            (reranker is None or _reranks_batches(reranker, scorer)):
+        ranker = _ranker(pipe, TopNRanker, exact=True, over_scorer=True)
+        if ranker is not None:
+            return "topn", ranker, plan
+        ranker = _ranker(pipe, StochasticTopNRanker, over_scorer=True)
+        if ranker is not None and n_lists:
+            return "sample", ranker, plan
+    return "loop", None, None
 
 
 def _candidate_addresses(lists, offsets, numbers, vocab):
@@ -820,8 +839,8 @@ def _sample_candidates(plan, ranker, keys, offsets, item_ids, lists, n, samples:
 
     scorer, lookup, _route = plan
     B = len(keys)
-    key_arr = np.asarray(keys)
-    nums = _item_numbers(scorer, item_ids)
+    key_arr = _as_array(keys)
+    nums = _item_numbers(scorer.items, item_ids)
     packed = _candidate_addresses(lists, offsets, nums, scorer.items)
     if packed is None:
         return None
@@ -872,7 +891,7 @@ def _random_candidates(pipe: Pipeline, selector, keys, offsets, item_ids, fields
     (:func:`_candidate_addresses`: by the vocabulary the lists carry, else by position) that
     cannot be packed.
     """
-    node = pipe.nodes[pipe.aliases.get("ranker", "ranker")]
+    node = pipe.node("ranker")
     cand = pipe.nodes.get(node.wiring.get("items"))
     lookup_node = pipe.nodes.get("history-lookup")
     if cand is None or cand.kind != "first-of" or cand.wiring["sources"][:1] != ["items"] or \
@@ -882,18 +901,14 @@ def _random_candidates(pipe: Pipeline, selector, keys, offsets, item_ids, fields
     vocab = None
     if lists is not None:
         vocab = next((il.vocabulary for il in lists if len(il)), None)
-    if vocab is not None:
-        numbers = vocab.numbers(item_ids, missing="negative") if len(item_ids) else \
-            np.zeros(0, np.int32)
-    else:
-        numbers = _item_codes(item_ids)
+    numbers = _item_codes(item_ids) if vocab is None else _item_numbers(vocab, item_ids)
     packed = _candidate_addresses(lists, offsets, numbers, vocab)
     if packed is None:
         return None
     addr, widths, order = packed
     B, total = len(keys), int(offsets[-1])
     n = selector._length(n)
-    key_arr = np.asarray(keys)
+    key_arr = _as_array(keys)
     streams = selector.streams(lookup_node.component.batch(key_arr).user_ids)
     # the result carries each picked entry's position in the caller's arrays
     where = np.arange(total, dtype=np.int32) if order is None else order.astype(np.int32)
@@ -942,44 +957,28 @@ def _recommend_candidates(pipe: Pipeline, users, n, candidates, batch_size: int,
     drawing rankers the lists :func:`_candidate_addresses` cannot pack -- a repeated item,
     another vocabulary than the scorer's, lists with and without a vocabulary.
     """
-    keys, offsets, item_ids, fields, lists = _candidate_lists(users, candidates)
-    node = pipe.nodes.get(pipe.aliases.get("scorer", "scorer"))
-    scorer = None if node is None else node.component
-    reranker = _reranker(pipe)
+    ragged = _candidate_lists(users, candidates)
+    keys, offsets, item_ids, fields, lists = ragged
+    scorer = _slot(pipe, "scorer")
+    reranker = _slot(pipe, "reranker")
     if scorer is None and rerank_depth is not None:
         raise ValueError("rerank_depth does not apply to a random selection")
-    batched = _check_rerank_depth(pipe, reranker, scorer, n, rerank_depth)
-    ranker = _ranks_scores(pipe)
-    plan = _candidate_route(pipe)
-    out = None
-    if scorer is None:
-        selector = _random_selector(pipe)
-        if selector is not None and reranker is None and fields is not None and len(keys):
-            out = _random_candidates(pipe, selector, keys, offsets, item_ids, fields, lists, n,
-                                     batch_size)
-    elif ranker is None and plan is not None and fields is not None and not fields and \
-            (reranker is None or batched) and len(keys):
-        sampler = _samples_scores(pipe)
-        got = None if sampler is None else _sample_candidates(
-            plan, sampler, keys, offsets, item_ids, lists, n, 1, batch_size)
-        if got is not None:
-            key_arr, idx, sc = got
-            idx, sc = idx[:, 0], sc[:, 0]
-            if batched:
-                idx, sc = reranker.rerank_batch(idx, sc, _rerank_length(n))
-            out = ItemListCollection.from_arrays(key_arr, idx, sc, scorer.items,
-                                                 key=("user_id",))
+    _check_rerank_depth(pipe, reranker, scorer, n, rerank_depth)
+    mode, ranker, plan = _candidate_mode(pipe, fields, len(keys))
+    out = None  # (in every mode but "loop" the reranker, if there is one, takes batches)
+    if mode == "random":
+        out = _random_candidates(pipe, ranker, keys, offsets, item_ids, fields, lists, n,
+                                 batch_size)
+    elif mode == "sample":
+        drawn = _draw_samples(pipe, keys, n, 1, batch_size, ragged, (mode, ranker, plan))
+        if drawn is not None:
+            out = _sampled_lists(drawn, scorer.items, reranker, n, key=("user_id",))
     if out is not None:
         return out
-    if plan is None or ranker is None or fields is None or fields or \
-            (reranker is not None and not batched):
-        if lists is None:
-            lists = [ItemList(item_ids=item_ids[offsets[i]:offsets[i + 1]],
-                              **{f: v[offsets[i]:offsets[i + 1]] for f, v in (fields or {}).items()})
-                     for i in range(len(keys))]
+    if mode != "topn":
         return ItemListCollection.from_dict(
-            {u: pipe.run("recommender", query=u, items=il, n=n) for u, il in zip(keys, lists)},
-            key=("user_id",))
+            {u: pipe.run("recommender", query=u, items=il, n=n)
+             for u, il in zip(keys, _query_lists(ragged))}, key=("user_id",))
 
     from . import _device as D
 
@@ -990,8 +989,8 @@ def _recommend_candidates(pipe: Pipeline, users, n, candidates, batch_size: int,
     length = -1 if length < 0 else int(length)
     depth = length if rerank_depth is None else int(rerank_depth)
     width = int(np.diff(offsets).max()) if depth < 0 else depth
-    key_arr = np.asarray(keys)
-    nums = _item_numbers(scorer, item_ids)
+    key_arr = _as_array(keys)
+    nums = _item_numbers(scorer.items, item_ids)
     idx = np.full((B, width), -1, np.int32)
     sc = np.full((B, width), np.nan, np.float32)
     if width:
@@ -1004,7 +1003,7 @@ def _recommend_candidates(pipe: Pipeline, users, n, candidates, batch_size: int,
                 i, v = D.lists_to_host(i_dev, v_dev)
                 idx[s0:s1, :i.shape[1]] = i
                 sc[s0:s1, :i.shape[1]] = v
-    if batched:
+    if reranker is not None:
         idx, sc = reranker.rerank_batch(idx, sc, _rerank_length(n))
     return ItemListCollection.from_arrays(key_arr, idx, sc, scorer.items, key=("user_id",))
 
@@ -1026,16 +1025,13 @@ def score(pipe: Pipeline, test, *, batch_size: int = 16384) -> ItemListCollectio
     ``score`` or ``nbr_counts``, lists with differing fields, a scorer without a route and
     vocabularies that disagree go through ``pipe.run`` query by query.
     """
-    keys, offsets, item_ids, fields, lists = _ragged_pairs(test)
+    ragged = _ragged_pairs(test)
+    keys, offsets, item_ids, fields, _lists = ragged
     plan = _candidate_route(pipe)
     if plan is None or fields is None or set(fields) & {"score", "nbr_counts"}:
-        if lists is None:
-            lists = [ItemList(item_ids=item_ids[offsets[i]:offsets[i + 1]],
-                              **{f: v[offsets[i]:offsets[i + 1]] for f, v in fields.items()})
-                     for i in range(len(keys))]
         return ItemListCollection.from_dict(
-            {u: pipe.run("scorer", query=u, items=il) for u, il in zip(_key_list(keys), lists)},
-            key=("user_id",))
+            {u: pipe.run("scorer", query=u, items=il)
+             for u, il in zip(_key_list(keys), _query_lists(ragged))}, key=("user_id",))
 
     import torch
 
@@ -1045,8 +1041,8 @@ def score(pipe: Pipeline, test, *, batch_size: int = 16384) -> ItemListCollectio
     B = len(keys)
     if B == 0:
         return ItemListCollection(("user_id",))
-    key_arr = keys if isinstance(keys, np.ndarray) else np.asarray(_key_list(keys))
-    nums = _item_numbers(scorer, item_ids)
+    key_arr = _as_array(keys)
+    nums = _item_numbers(scorer.items, item_ids)
     total = int(offsets[-1])
     knn = isinstance(scorer, ItemKNNScorer)
     scores = np.empty(total, np.float32)
@@ -1063,9 +1059,4 @@ def score(pipe: Pipeline, test, *, batch_size: int = 16384) -> ItemListCollectio
             counts[lo:hi] = host[hi - lo:]
         else:
             scores[lo:hi] = s_dev.cpu().numpy()
-    out_fields = dict(fields)
-    if knn:
-        out_fields["nbr_counts"] = counts
-    out_fields["score"] = scores
-    return ItemListCollection.from_ragged(keys, offsets, item_ids, out_fields, key=("user_id",),
-                                          absent={"nbr_counts": nohist} if knn else None)
+    return _scored_lists(keys, offsets, item_ids, fields, scores, counts, nohist)
