@@ -1570,6 +1570,32 @@ int lk_hpf_loglik_rows(const void *d_indptr, int indptr_is_64, const int32_t *d_
                        const float *d_theta, const float *d_beta, int32_t k, int32_t ld,
                        double *d_out, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Non-negative matrix factorization (csrc/nmf.hip): the coordinate sweep of `NMFScorer.train`
+ * (src/lenskit/sklearn/nmf.py:72-110), which in the reference is sklearn's
+ * `non_negative_factorization` -> `_fit_coordinate_descent` -> `_update_cdnmf_fast`.  One
+ * half-iteration is lk_gramian (`HHt = Ht^T Ht + l2_reg I`), lk_csr_spmm (`XHt = X Ht`) and
+ *
+ * lk_nmf_cd_sweep: d_w [n x ld] (updated in place) and d_xht [n x ld] are padded float32 panels,
+ *   ld = lk_padded_dim(k), 1 <= k <= lk_nmf_max_k() = 128; d_hht is [k x k] with leading dimension
+ *   ld_hht.  With x = d_xht - l1_reg (rounded once), for every row i and t = 0 .. k-1 in order:
+ *     grad = -x[i][t];  grad += d_hht[t][r] * d_w[i][r] for r = 0 .. k-1, product and sum rounded
+ *     separately (no fused multiply-add, no tree; the division is IEEE);
+ *     pg = d_w[i][t] == 0 ? min(0, grad) : grad;
+ *     d_w[i][t] = max(d_w[i][t] - grad / d_hht[t][t], 0) unless d_hht[t][t] == 0.
+ *   The rows are independent, so d_w has the bits of sklearn's float32 loop.  The pad columns of
+ *   d_w are written as zero.  *d_violation (float64, device) receives the sum of |pg| over all
+ *   rows and coordinates: float64 sums in a fixed order (coordinate order in a row, row order in a
+ *   block of 64 rows, then the blocks), no floating-point atomics -- a function of the operands
+ *   alone, but not sklearn's sequential float32 sum.  d_ws: lk_nmf_workspace_bytes(n) bytes.
+ *   Asynchronous on `stream`.
+ * ---------------------------------------------------------------------- */
+int32_t lk_nmf_max_k(void);
+size_t lk_nmf_workspace_bytes(int64_t n);
+int lk_nmf_cd_sweep(float *d_w, int64_t n, int32_t k, int32_t ld, const float *d_hht,
+                    int32_t ld_hht, const float *d_xht, float l1_reg, double *d_violation,
+                    void *d_ws, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

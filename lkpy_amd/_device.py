@@ -3314,3 +3314,105 @@ class HPFState:
     def host_factors(self) -> tuple[np.ndarray, np.ndarray]:
         "(theta [users x k], beta [items x k]) on the host"
         return to_host_unpadded(self.theta, self.k), to_host_unpadded(self.beta, self.k)
+
+
+# ---- non-negative matrix factorization (csrc/nmf.hip) ----------------------------------------
+def nmf_max_k() -> int:
+    "The largest ``k`` ``lk_nmf_cd_sweep`` serves (lk_nmf_max_k)."
+    return int(_native.load().lk_nmf_max_k())
+
+
+def nmf_cd_sweep(w: torch.Tensor, hht: torch.Tensor, xht: torch.Tensor, l1_reg: float,
+                 out: torch.Tensor | None = None, ws: torch.Tensor | None = None) -> torch.Tensor:
+    """
+    One coordinate sweep over the rows of the padded panel ``w`` [n x KP], in place
+    (lk_nmf_cd_sweep: sklearn's ``_update_cdnmf_fast`` in float32, bit for bit): ``hht`` [k x k]
+    is ``Ht^T Ht + l2_reg I`` and ``xht`` [n x KP] the padded ``X Ht``, from which ``l1_reg`` is
+    subtracted.  Returns the sweep's violation ``sum |pg|`` as a device float64 [1] (``out``, if
+    given); nothing is read back here.  ``ValueError`` for a ``k`` above :func:`nmf_max_k`.
+    """
+    lib = _native.require_gpu()
+    k = int(hht.shape[0])
+    if not 1 <= k <= nmf_max_k():
+        raise ValueError(f"nmf_cd_sweep: k = {k} outside 1..lk_nmf_max_k() = {nmf_max_k()}")
+    kp = padded_dim(k)
+    n = int(w.shape[0])
+    assert w.dtype == torch.float32 and w.is_contiguous() and tuple(w.shape) == (n, kp)
+    assert xht.dtype == torch.float32 and xht.is_contiguous() and tuple(xht.shape) == (n, kp)
+    assert hht.dtype == torch.float32 and hht.shape[1] == k and hht.stride(1) == 1
+    if out is None:
+        out = torch.empty(1, dtype=torch.float64, device=w.device)
+    assert out.dtype == torch.float64 and out.numel() == 1
+    need = lib.lk_nmf_workspace_bytes(n)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=w.device)
+    check(lib.lk_nmf_cd_sweep(_ptr(w), n, k, kp, _ptr(hht), hht.stride(0), _ptr(xht),
+                              float(l1_reg), _ptr(out), _ptr(ws), _stream()), "lk_nmf_cd_sweep")
+    return out
+
+
+def nmf_fit(csr: DeviceCSR, csr_t: DeviceCSR, w0: np.ndarray, h0: np.ndarray, max_iter: int,
+            tol: float, l1_w: float = 0.0, l1_h: float = 0.0, l2_w: float = 0.0,
+            l2_h: float = 0.0, *, stats: dict | None = None):
+    """
+    Frobenius NMF by coordinate descent, sklearn's ``_fit_coordinate_descent`` in float32: from
+    ``w0`` [n_rows x k] and ``h0`` [k x n_cols], every iteration updates W (``HHt = Ht^T Ht + l2_w
+    I`` by lk_gramian, ``XHt = X Ht`` by lk_csr_spmm, then lk_nmf_cd_sweep with ``l1_w``) and then
+    Ht the same way on ``csr_t`` (:func:`csr_transpose`, formed once) with W.  The violation of an
+    iteration is the sum of its two sweeps'; the fit stops when the first iteration's is 0 or once
+    ``violation / violation_init <= tol`` -- the two float64 values are the one read-back of an
+    iteration.
+
+    Returns (W f32 [n_rows x k], H f32 [k x n_cols], n_iter, the violations of the iterations run)
+    on the host.  ``stats`` (a dict, for the timing tool): the stream is synchronised around every
+    step and the dict receives the seconds spent in ``gramian``, ``spmm`` and ``sweep``.
+    """
+    from time import perf_counter
+
+    n_rows, n_cols = csr.shape
+    w0 = np.ascontiguousarray(w0, dtype=np.float32)
+    ht0 = np.ascontiguousarray(np.asarray(h0, dtype=np.float32).T)
+    k = w0.shape[1]
+    if not 1 <= k <= nmf_max_k():
+        raise ValueError(f"nmf_fit: k = {k} outside 1..lk_nmf_max_k() = {nmf_max_k()}")
+    if w0.shape != (n_rows, k) or ht0.shape != (n_cols, k):
+        raise ValueError(f"nmf_fit: the start {w0.shape} x {ht0.T.shape} does not fit the "
+                         f"matrix {csr.shape}")
+    if tuple(csr_t.shape) != (n_cols, n_rows) or csr_t.nnz != csr.nnz:
+        raise ValueError("nmf_fit: csr_t is not the transpose of csr")
+    dev = csr.indices.device
+    w, ht = to_device_padded(w0, dev), to_device_padded(ht0, dev)
+    gramian = Gramian(k, dev)
+    hht = torch.empty((k, k), dtype=torch.float32, device=dev)
+    viol = torch.empty(2, dtype=torch.float64, device=dev)
+    ws = torch.empty(_native.load().lk_nmf_workspace_bytes(max(n_rows, n_cols)),
+                     dtype=torch.uint8, device=dev)
+    if stats is not None:
+        stats.update(gramian=0.0, spmm=0.0, sweep=0.0)
+
+    def step(key, fn, *a):
+        if stats is None:
+            return fn(*a)
+        torch.cuda.synchronize(dev)
+        t0 = perf_counter()
+        out = fn(*a)
+        torch.cuda.synchronize(dev)
+        stats[key] += perf_counter() - t0
+        return out
+
+    def half(mat, this, other, l1, l2, out):
+        step("gramian", gramian, other, l2, hht)
+        xht = step("spmm", csr_spmm, mat, other, k)
+        step("sweep", nmf_cd_sweep, this, hht, xht, l1, out, ws)
+
+    history: list[float] = []
+    n_iter = 0
+    for n_iter in range(1, int(max_iter) + 1):
+        half(csr, w, ht, l1_w, l2_w, viol[0:1])
+        half(csr_t, ht, w, l1_h, l2_h, viol[1:2])
+        v = viol.cpu().numpy()
+        history.append(float(v[0] + v[1]))
+        if history[0] == 0 or history[-1] / history[0] <= tol:
+            break
+    return (to_host_unpadded(w, k), np.ascontiguousarray(to_host_unpadded(ht, k).T), n_iter,
+            np.asarray(history, dtype=np.float64))

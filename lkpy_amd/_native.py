@@ -400,6 +400,11 @@ def _declare(lib):
         "lk_hpf_loglik_rows": (
             c_int, [vp, c_int, vp, vp, c_int64, c_int64, c_int64, vp, vp, c_int32, c_int32, vp, vp]
         ),
+        "lk_nmf_max_k": (c_int32, []),
+        "lk_nmf_workspace_bytes": (c_size_t, [c_int64]),
+        "lk_nmf_cd_sweep": (
+            c_int, [vp, c_int64, c_int32, c_int32, vp, c_int32, vp, c_float, vp, vp, vp]
+        ),
         "lk_als_implicit_half_epoch_host": (
             c_int,
             [vp, c_int, vp, vp, c_int64, c_int64, c_int32, vp, vp, vp, c_int32, vp],
