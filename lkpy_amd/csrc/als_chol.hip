@@ -909,9 +909,26 @@ __host__ __device__ constexpr int hybrid_lds_floats()
     return LPack<NT * 16>::SIZE + NT * 16 + 256;
 }
 
+// The lane sets of the solver are compile-time constants: 64-bit masks that the scalar unit moves
+// into an SGPR pair (`__builtin_amdgcn_inverse_ballot_w64`), where `lane > j` cost a v_cmp each.
+// lanes_above(j): the lanes j + 1 .. 63; lanes_below(j): the lanes 0 .. j - 1.
+__host__ __device__ constexpr unsigned long long lanes_above(int j)
+{
+    return j >= 63 ? 0ull : ~0ull << (j + 1);
+}
+__host__ __device__ constexpr unsigned long long lanes_below(int j)
+{
+    return j >= 64 ? ~0ull : (1ull << j) - 1;
+}
+static_assert(lanes_above(-1) == ~0ull && lanes_above(0) == ~1ull && lanes_above(62) == 1ull << 63 &&
+                  lanes_above(63) == 0 && lanes_below(0) == 0 && lanes_below(63) == ~0ull >> 1 &&
+                  lanes_below(64) == ~0ull,
+              "lane masks: lane > j and lane < j for every j the solver asks");
+
 template <int NT, int M>
 __device__ __forceinline__ void hybrid_step(Gram<NT> &G, float &b, float &minpiv,
-                                            float *__restrict__ lds, const int lane)
+                                            float *__restrict__ lds, const int lane, const int ew,
+                                            const int rz)
 {
     constexpr int KP = NT * 16, J = 4 * M, TJ = M >> 2, MG = M & 3;
     using P = LPack<KP>;
@@ -922,13 +939,14 @@ __device__ __forceinline__ void hybrid_step(Gram<NT> &G, float &b, float &minpiv
     // E. extraction
 #pragma unroll
     for (int t = TJ; t < NT; ++t)
-        if (slot == MG)
-            *reinterpret_cast<f32x4 *>(&scr[(t * 16 + (lane & 15)) * 4]) = G.t[tidx(TJ, t)];
+        if (slot == MG)  // (ew = 4 (lane & 15), held in a register: the tile is an immediate)
+            *reinterpret_cast<f32x4 *>(&scr[t * 64 + ew]) = G.t[tidx(TJ, t)];
     // (the zeroed quad and the masked read stay: with every lane reading -- the lanes left of the
-    // panel would get stale words that `lane > j` discards below -- the half-epoch no longer
-    // reproduced its recorded bits, for a reason not found: DESIGN.md section 4.1d)
+    // panel would get stale words that the column masks discard below -- the half-epoch once no
+    // longer reproduced its recorded bits, for a reason not found: DESIGN.md sections 4.1d, 4.1f)
     f32x4 pv = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (slot >= TJ && lane < KP) pv = *reinterpret_cast<const f32x4 *>(&scr[lane * 4]);
+    if (__builtin_amdgcn_inverse_ballot_w64(lanes_above(16 * TJ - 1) & lanes_below(KP)))
+        pv = *reinterpret_cast<const f32x4 *>(&scr[lane * 4]);
     float pr[4] = {pv.x, pv.y, pv.z, pv.w};
 
     // F. the four columns
@@ -943,9 +961,10 @@ __device__ __forceinline__ void hybrid_step(Gram<NT> &G, float &b, float &minpiv
         // the same value to the same word; at KP = 64 every lane stores its lj at the column's
         // base + lane -- LPack says where the lanes outside the stored segment land; narrower
         // systems leave lanes past KP, which aim at their own word of the extraction scratch,
-        // dead until the next panel)
-        rinvarr[j] = rinv;
-        const float lj = (lane > j) ? pr[s0] * rinv : 0.f;  // strictly-lower column j
+        // dead until the next panel; rz = 0 in a register spares a v_mov_b32 of the base per panel)
+        rinvarr[j + rz] = rinv;
+        // strictly-lower column j: exactly +0 in the lanes at and above the diagonal
+        const float lj = __builtin_amdgcn_inverse_ballot_w64(lanes_above(j)) ? pr[s0] * rinv : 0.f;
         if (j + 1 < KP) {
             if constexpr (KP == 64) {
                 lds[P::off(j) - P::c0(j) + lane] = lj;
@@ -984,9 +1003,10 @@ __device__ __forceinline__ void hybrid_step(Gram<NT> &G, float &b, float &minpiv
 template <int NT, int... Ms>
 __device__ __forceinline__ void hybrid_steps(Gram<NT> &G, float &b, float &minpiv,
                                              float *__restrict__ lds, const int lane,
+                                             const int ew, const int rz,
                                              std::integer_sequence<int, Ms...>)
 {
-    (hybrid_step<NT, Ms>(G, b, minpiv, lds, lane), ...);
+    (hybrid_step<NT, Ms>(G, b, minpiv, lds, lane, ew, rz), ...);
 }
 
 // G: accumulator tiles of A' and the right-hand side (every lane: y'[16 t + sub]).  Returns
@@ -1010,7 +1030,11 @@ __device__ __forceinline__ float hybrid_solve(Gram<NT> &G, float &b, float *__re
 #pragma unroll
     for (int tt = 0; tt < NT; ++tt) b = ((lane >> 4) == tt) ? G.y[tt] : b;
     float minpiv = 3.0e38f;
-    hybrid_steps<NT>(G, b, minpiv, lds, lane, std::make_integer_sequence<int, KP / 4>{});
+    // word of this lane's quad in a tile's part of the extraction scratch, and a zero: opaque, so
+    // that the addresses made of them are formed once and not again in every panel
+    int ew = (lane & 15) * 4, rz = 0;
+    asm volatile("" : "+v"(ew), "+v"(rz));
+    hybrid_steps<NT>(G, b, minpiv, lds, lane, ew, rz, std::make_integer_sequence<int, KP / 4>{});
 #ifdef LK_ALS_PHASES
     asm volatile("" : "+v"(b));
     *tmid = __builtin_amdgcn_s_memtime();
@@ -1022,8 +1046,11 @@ __device__ __forceinline__ float hybrid_solve(Gram<NT> &G, float &b, float *__re
     const float *mycol = lds + P::off(lane) - my_c0;
 #pragma unroll
     for (int j4 = KP / 4 - 1; j4 >= 0; --j4) {
+        // (lane < KP - 1 && 4 * j4 >= my_c0: the lanes 0 .. min(4 j4 + 2, KP - 2))
+        const int top = 4 * j4 + 3 < KP - 1 ? 4 * j4 + 3 : KP - 1;
         f32x4 l4 = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (lane < KP - 1 && 4 * j4 >= my_c0) l4 = *reinterpret_cast<const f32x4 *>(mycol + 4 * j4);
+        if (__builtin_amdgcn_inverse_ballot_w64(lanes_below(top)))
+            l4 = *reinterpret_cast<const f32x4 *>(mycol + 4 * j4);
 #pragma unroll
         for (int u = 3; u >= 0; --u) {
             const int j = 4 * j4 + u;

@@ -39,7 +39,10 @@ def transpose4(x):
     return [y0, y1, y2, y3]
 
 
-def solve(A, y):
+def solve(A, y, read_all=False, poison=0.0):
+    """read_all: the extraction as section 4.1d tried it -- every lane reads its quad of the scratch,
+    the lanes left of the panel get whatever lies there (`poison` to begin with, stale panels
+    later) and rely on `lane > j` to discard it."""
     KP = A.shape[0]
     NT = KP // 16
     f = np.float32
@@ -54,7 +57,7 @@ def solve(A, y):
     SIZE = KP * KP // 2 + KP
     img = np.full(SIZE, np.nan, f)
     rinvarr = np.zeros(KP, f)
-    scr = np.zeros(4 * 64, f)
+    scr = np.full(4 * 64, poison, f)
     minpiv = f(3e38)
     for m in range(KP // 4):
         J, tj, mg = 4 * m, m >> 2, m & 3
@@ -65,7 +68,8 @@ def solve(A, y):
                 scr[((t * 16 + SUB) * 4 + r)[w]] = T[tidx(tj, t)][w, r]
         pr = [scr[(SLOT * 16 + SUB) * 4 + s].copy() for s in range(4)]
         live = (SLOT >= tj) & (LANES < KP)
-        pr = [np.where(live, v, f(0)).astype(f) for v in pr]
+        if not read_all:
+            pr = [np.where(live, v, f(0)).astype(f) for v in pr]
         lp = [None] * 4
         for s0 in range(4):
             j = J + s0
@@ -77,9 +81,10 @@ def solve(A, y):
             w = (LANES >= c0(j)) & (LANES < KP)
             img[(off(j, KP) + LANES - c0(j))[w]] = lj[w]
             zj = b[j] * rinv
-            b = b - lj * zj
-            for s in range(s0 + 1, 4):
-                pr[s] = pr[s] - lj * lj[J + s]
+            with np.errstate(invalid="ignore"):
+                b = b - lj * zj
+                for s in range(s0 + 1, 4):
+                    pr[s] = pr[s] - lj * lj[J + s]
             lp[s0] = lj
         q = transpose4(lp)
         for ti in range(tj, NT):
@@ -90,9 +95,11 @@ def solve(A, y):
     b = b * dinv  # z
     my_c0 = (lane + 1) & ~3
     for j4 in range(KP // 4 - 1, -1, -1):
+        # (lane < KP - 1 and 4 j4 >= c0(lane): the constant lane set 0 .. min(4 j4 + 2, KP - 2))
         l4 = np.zeros((64, 4), f)
         for i in range(64):
-            if i < KP - 1 and 4 * j4 >= my_c0[i]:
+            if i <= min(4 * j4 + 2, KP - 2):
+                assert 4 * j4 >= my_c0[i]
                 base = off(i, KP) - my_c0[i] + 4 * j4
                 l4[i] = img[base:base + 4]
         for u in range(3, -1, -1):
@@ -113,6 +120,11 @@ def main():
             A = (M.T @ M + 0.5 * np.eye(KP)).astype(np.float32)
             y = rng.standard_normal(KP).astype(np.float32)
             x, mp = solve(A, y)
+            # section 4.1f: in this model the unmasked extraction changes no bit, whatever the
+            # dead words of the scratch hold
+            for poison in (0.0, 1.0e30, np.inf, np.nan):
+                x2, mp2 = solve(A, y, read_all=True, poison=poison)
+                assert x2.tobytes() == x.tobytes() and mp2 == mp, poison
             ref = np.linalg.solve(A.astype(np.float64), y.astype(np.float64))
             err = np.linalg.norm(x - ref) / np.linalg.norm(ref)
             print(KP, trial, "rel err %.2e" % err, "minpiv %.3g" % mp)
