@@ -571,6 +571,51 @@ int lk_predict_merge(int64_t n_queries, const int64_t *d_tgt_ptr, const int32_t 
                      const uint8_t *d_user_add, uint8_t *d_out_is_fallback, void *stream);
 
 /* ------------------------------------------------------------------------
+ * The bias model on the device (csrc/bias.hip): the fit of `BiasModel.learn`
+ * (src/lenskit/basic/bias.py:83-150) and `BiasScorer`'s score for whole batches.  All calls are
+ * asynchronous on `stream`; there is no atomic in any of them.
+ *
+ * lk_bias_fit_pass is ONE pass of the fit over the bins of a CSR (offsets i32/i64; a bin is a
+ *   row): the item pass over the transposed ratings (lk_csr_transpose is stable, so an item's
+ *   entries are in dataset order), the user pass over the ratings themselves.  For bin b, in the
+ *   order of its entries e,
+ *     c[e]  = d_values[e] -f32 (float)global_bias  [-f32 d_sub[d_indices[e]]]   (d_sub NULL: no
+ *             second term; d_indices is read only with d_sub, n_sub = its length)
+ *     sum   = 0.0 + (double)c[e0] + (double)c[e1] + ...     one float64 chain, never reassociated
+ *     count = damping + 1.0 + 1.0 + ...                      a chain too: NOT damping + n
+ *     d_out[b] = (float)(sum / count) where count > 0, else 0
+ *   which are the bits of the host's `np.add.at` / `np.divide(..., where=counts > 0)`.  A bin of at
+ *   most lk_bias_fit_short_max() entries is summed by one lane, a longer one by one wave that
+ *   loads lk_bias_fit_chunk() entries at a time.
+ * lk_bias_score_panel writes d_panel [n_rows x n_items] (rows `ld` floats apart):
+ *   cell (q, i) = ((float)global_bias +f32 d_item_biases[i]) +f32 d_user_bias[q], the item term
+ *   only with d_item_biases, the user term only where d_user_add[q] != 0 (NULL: never) -- what
+ *   lk_bias_user_offsets returns.  With d_user_nums (int32 [n_rows]; NULL: nothing is struck) the
+ *   cells of row q at the items of row d_user_nums[q] of the training matrix (d_hist_indptr
+ *   i32/i64, d_hist_indices; -1 or >= n_users: no row) are then set to NaN.
+ * lk_bias_score_ragged writes the same cell for every entry e of query q (d_tgt_ptr int64
+ *   [n_queries + 1] offsets into d_tgt_items, n_entries = d_tgt_ptr[n_queries]) to d_out[e]; a
+ *   negative or >= n_items target is an unknown item, whose cell has no item term -- it is NOT
+ *   NaN (`BiasModel.compute_for_items`, bias.py:166-241).
+ * ---------------------------------------------------------------------- */
+int32_t lk_bias_fit_short_max(void);
+int32_t lk_bias_fit_chunk(void);
+int lk_bias_fit_pass(const void *d_indptr, int indptr_is_64, const int32_t *d_indices,
+                     const float *d_values, int64_t n_bins, double global_bias,
+                     const float *d_sub, int64_t n_sub, double damping, float *d_out,
+                     void *stream);
+int lk_bias_score_panel(int64_t n_rows, int64_t n_items, double global_bias,
+                        const float *d_item_biases, const float *d_user_bias,
+                        const uint8_t *d_user_add, float *d_panel, int64_t ld,
+                        const void *d_hist_indptr, int indptr_is_64,
+                        const int32_t *d_hist_indices, int64_t n_users,
+                        const int32_t *d_user_nums, void *stream);
+int lk_bias_score_ragged(int64_t n_queries, const int64_t *d_tgt_ptr, const int32_t *d_tgt_items,
+                         int64_t n_entries, int64_t n_items, double global_bias,
+                         const float *d_item_biases, const float *d_user_bias,
+                         const uint8_t *d_user_add, float *d_out, void *stream);
+
+/* ------------------------------------------------------------------------
  * `BiasedMFScorer.__call__` for a BATCH of queries (csrc/bmf_batch.hip): the host arithmetic of
  * the explicit-feedback ALS scorer around its row solve and its lk_score_dense row
  * (src/lenskit/als/_common.py:133-175, _explicit.py:55-91, basic/bias.py:166-241), so that a

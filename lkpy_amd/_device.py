@@ -908,6 +908,88 @@ def bias_user_offsets(hist: DeviceCSR, user_nums: torch.Tensor, global_bias: flo
     return ub, add
 
 
+def bias_fit(csr: DeviceCSR, csr_t: DeviceCSR | None, global_bias: float, damping_item: float,
+             damping_user: float, *, items: bool = True, users: bool = True):
+    """
+    ``BiasModel.learn`` on the device (lk_bias_fit_pass, src/lenskit/basic/bias.py:83-150):
+    ``csr`` the ratings (users x items, f32 values, entries in dataset order), ``csr_t`` its stable
+    transpose with values (:func:`csr_transpose`; needed for the item pass only).  Returns device
+    f32 (item biases | None, user biases | None) -- the host's bits: per bin two float64 chains
+    in dataset order, the user pass over the ratings less the item biases.
+    """
+    lib = _native.require_gpu()
+    dev = csr.indices.device
+    n_users, n_items = csr.shape
+    assert csr.values is not None and csr.values.dtype == torch.float32
+    ib = ub = None
+    if items:
+        assert csr_t is not None and csr_t.values is not None and csr_t.shape == (n_items, n_users)
+        ib = torch.zeros(n_items, dtype=torch.float32, device=dev)
+        check(
+            lib.lk_bias_fit_pass(_ptr(csr_t.indptr), 1 if csr_t.is64 else 0, _ptr(None),
+                                 _ptr(csr_t.values), n_items, float(global_bias), _ptr(None), 0,
+                                 float(damping_item), _ptr(ib), _stream()),
+            "lk_bias_fit_pass",
+        )
+    if users:
+        ub = torch.zeros(n_users, dtype=torch.float32, device=dev)
+        check(
+            lib.lk_bias_fit_pass(_ptr(csr.indptr), 1 if csr.is64 else 0, _ptr(csr.indices),
+                                 _ptr(csr.values), n_users, float(global_bias), _ptr(ib), n_items,
+                                 float(damping_user), _ptr(ub), _stream()),
+            "lk_bias_fit_pass",
+        )
+    return ib, ub
+
+
+def bias_score_panel(n_items: int, global_bias: float, item_biases: torch.Tensor | None,
+                     user_bias: torch.Tensor, user_add: torch.Tensor, *,
+                     strike: DeviceCSR | None = None, user_nums: torch.Tensor | None = None):
+    """
+    The [B x n_items] f32 panel of ``BiasScorer`` scores (lk_bias_score_panel): cell (q, i) =
+    (float32(mu) + b_i) + ub_q, the user term where ``user_add[q]``; with ``strike`` (the training
+    matrix) and ``user_nums`` (device int32 [B]) NaN at each query's own training items.
+    """
+    lib = _native.require_gpu()
+    B = int(user_bias.shape[0])
+    panel = torch.empty((B, int(n_items)), dtype=torch.float32, device=user_bias.device)
+    assert user_add.dtype == torch.uint8 and (user_nums is None or user_nums.dtype == torch.int32)
+    check(
+        lib.lk_bias_score_panel(
+            B, int(n_items), float(global_bias), _ptr(item_biases), _ptr(user_bias),
+            _ptr(user_add), _ptr(panel), int(n_items),
+            _ptr(strike.indptr if strike is not None else None),
+            1 if strike is not None and strike.is64 else 0,
+            _ptr(strike.indices if strike is not None else None),
+            strike.shape[0] if strike is not None else 0,
+            _ptr(user_nums if strike is not None else None), _stream()
+        ),
+        "lk_bias_score_panel",
+    )  # fmt: skip
+    return panel
+
+
+def bias_score_ragged(tgt_ptr: torch.Tensor, tgt_items: torch.Tensor, n_items: int,
+                      global_bias: float, item_biases: torch.Tensor | None,
+                      user_bias: torch.Tensor, user_add: torch.Tensor):
+    """
+    ``BiasScorer`` scores at ragged targets (lk_bias_score_ragged): device f32 [entries], entry t
+    of query q is (float32(mu) + b_item) + ub_q; an unknown item (negative) has no item term and
+    is not NaN.  ``tgt_ptr`` device int64 [B + 1], ``tgt_items`` device int32.
+    """
+    lib = _native.require_gpu()
+    n = int(tgt_items.shape[0])
+    out = torch.empty(n, dtype=torch.float32, device=tgt_items.device)
+    assert tgt_ptr.dtype == torch.int64 and tgt_items.dtype == torch.int32
+    check(
+        lib.lk_bias_score_ragged(int(tgt_ptr.shape[0]) - 1, _ptr(tgt_ptr), _ptr(tgt_items), n,
+                                 int(n_items), float(global_bias), _ptr(item_biases),
+                                 _ptr(user_bias), _ptr(user_add), _ptr(out), _stream()),
+        "lk_bias_score_ragged",
+    )
+    return out
+
+
 def predict_merge(tgt_ptr: torch.Tensor, tgt_items: torch.Tensor, n_items: int,
                   scores: torch.Tensor, item_means: torch.Tensor | None, *,
                   fallback: bool = False, global_bias: float = 0.0,

@@ -179,6 +179,20 @@ def _declare(lib):
             [c_int64, vp, vp, c_int64, c_int64, vp, vp, c_int, ctypes.c_double, vp, vp, vp, vp,
              vp],
         ),
+        "lk_bias_fit_short_max": (c_int32, []),
+        "lk_bias_fit_chunk": (c_int32, []),
+        "lk_bias_fit_pass": (
+            c_int,
+            [vp, c_int, vp, vp, c_int64, ctypes.c_double, vp, c_int64, ctypes.c_double, vp, vp],
+        ),
+        "lk_bias_score_panel": (
+            c_int,
+            [c_int64, c_int64, ctypes.c_double, vp, vp, vp, vp, c_int64, vp, c_int, vp, c_int64,
+             vp, vp],
+        ),
+        "lk_bias_score_ragged": (
+            c_int, [c_int64, vp, vp, c_int64, c_int64, ctypes.c_double, vp, vp, vp, vp, vp]
+        ),
         "lk_bmf_residual_rows": (
             c_int,
             [vp, c_int, vp, vp, c_int64, c_int64, c_int64, vp, vp, ctypes.c_double, vp,

@@ -795,13 +795,13 @@ class BiasedMFTrainer(ModelTrainer):
         cfg = scorer.config
         scorer.users, scorer.items = data.users, data.items
         self.rng = options.random_generator()
+        dev = self.device = D.device(None if options.configured_device() in ("cuda", "cpu") else
+                                     options.configured_device())
         ui = self.prepare_matrix(data)
         k = cfg.embedding_size
         # item matrix FIRST, then users, same generator (_common.py:287-301)
         scorer.item_embeddings = self.initial_params(data.item_count, k)
         scorer.user_embeddings = self.initial_params(data.user_count, k)
-        dev = D.device(None if options.configured_device() in ("cuda", "cpu") else
-                       options.configured_device())
         backend = HipBackend(k, dev, _native.SOLVER_CHOLESKY, _reference_order(options))
         self.engine = ImplicitALSEngine(sps.csr_array(ui), k, cfg.user_reg, cfg.item_reg,
                                         scorer.user_embeddings, scorer.item_embeddings, backend,
@@ -811,7 +811,8 @@ class BiasedMFTrainer(ModelTrainer):
     def prepare_matrix(self, data: Dataset) -> sps.coo_array:
         "_explicit.py:95-102: ratings minus the learned biases, float32"
         rmat = data.interactions().matrix().scipy(attribute="rating", layout="coo")
-        self.scorer.bias = BiasModel.learn(data, damping=self.scorer.config.damping)
+        self.scorer.bias = BiasModel.learn(data, damping=self.scorer.config.damping,
+                                           device=self.device)
         return self.scorer.bias.transform_matrix(rmat).astype(np.float32)
 
     def initial_params(self, nrows: int, ncols: int) -> np.ndarray:

@@ -6,7 +6,8 @@ two target TOMLs need it (host NumPy; not on the accelerated path except ``TopNR
 ``TrainingItemsCandidateSelector``  src/lenskit/basic/candidates.py:50-94
 ``TopNRanker``                      src/lenskit/basic/topn.py:32-69 (-> ItemList.top_n ->
                                     the GPU top-N kernel)
-``BiasScorer`` / ``FallbackScorer`` src/lenskit/basic/bias.py, composite.py (std:topn-predict)
+``BiasScorer`` / ``FallbackScorer`` src/lenskit/basic/bias.py, composite.py (std:topn-predict;
+                                    the fit and the batch paths are csrc/bias.hip)
 ``PopScorer`` / ``TimeBoundedPopScore``  src/lenskit/basic/popularity.py (host training; the batch
                                     path is one walk over a shared order, csrc/popular.hip)
 ``RandomSelector``                  src/lenskit/basic/random.py (the stochastic ranker's draws
@@ -250,13 +251,47 @@ class BiasModel:
         self.global_bias = float(global_bias)
         self.items = self.users = None
         self.item_biases = self.user_biases = None
+        # (item, user) biases left in HBM by a device fit (``learn(device=...)``); never pickled
+        self.device_biases = None
+
+    def __getstate__(self):
+        st = dict(self.__dict__)
+        st["device_biases"] = None
+        return st
 
     @classmethod
-    def learn(cls, data: Dataset, damping=0.0, *, entities=("user", "item")) -> "BiasModel":
-        "bias.py:83-150, call for call (float64 sums, float32 biases)."
+    def learn(cls, data: Dataset, damping=0.0, *, entities=("user", "item"), device=None,
+              csr=None, csr_t=None) -> "BiasModel":
+        """
+        bias.py:83-150, call for call (float64 sums, float32 biases).  ``device`` (a HIP device):
+        the two passes run there (``lk_bias_fit_pass``, csrc/bias.hip) and give the bits of the
+        host arithmetic below; ``csr`` / ``csr_t`` are the ratings in HBM (users x items with the
+        float32 values, entries in the dataset's order) and their stable transpose with values
+        where the caller holds them already -- they are built here otherwise.  The fitted
+        vectors stay on the device too (``device_biases``).  Ratings that are not float32 are
+        fitted on the host.
+        """
         ratings = data.interaction_matrix(format="scipy", layout="coo", field="rating")
         nrows, ncols = ratings.shape
         model = cls(damping, float(np.mean(ratings.data)))
+        if device is not None and ratings.data.dtype == np.float32:
+            from . import _device as D
+
+            dev = D.device(device)
+            if csr is None:
+                csr = D.DeviceCSR.from_arrays(data._indptr, data._cols, ratings.data,
+                                              (nrows, ncols), dev)
+            if csr_t is None and "item" in entities:
+                csr_t = D.csr_transpose(csr, with_values=True)
+            ib, ub = D.bias_fit(csr, csr_t, model.global_bias, _damping(damping, "item"),
+                                _damping(damping, "user"), items="item" in entities,
+                                users="user" in entities)
+            if ib is not None:
+                model.items, model.item_biases = data.items, ib.cpu().numpy()
+            if ub is not None:
+                model.users, model.user_biases = data.users, ub.cpu().numpy()
+            model.device_biases = (ib, ub)
+            return model
         centered = ratings.data - model.global_bias
         if "item" in entities:
             counts = np.full(ncols, _damping(damping, "item"))
@@ -326,15 +361,41 @@ class BiasModel:
 
 class BiasScorer(Component):
     """``BiasScorer`` (src/lenskit/basic/bias.py:278-360) over :class:`BiasModel`:
-    score = mu + b_i + b_u."""
+    score = mu + b_i + b_u.
+
+    Trained on the device where there is one (``lk_bias_fit_pass``; the host arithmetic of
+    ``BiasModel.learn`` without -- the model has the same bits either way).  A whole batch of
+    queries is scored by csrc/bias.hip: :meth:`recommend_batch` and :meth:`dense_scores_batch`
+    through [rows x items] panels of at most ``PANEL_BYTES``, :meth:`score_candidates_batch` at
+    the ragged targets alone.  A cell is ``(float32(mu) + b_i) + ub_q`` with the user term of
+    :meth:`user_offsets_batch`; an item the model does not know scores ``float32(mu) (+ ub_q)``,
+    not NaN (``scores_unknown_items``).
+    """
 
     config: BiasConfig
+
+    PANEL_BYTES = 1 << 30  # score panel of one recommend step
+    accepts_history_batch = True  # the batch calls take a HistoryBatch
+    returns_device_lists = True  # recommend_batch has ``device_output``
+    scores_unknown_items = True  # a candidate outside the vocabulary keeps a finite score
 
     def is_trained(self):
         return hasattr(self, "model")
 
     def train(self, data: Dataset, options: TrainingOptions = TrainingOptions()):
-        self.model = BiasModel.learn(data, self.config.damping, entities=self.config.entities)
+        from . import _native
+
+        device = None
+        name = options.configured_device()
+        if name != "cpu":
+            try:
+                from . import _device as D
+
+                device = D.device(None if name == "cuda" else name)
+            except _native.BackendUnavailable:
+                device = None  # (no HIP device: the host arithmetic, the same bits)
+        self.model = BiasModel.learn(data, self.config.damping, entities=self.config.entities,
+                                     device=device)
 
     # the learned parameters, under the names the reference's scorer exposes
     global_bias = property(lambda self: self.model.global_bias)
@@ -357,10 +418,116 @@ class BiasScorer(Component):
             from . import _device as D
 
             ib = self.model.item_biases
-            return None if ib is None else torch.from_numpy(
-                np.ascontiguousarray(ib, dtype=np.float32)).to(D.device())
+            if ib is None:
+                return None
+            kept = getattr(self.model, "device_biases", None)
+            if kept is not None and kept[0] is not None and kept[0].device == D.device():
+                return kept[0]  # (a device fit left them there)
+            return torch.from_numpy(np.ascontiguousarray(ib, dtype=np.float32)).to(D.device())
 
         return self._device_cache("item_biases", upload, self.model)
+
+    def takes_batches_of(self, lookup) -> bool:
+        """Can a batch go by the numbers of ``lookup``'s training matrix?  The model has an item
+        vocabulary and it is that matrix's; with a user term the users are its users and its
+        ratings are float32 (the host sums the history's own ratings: float32 in HBM).  Answered
+        once per (model, training matrix): comparing vocabularies that are not one object is a
+        full comparison."""
+        model = getattr(self, "model", None)
+        inter = getattr(lookup, "interactions", None)
+        if model is None or model.items is None or inter is None or not hasattr(lookup, "batch"):
+            return False
+        return self._device_cache("takes_batches_of", lambda: self._matches(model, inter._ds),
+                                  model, inter)
+
+    @staticmethod
+    def _matches(model, ds) -> bool:
+        if not (model.items is ds.items or model.items == ds.items):
+            return False
+        if model.users is not None:
+            rating = ds._attrs.get("rating")
+            if not (model.users is ds.users or model.users == ds.users) or rating is None or \
+                    rating.dtype != np.float32:
+                return False
+        return True
+
+    def _panel_rows(self) -> int:
+        return max(1, self.PANEL_BYTES // (4 * max(len(self.model.items), 1)))
+
+    def _panel(self, batch: "HistoryBatch", *, strike_history: bool):
+        "One ``lk_bias_score_panel`` call: the device panel of the queries of ``batch``."
+        import torch
+
+        from . import _device as D
+
+        if not isinstance(batch, HistoryBatch) or not self.takes_batches_of(batch.lookup):
+            raise TypeError("BiasScorer's batch calls take a HistoryBatch over the training "
+                            "matrix the model was fitted on")
+        ub, add = self.user_offsets_batch(batch)
+        strike = nums = None
+        if strike_history:
+            strike = batch.lookup._device_matrix()["csr"]
+            nums = torch.from_numpy(batch.user_nums).to(ub.device)
+        return D.bias_score_panel(len(self.model.items), self.model.global_bias,
+                                  self._device_item_biases(), ub, add, strike=strike,
+                                  user_nums=nums)
+
+    def dense_scores_batch(self, queries):
+        """(panel f32 [B x items] on the device, valid -- all True: an unknown user is scored
+        without a user term --, history CSR): nothing is struck, the history is for the caller
+        to exclude."""
+        return (self._panel(queries, strike_history=False), np.ones(len(queries), dtype=bool),
+                queries.csr(with_values=False))
+
+    def recommend_batch(self, queries, n: int | None, *, exclude_history: bool = True,
+                        device_output: bool = False):
+        """
+        The top ``n`` (None or negative: every candidate) of many queries at once -- what the
+        ``recommender`` pipeline computes per query: every training item but the query's own,
+        scored, ``TopNRanker``.  ``queries``: a :class:`HistoryBatch`.  Panels of at most
+        ``PANEL_BYTES``, each selected from by ``lk_argtopn`` (score descending, then item number
+        ascending: the per-query order).  Returns (item numbers [B x n] with -1 padding, scores
+        [B x n] with NaN padding), on the device with ``device_output``.
+        """
+        import torch
+
+        from . import _device as D
+
+        B = len(queries)
+        n_items = len(self.model.items)
+        n = -1 if n is None else int(n)
+        cols = n_items if n < 0 else n
+        d = D.device()
+        oi = torch.full((B, cols), -1, dtype=torch.int32, device=d)
+        osc = torch.full((B, cols), float("nan"), dtype=torch.float32, device=d)
+        step = self._panel_rows()
+        for lo in range(0, B, step):
+            sub = queries if lo == 0 and B <= step else queries.subset(slice(lo, lo + step))
+            panel = self._panel(sub, strike_history=exclude_history)
+            idx = D.argtopn(panel, n)
+            oi[lo:lo + step, :idx.shape[1]] = idx
+            osc[lo:lo + step, :idx.shape[1]] = D.take_scores(panel, idx)
+            del panel
+        if device_output:
+            return oi, osc
+        return D.lists_to_host(oi, osc)
+
+    def score_candidates_batch(self, queries, tgt_ptr, item_nums, *, d_targets=None):
+        """
+        The scores of each query's OWN items, left on the device: f32 [total], entry t of query q
+        is ``(float32(mu) + b_i) + ub_q``, the bits ``__call__`` gives (``lk_bias_score_ragged``:
+        one pass, no panel).  An unknown item is NOT NaN: it has no item term.  ``tgt_ptr`` int64
+        [B + 1] and ``item_nums`` int32 are host arrays, ``d_targets`` their device copies.
+        """
+        from . import _device as D
+
+        if not isinstance(queries, HistoryBatch) or not self.takes_batches_of(queries.lookup):
+            raise TypeError("BiasScorer's batch calls take a HistoryBatch over the training "
+                            "matrix the model was fitted on")
+        ub, add = self.user_offsets_batch(queries)
+        d_ptr, d_nums = d_targets or D.upload_targets(tgt_ptr, item_nums, ub.device)
+        return D.bias_score_ragged(d_ptr, d_nums, len(self.model.items), self.model.global_bias,
+                                   self._device_item_biases(), ub, add)
 
     def user_offsets_batch(self, batch: "HistoryBatch"):
         """

@@ -132,8 +132,17 @@ def _recommend_loop(pipe: Pipeline, users, n) -> ItemListCollection:
 
 
 def _takes_history_batches(scorer, lookup) -> bool:
-    "the lookup hands out ``HistoryBatch`` es and the scorer's batch calls take them"
-    return hasattr(lookup, "batch") and getattr(scorer, "accepts_history_batch", False)
+    """the lookup hands out ``HistoryBatch`` es and the scorer's batch calls take them -- those
+    of THIS lookup, where the scorer has a say in it (``takes_batches_of``: ``BiasScorer``)"""
+    if not (hasattr(lookup, "batch") and getattr(scorer, "accepts_history_batch", False)):
+        return False
+    return _takes_batches_of(scorer, lookup)
+
+
+def _takes_batches_of(scorer, lookup) -> bool:
+    "``scorer.takes_batches_of(lookup)`` where the scorer has such a rule; True without one"
+    rule = getattr(scorer, "takes_batches_of", None)
+    return rule is None or bool(rule(lookup))
 
 
 def _reranks_batches(reranker, scorer) -> bool:
@@ -351,7 +360,8 @@ def predict(pipe: Pipeline, pairs, *, batch_size: int = 16384) -> ItemListCollec
     with its ``BiasScorer`` fallback, or without a fallback) whose vocabularies agree is run as
     whole batches by user number (:func:`_predict_batched`): the lists are the per-query
     composition's bit for bit (float32 of it where the biased-MF scorer alone hands out float64).
-    Every other pipeline runs query by query.
+    So is a pipeline whose scorer is a trained ``BiasScorer`` (:func:`_predict_bias`).  Every
+    other pipeline runs query by query.
     """
     ragged = _ragged_pairs(pairs)
     keys, offsets, item_ids, fields, _lists = ragged
@@ -359,6 +369,9 @@ def predict(pipe: Pipeline, pairs, *, batch_size: int = 16384) -> ItemListCollec
     if parts is not None and fields is not None and not (
             set(fields) & {"score", "nbr_counts", "is_fallback"}):
         return _predict_batched(parts, keys, offsets, item_ids, fields, batch_size)
+    parts = _bias_predict_parts(pipe)
+    if parts is not None and fields is not None and not (set(fields) & {"score", "is_fallback"}):
+        return _predict_bias(parts, keys, offsets, item_ids, fields, batch_size)
     if isinstance(pairs, dict):
         return _predict_loop(pipe, pairs)
     return _predict_loop(pipe, dict(zip(_key_list(keys), _query_lists(ragged))))
@@ -568,6 +581,56 @@ def _predict_batched(parts, keys, offsets, item_ids, fields, batch_size: int):
     return _scored_lists(keys, offsets, item_ids, fields, scores, counts, nohist, fb)
 
 
+def _bias_predict_parts(pipe: Pipeline):
+    """(BiasScorer, lookup, with_fallback) when ``rating-predictor`` is a trained ``BiasScorer`` that
+    takes the lookup's batches (``takes_batches_of``: an item vocabulary, the lookup's
+    vocabularies, float32 ratings under a user term), alone or under the ``FallbackScorer`` of
+    ``std:topn-predict`` over a trained ``BiasScorer``; None otherwise."""
+    from .basic import BiasScorer, FallbackScorer
+
+    scorer = _slot(pipe, "scorer")
+    lookup_node = pipe.nodes.get("history-lookup")
+    if not isinstance(scorer, BiasScorer) or lookup_node is None or not scorer.is_trained():
+        return None
+    lookup = lookup_node.component
+    if _numbered_dataset(scorer, lookup) is None or not _takes_history_batches(scorer, lookup):
+        return None
+    target = pipe.aliases.get("rating-predictor")
+    if target == pipe.aliases.get("scorer", "scorer"):
+        return scorer, lookup, False
+    merger = pipe.nodes.get("rating-merger")
+    if target != "rating-merger" or merger is None:
+        return None  # (``std:topn`` has no rating predictor: the loop raises, as before)
+    fb = pipe.nodes.get("fallback-predictor")
+    if not isinstance(merger.component, FallbackScorer) or fb is None or \
+            not isinstance(fb.component, BiasScorer) or not fb.component.is_trained():
+        return None
+    return scorer, lookup, True
+
+
+def _predict_bias(parts, keys, offsets, item_ids, fields, batch_size: int):
+    """
+    ``rating-predictor`` of a Bias pipeline for whole batches: per batch the user terms
+    (``lk_bias_user_offsets``), the cells at the targets (``lk_bias_score_ragged``) and one
+    download.  A ``BiasScorer`` scores every target -- an unknown item, an unknown user -- so the
+    fallback of ``std:topn-predict`` is never taken: ``is_fallback`` is there, and all False.
+    """
+    scorer, lookup, with_fallback = parts
+    B = len(keys)
+    if B == 0:
+        return ItemListCollection(("user_id",))
+    key_arr = _as_array(keys)
+    nums = _item_numbers(scorer.items, item_ids)
+    total = int(offsets[-1])
+    scores = np.empty(total, np.float32)
+    for _s0, _s1, lo, hi, _hb, _h_ptr, _d_ptr, _d_nums, s_dev, _c in _scored_batches(
+            (scorer, lookup, "own"), key_arr, offsets, nums, batch_size):
+        if s_dev is not None:
+            scores[lo:hi] = s_dev.cpu().numpy()
+    return _scored_lists(keys, offsets, item_ids, fields, scores,
+                         is_fallback=np.zeros(total, np.bool_) if with_fallback else None)
+
+
 def _scored_lists(keys, offsets, item_ids, fields, scores, counts=None, nohist=None,
                   is_fallback=None) -> ItemListCollection:
     """The result of ``predict`` / ``score``: the caller's ids and fields, then ``nbr_counts``
@@ -615,7 +678,7 @@ def _candidate_route(pipe: Pipeline):
     ``GlobalBiasPairScoring``: ``FlexMFExplicitScorer``, ``BiasedSVDScorer``; ``ItemKNNScorer``;
     ``SLIMScorer`` and ``AssociationScorer``: the chain of their panel cell at the targets only,
     ``lk_sparse_score_candidates``; ``PopScorer`` / ``TimeBoundedPopScore``: the score row read at
-    the targets);
+    the targets; ``BiasScorer``: its cell at the targets, ``lk_bias_score_ragged``);
     ``"panel"`` -- ``dense_scores_batch`` read at the targets by ``lk_panel_take_ragged``
     (``EASEScorer``, ``UserKNNScorer``: the two whose panel is shown bit-equal to ``__call__``).
     The pipeline must be wired as ``std:topn`` wires it (the scorer scores ``items`` when given;
@@ -645,6 +708,8 @@ def _candidate_route(pipe: Pipeline):
         return None
     if hasattr(scorer, "is_trained") and not scorer.is_trained():
         return None
+    if not _takes_batches_of(scorer, lookup):
+        return None  # (``BiasScorer``: a user term over ratings that are not float32)
     if isinstance(scorer, (ItemKNNScorer, UserKNNScorer)) and scorer.config.explicit and \
             ds._attrs.get("rating") is None:
         return None  # (the per-query path raises / answers NaN: it goes on doing so)
@@ -694,6 +759,19 @@ def _scored_batches(plan, key_arr, offsets, nums, batch_size: int, *, with_count
             s_dev = scorer.score_candidates_batch(hb, h_ptr, nums[lo:hi],
                                                   d_targets=(d_ptr, d_nums))
         yield s0, s1, lo, hi, hb, h_ptr, d_ptr, d_nums, s_dev, counts
+
+
+def _ranks_unknown_items(scorer, item_ids=None, *, nums=None) -> bool:
+    """Does a ranking of these candidates (``item_ids``, or their numbers ``nums``) hold items the
+    scorer's vocabulary does not?  Every scorer but ``BiasScorer`` answers NaN for such an item and
+    the rankers drop it -- for them the answer is False, unlooked --; ``BiasScorer`` scores it
+    (``scores_unknown_items``) and ``pipe.run`` lists it under its id, which a list of item NUMBERS
+    cannot say: such a call goes query by query."""
+    if not getattr(scorer, "scores_unknown_items", False):
+        return False
+    if nums is None:
+        nums = _item_numbers(scorer.items, item_ids)
+    return bool((nums < 0).any())
 
 
 def _item_numbers(vocab, item_ids) -> np.ndarray:
@@ -841,6 +919,8 @@ def _sample_candidates(plan, ranker, keys, offsets, item_ids, lists, n, samples:
     B = len(keys)
     key_arr = _as_array(keys)
     nums = _item_numbers(scorer.items, item_ids)
+    if _ranks_unknown_items(scorer, nums=nums):
+        return None
     packed = _candidate_addresses(lists, offsets, nums, scorer.items)
     if packed is None:
         return None
@@ -955,7 +1035,10 @@ def _recommend_candidates(pipe: Pipeline, users, n, candidates, batch_size: int,
     scorer (a ``score`` among them: the per-query lists keep them), a reranker without
     ``rerank_batch``, a scorer without a route, vocabularies that disagree, and under the two
     drawing rankers the lists :func:`_candidate_addresses` cannot pack -- a repeated item,
-    another vocabulary than the scorer's, lists with and without a vocabulary.
+    another vocabulary than the scorer's, lists with and without a vocabulary.  So does a call
+    whose lists hold an item outside the vocabulary of a scorer that scores such items
+    (``BiasScorer``: ``_ranks_unknown_items``); with ``rerank_depth``, which the loop cannot
+    honour, that call raises ``ValueError``.
     """
     ragged = _candidate_lists(users, candidates)
     keys, offsets, item_ids, fields, lists = ragged
@@ -965,6 +1048,11 @@ def _recommend_candidates(pipe: Pipeline, users, n, candidates, batch_size: int,
         raise ValueError("rerank_depth does not apply to a random selection")
     _check_rerank_depth(pipe, reranker, scorer, n, rerank_depth)
     mode, ranker, plan = _candidate_mode(pipe, fields, len(keys))
+    if mode == "topn" and _ranks_unknown_items(scorer, item_ids):
+        if rerank_depth is not None:  # (the loop reranks the ranker's n items: it has no depth)
+            raise ValueError("rerank_depth needs candidate lists of items the scorer knows: "
+                             "an item outside its vocabulary sends the call through pipe.run")
+        mode = "loop"
     out = None  # (in every mode but "loop" the reranker, if there is one, takes batches)
     if mode == "random":
         out = _random_candidates(pipe, ranker, keys, offsets, item_ids, fields, lists, n,

@@ -120,7 +120,7 @@ class BiasedSVDScorer(GlobalBiasPairScoring, Component, Trainable):
             raise ValueError(f"embedding_size + {D.SVD_OVERSAMPLES} = {l} sketch columns need at "
                              f"least that many users and items, got {data.user_count} x "
                              f"{data.item_count}")
-        bias = BiasModel.learn(data, cfg.damping)
+        bias = BiasModel.learn(data, cfg.damping, device=dev)
         resid = bias.transform_matrix(
             data.interaction_matrix(format="scipy", layout="coo", field="rating")).tocsr()
         resid.sort_indices()

@@ -178,7 +178,7 @@ def _component(ds, reps=3):
         sc.recommend_batch(lookup.batch(uids), 100)
         ts.append(time.perf_counter() - t0)
     return {"train_seconds": round(t_train, 4),
-            "train_what": "BiasedSVDScorer.train: bias model on the host, upload, transpose, "
+            "train_what": "BiasedSVDScorer.train: bias model (on the device), upload, transpose, "
                           "fit, download",
             "recommend": {"users": int(n), "n": 100, "seconds": round(min(ts), 5),
                           "seconds_all": [round(t, 5) for t in ts],
