@@ -1641,6 +1641,61 @@ int lk_nmf_cd_sweep(float *d_w, int64_t n, int32_t k, int32_t ld, const float *d
                     int32_t ld_hht, const float *d_xht, float l1_reg, double *d_violation,
                     void *d_ws, void *stream);
 
+/* ------------------------------------------------------------------------
+ * FunkSVD (csrc/funksvd.hip): the featurewise SGD of `FunkSVDScorer.train`
+ * (src/lenskit/funksvd.py:111-197) run level by level.  A sample reads and writes only its
+ * user's and its item's entry of the feature's two columns, so with
+ *   level(s) = 1 + max(level of the previous sample of u, level of the previous sample of i)
+ * the samples of one level commute exactly and the levels in order give the bits of the
+ * reference's sequential walk.
+ *
+ * lk_funksvd_plan_levels (HOST arrays; replaces nothing of the reference, which has no schedule):
+ *   users / items [n] are the shuffled samples (funksvd.py:132-137), 0 <= users < n_users, 0 <=
+ *   items < n_items (LK_E_INVALID otherwise).  level[n] receives each sample's level counted from
+ *   0, *depth the number of levels.  One sequential O(n) pass.
+ * lk_funksvd_plan_order (HOST arrays): the stable counting sort by level.  order[n]: sample
+ *   positions in level order, ascending inside a level; level_ptr[depth + 1]: the levels' offsets
+ *   in `order`; run_end[depth]: for a level inside a NARROW RUN -- a run of consecutive levels of
+ *   at most lk_funksvd_narrow_width() = 64 samples each, extended level by level while it holds
+ *   at most lk_funksvd_stage_samples() = 2048 samples, which the kernel stages in LDS -- one
+ *   past the run's last level, for a wider level the level itself.
+ *
+ * lk_funksvd_train_feature: `epochs` calls of `FunkSVDTrainer::feature_epoch`
+ *   (src/accel/funksvd.rs:67-128) for one feature, in ONE launch of one workgroup.  d_users,
+ *   d_items, d_ratings, d_est [n] are the samples IN LEVEL ORDER (n = d_level_ptr[depth]),
+ *   d_level_ptr / d_run_end the plan's arrays on the device, d_ucol [n_users] / d_icol [n_items]
+ *   the feature's columns (updated in place).  Per sample, funksvd.rs:98-124 operation for
+ *   operation in float64 with no fused multiply-add:
+ *     pred = clamp((est + ufv * ifv) + trail, rmin, rmax);  err = r - pred;
+ *     ufd = (err * ifv - reg * ufv) * lr;  ifd = (err * ufv - reg * ifv) * lr  (old ufv, ifv);
+ *     ucol[u] = (float)(ufv + ufd);  icol[i] = (float)(ifv + ifd).
+ *   rmin / rmax are -inf / +inf without a range.  d_sse[e] (float64) receives epoch e's sum of
+ *   err^2: per-lane partial sums through a fixed tree -- repeatable, but not the reference's
+ *   sequential sum (which is only logged, funksvd.rs:115,126).  With `finish` != 0 the launch
+ *   ends with funksvd.py:188-190 in float32, product and sum rounded separately:
+ *     est = clip(est + ucol[u] * icol[i], (float)rmin, (float)rmax).
+ *   The columns sit in LDS when (n_users + n_items) * 4 <= lk_funksvd_lds_column_bytes(), in
+ *   global memory otherwise or with LK_FUNKSVD_GLOBAL_COLUMNS in `flags` (same bits).  With the
+ *   columns in LDS one wave walks a narrow run alone, fences between its levels; every other
+ *   level, and every level with the columns in global memory, ends in a block barrier.  A call
+ *   with e1 epochs followed by one with e2 gives the bits of one call with e1 + e2.
+ *   Asynchronous on `stream`.
+ * ---------------------------------------------------------------------- */
+#define LK_FUNKSVD_GLOBAL_COLUMNS 1
+int32_t lk_funksvd_narrow_width(void);
+int32_t lk_funksvd_stage_samples(void);
+size_t lk_funksvd_lds_column_bytes(void);
+int lk_funksvd_plan_levels(const int32_t *users, const int32_t *items, int64_t n, int64_t n_users,
+                           int64_t n_items, int32_t *level, int32_t *depth);
+int lk_funksvd_plan_order(const int32_t *level, int64_t n, int32_t depth, int64_t *order,
+                          int64_t *level_ptr, int32_t *run_end);
+int lk_funksvd_train_feature(const int32_t *d_users, const int32_t *d_items,
+                             const float *d_ratings, float *d_est, const int64_t *d_level_ptr,
+                             const int32_t *d_run_end, int32_t depth, float *d_ucol,
+                             float *d_icol, int64_t n_users, int64_t n_items, int32_t epochs,
+                             int32_t finish, double lr, double reg, double trail, double rmin,
+                             double rmax, int32_t flags, double *d_sse, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

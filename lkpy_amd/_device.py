@@ -3498,3 +3498,176 @@ def nmf_fit(csr: DeviceCSR, csr_t: DeviceCSR, w0: np.ndarray, h0: np.ndarray, ma
             break
     return (to_host_unpadded(w, k), np.ascontiguousarray(to_host_unpadded(ht, k).T), n_iter,
             np.asarray(history, dtype=np.float64))
+
+
+# ---- FunkSVD (csrc/funksvd.hip) --------------------------------------------------------------
+# sample-steps (samples x epochs) one launch may hold: the kernel walks 1.7e8 to 1.9e8 samples a
+# second (profiles/funksvd_mi355x.json), so a launch ends within 0.4 s
+FUNKSVD_STEP_BUDGET = 1 << 26
+
+
+@dataclass
+class FunkSVDPlan:
+    """The level schedule of a shuffled sample list (lk_funksvd_plan_levels / _order), on the
+    host: ``order`` int64 [n] (sample positions in level order, ascending inside a level),
+    ``level_ptr`` int64 [depth + 1], ``run_end`` int32 [depth] (the narrow-run marks) and
+    ``level`` int32 [n] (each sample's level).  ``from_recurrence``: :func:`funksvd_plan` made it
+    (a schedule a caller assigned is checked for repeats before it is run)."""
+
+    order: np.ndarray
+    level_ptr: np.ndarray
+    run_end: np.ndarray
+    level: np.ndarray
+    from_recurrence: bool = False
+
+    @property
+    def depth(self) -> int:
+        return len(self.level_ptr) - 1
+
+
+def funksvd_lds_column_bytes() -> int:
+    "The bytes of feature columns ``lk_funksvd_train_feature`` keeps in LDS."
+    return int(_native.load().lk_funksvd_lds_column_bytes())
+
+
+def funksvd_plan(users: np.ndarray, items: np.ndarray, n_users: int, n_items: int) -> FunkSVDPlan:
+    """
+    The level schedule of the samples ``(users[s], items[s])`` in their (shuffled) order:
+    ``level(s) = 1 + max(level of the previous sample of the user, ... of the item)``, one
+    sequential pass and one stable counting sort in the native library, on the host (no device
+    is needed).  ``ValueError`` for a number outside ``n_users`` / ``n_items``.
+    """
+    lib = _native.load()
+    users = np.ascontiguousarray(users, dtype=np.int32)
+    items = np.ascontiguousarray(items, dtype=np.int32)
+    n = len(users)
+    if users.shape != (n,) or items.shape != (n,):
+        raise ValueError("funksvd_plan: users and items must be vectors of one length")
+    level = np.empty(n, np.int32)
+    depth = ctypes.c_int32(0)
+    hp = lambda a: ctypes.c_void_p(a.ctypes.data)  # noqa: E731
+    check(lib.lk_funksvd_plan_levels(hp(users), hp(items), n, int(n_users), int(n_items),
+                                     hp(level), ctypes.byref(depth)), "lk_funksvd_plan_levels")
+    plan = funksvd_plan_of_levels(level, depth.value)
+    plan.from_recurrence = True
+    return plan
+
+
+def funksvd_plan_of_levels(level: np.ndarray, depth: int | None = None) -> FunkSVDPlan:
+    """
+    The plan of a given level assignment (lk_funksvd_plan_order: the stable counting sort and the
+    narrow-run marks).  Any assignment in which no user and no item repeats inside a level and
+    every user's and item's samples keep their order is a schedule with the sequential walk's
+    bits; :func:`funksvd_plan` makes the shallowest one.
+    """
+    lib = _native.load()
+    level = np.ascontiguousarray(level, dtype=np.int32)
+    n = len(level)
+    if depth is None:
+        depth = int(level.max()) + 1 if n else 0
+    hp = lambda a: ctypes.c_void_p(a.ctypes.data)  # noqa: E731
+    order = np.empty(n, np.int64)
+    level_ptr = np.empty(depth + 1, np.int64)
+    run_end = np.empty(depth, np.int32)
+    check(lib.lk_funksvd_plan_order(hp(level), n, depth, hp(order), hp(level_ptr), hp(run_end)),
+          "lk_funksvd_plan_order")
+    return FunkSVDPlan(order, level_ptr, run_end, level)
+
+
+def funksvd_fit(users: np.ndarray, items: np.ndarray, ratings: np.ndarray, est: np.ndarray,
+                n_users: int, n_items: int, k: int, epochs: int, lr: float, reg: float,
+                rmin: float = -np.inf, rmax: float = np.inf, *, initial: float = 0.1,
+                plan: FunkSVDPlan | None = None, dev=None, global_columns: bool = False,
+                step_budget: int | None = None, stats: dict | None = None):
+    """
+    The reference's FunkSVD training loop (funksvd.py:148-190) on the device, bit for bit: from
+    the shuffled samples (``users``, ``items`` int32, ``ratings`` float32) and their initial
+    estimates ``est`` (float32; not modified), ``k`` features one after the other, ``epochs``
+    epochs each, by ``lk_funksvd_train_feature`` over the samples in level order
+    (:func:`funksvd_plan`, made here unless ``plan`` is given).  The level-ordered arrays are
+    uploaded once; feature f trains with ``trail = initial * initial * (k - f - 1)`` and leaves
+    its clipped contribution in the estimates for the next.
+
+    A feature's epochs are split over several launches so that none holds more than
+    ``step_budget`` (default :data:`FUNKSVD_STEP_BUDGET`) sample-steps, which changes no bit.
+    ``global_columns`` (a test hook) keeps the feature columns in global memory at any size.
+
+    Returns (user embeddings f32 [n_users x k], item embeddings f32 [n_items x k], the epochs'
+    training RMSE f64 [k x epochs]) on the host.  ``stats`` (a dict, for the timing tool)
+    receives ``plan_seconds``, ``train_seconds`` (the launches, synchronised), ``depth``,
+    ``epochs_per_launch`` and ``sse`` (the epochs' squared errors as the kernel summed them).
+    """
+    from time import perf_counter
+
+    lib = _native.require_gpu()
+    dev = device(dev)
+    users = np.ascontiguousarray(users, dtype=np.int32)
+    items = np.ascontiguousarray(items, dtype=np.int32)
+    ratings = np.ascontiguousarray(ratings, dtype=np.float32)
+    est = np.ascontiguousarray(est, dtype=np.float32)
+    n = len(users)
+    if not (users.shape == items.shape == ratings.shape == est.shape == (n,)):
+        raise ValueError("funksvd_fit: users, items, ratings and est must be vectors of one length")
+    k, epochs = int(k), int(epochs)
+    if k < 1 or epochs < 1:
+        raise ValueError(f"funksvd_fit: k = {k} and epochs = {epochs} must be positive")
+    t0 = perf_counter()
+    if plan is None:
+        plan = funksvd_plan(users, items, n_users, n_items)
+    elif not plan.from_recurrence:  # a caller's schedule: two samples of a level share nothing
+        if len(plan.level) != n:
+            raise ValueError("funksvd_fit: the plan does not belong to these samples")
+        for ent, count in ((users, n_users), (items, n_items)):
+            key = plan.level.astype(np.int64) * max(int(count), 1) + ent
+            if len(np.unique(key)) != n:
+                raise ValueError("funksvd_fit: a user or an item repeats inside a level")
+    t_plan = perf_counter() - t0
+    ptr = plan.level_ptr
+    if len(plan.order) != n or len(plan.run_end) != plan.depth or ptr[0] != 0 or ptr[-1] != n \
+            or (np.diff(ptr) < 0).any():
+        raise ValueError("funksvd_fit: the plan does not belong to these samples")
+    # the run marks address level_ptr and size the kernel's stage: held to lk_funksvd_plan_order's
+    at = np.arange(plan.depth)
+    run = plan.run_end > at
+    if (plan.run_end < at).any() or (plan.run_end > plan.depth).any() or \
+            (ptr[plan.run_end[run]] - ptr[at[run]] > lib.lk_funksvd_stage_samples()).any() or \
+            (np.diff(ptr)[run] > lib.lk_funksvd_narrow_width()).any():
+        raise ValueError("funksvd_fit: the plan's narrow-run marks are not lk_funksvd_plan_order's")
+    if n and (users.min() < 0 or users.max() >= n_users or items.min() < 0
+              or items.max() >= n_items):
+        raise ValueError("funksvd_fit: a sample's user or item number is out of range")
+    budget = FUNKSVD_STEP_BUDGET if step_budget is None else int(step_budget)
+    per_launch = max(1, min(epochs, budget // max(n, 1)))
+
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    d_users, d_items = up(users[plan.order]), up(items[plan.order])
+    d_ratings, d_est = up(ratings[plan.order]), up(est[plan.order])
+    d_ptr, d_run = up(ptr), up(plan.run_end)
+    # one feature's column is one contiguous row of these
+    d_ut = torch.full((k, int(n_users)), float(initial), dtype=torch.float32, device=dev)
+    d_it = torch.full((k, int(n_items)), float(initial), dtype=torch.float32, device=dev)
+    d_sse = torch.zeros((k, epochs), dtype=torch.float64, device=dev)
+    flags = _native.FUNKSVD_GLOBAL_COLUMNS if global_columns else 0
+    torch.cuda.synchronize(dev)
+    t0 = perf_counter()
+    for f in range(k):
+        trail = initial * initial * (k - f - 1)  # funksvd.py:174, in Python floats
+        done = 0
+        while done < epochs:
+            e = min(per_launch, epochs - done)
+            check(lib.lk_funksvd_train_feature(
+                _ptr(d_users), _ptr(d_items), _ptr(d_ratings), _ptr(d_est), _ptr(d_ptr),
+                _ptr(d_run), plan.depth, _ptr(d_ut[f]), _ptr(d_it[f]), int(n_users),
+                int(n_items), e, int(done + e == epochs), float(lr), float(reg), float(trail),
+                float(rmin), float(rmax), flags, _ptr(d_sse[f, done:]), _stream()),
+                "lk_funksvd_train_feature")
+            done += e
+    torch.cuda.synchronize(dev)
+    t_train = perf_counter() - t0
+    sse = d_sse.cpu().numpy()
+    if stats is not None:
+        stats.update(plan_seconds=t_plan, train_seconds=t_train, depth=plan.depth,
+                     epochs_per_launch=per_launch, sse=sse)
+    rmse = np.sqrt(sse / max(n, 1))  # funksvd.rs:126
+    return (np.ascontiguousarray(d_ut.cpu().numpy().T), np.ascontiguousarray(d_it.cpu().numpy().T),
+            rmse)

@@ -1,6 +1,7 @@
 """
 Device scoring of factor models with bias terms, shared by the FlexMF scorers
-(``lkpy_amd.flexmf``) and the SVD scorer (``lkpy_amd.sklearn.svd``): the biases are extra columns
+(``lkpy_amd.flexmf``), the SVD scorer (``lkpy_amd.sklearn.svd``) and the FunkSVD scorer
+(``lkpy_amd.funksvd``): the biases are extra columns
 of the two operand matrices, so that a score is one inner product on ``lk_score_topk``,
 ``lk_score_dense`` or ``lk_mf_score_pairs``.
 
@@ -17,7 +18,7 @@ import torch
 
 from . import _device as D
 from ._queries import pack_histories, pack_targets, resolve_queries, user_numbers
-from .basic import HistoryBatch
+from .basic import HistoryBatch, _damping
 from .data import ItemList, RecQuery
 
 
@@ -168,11 +169,14 @@ class GlobalBiasPairScoring(BiasedFactorScoring):
         packed[2 * (nq + 1):2 * (nq + 1) + nq] = user_rows
         packed[2 * (nq + 1) + nq:] = item_nums
         d_packed = torch.from_numpy(packed).to(st["device"])
-        out = D.mf_score_pairs(users, st["Q"], self._score_k,
-                               d_packed[2 * (nq + 1):2 * (nq + 1) + nq],
-                               d_packed[:2 * (nq + 1)].view(torch.int64),
-                               d_packed[2 * (nq + 1) + nq:])
+        out = self._pair_scores(users, st["Q"], d_packed[2 * (nq + 1):2 * (nq + 1) + nq],
+                                d_packed[:2 * (nq + 1)].view(torch.int64),
+                                d_packed[2 * (nq + 1) + nq:], tgt_ptr)
         return out if device_output else out.cpu().numpy()
+
+    def _pair_scores(self, users, items, d_rows, d_ptr, d_nums, tgt_ptr):
+        "the kernel behind ``_score_rows`` (``tgt_ptr``: the host copy of the offsets ``d_ptr``)"
+        return D.mf_score_pairs(users, items, self._score_k, d_rows, d_ptr, d_nums)
 
     def score_candidates_batch(self, queries, tgt_ptr, item_nums, *, d_targets=None):
         """
@@ -208,3 +212,71 @@ class GlobalBiasPairScoring(BiasedFactorScoring):
 
     def __call__(self, query, items: ItemList) -> ItemList:
         return self.score_batch([query], [items])[0]
+
+
+class QueryUserBias:
+    """
+    For a :class:`GlobalBiasPairScoring` scorer whose biases are a ``BiasModel`` (``self.bias``):
+    the user bias of a query follows ``BiasModel.compute_for_items`` -- recomputed from the
+    query's rated history where it has one, the stored bias otherwise -- so the user operand's
+    bias column is set per query.  Mixed in before the scoring class (``BiasedSVDScorer``,
+    ``FunkSVDScorer``).
+    """
+
+    user_bias = property(lambda self: self.bias.user_biases)
+    item_bias = property(lambda self: self.bias.item_biases)
+    global_bias = property(lambda self: self.bias.global_bias)
+
+    def _device_item_bias(self):
+        def upload():
+            ib = self.bias.item_biases
+            return None if ib is None else torch.from_numpy(
+                np.ascontiguousarray(ib, dtype=np.float32)).to(D.device())
+
+        return self._device_cache("item_bias", upload, self.bias)
+
+    def _history_user_bias(self, query: RecQuery):
+        """The user bias ``BiasModel.compute_for_items`` computes from the query's rated history
+        (bias.py:211-229), or None where it takes the stored one."""
+        hist = query.query_items
+        ratings = hist.field("rating") if hist is not None else None
+        if ratings is None:
+            return None
+        b = self.bias
+        uoff = np.asarray(ratings, dtype=np.float64) - b.global_bias
+        if b.item_biases is not None:
+            nums = hist.numbers(vocabulary=b.items, missing="negative")
+            known = nums >= 0
+            uoff[known] -= b.item_biases[nums[known]]
+        ub = np.sum(uoff) / (np.sum(np.isfinite(uoff)) + _damping(b.damping, "user"))
+        return np.float32(0.0 if np.isnan(ub) else ub)
+
+    def _query_rows(self, queries):
+        """The users' operand rows with the bias column as ``compute_for_items`` sets it: from
+        the query's ratings where it has some (a ``HistoryBatch``: ``lk_bias_user_offsets`` on
+        the training matrix in HBM), else the stored bias the row already carries."""
+        u, valid = self._user_rows(user_numbers(queries, self.users))
+        if self.bias.user_biases is None or len(valid) == 0:
+            return u, valid
+        col = self.config.embedding_size + 1  # [x_u, 1, b_u, 1]
+        dev = u.device
+        if isinstance(queries, HistoryBatch):
+            mat = queries.lookup._device_matrix()
+            if not mat["has_ratings"]:
+                return u, valid
+            nums = torch.from_numpy(np.ascontiguousarray(queries.user_nums, np.int32)).to(dev)
+            ub, add = D.bias_user_offsets(mat["csr"], nums, self.bias.global_bias,
+                                          self._device_item_bias(),
+                                          _damping(self.bias.damping, "user"))
+            u[:, col] = torch.where(add.bool(), ub, u[:, col])
+            return u, valid
+        own = [self._history_user_bias(q) for q in queries]
+        rows = [i for i, b in enumerate(own) if b is not None]
+        if rows:
+            vals = np.asarray([own[i] for i in rows], dtype=np.float32)
+            u[torch.from_numpy(np.asarray(rows)).to(dev), col] = torch.from_numpy(vals).to(dev)
+        return u, valid
+
+    def _pair_operand(self, queries: list[RecQuery]):
+        u, valid = self._query_rows(queries)
+        return u, np.where(valid, np.arange(len(valid)), -1)

@@ -51,6 +51,7 @@ SPARSE_REDUCTIONS = {"sum": 0, "mean": 1, "max": 2}  # LK_SPARSE_SUM / _MEAN / _
 GEMM_LOWER = 1
 GEMM_K_FROM_COL = 2
 GEMM_K_FROM_ROW = 4
+FUNKSVD_GLOBAL_COLUMNS = 1  # LK_FUNKSVD_GLOBAL_COLUMNS: lk_funksvd_train_feature's flag
 
 
 class FlexMFTables(ctypes.Structure):
@@ -418,6 +419,15 @@ def _declare(lib):
         "lk_nmf_workspace_bytes": (c_size_t, [c_int64]),
         "lk_nmf_cd_sweep": (
             c_int, [vp, c_int64, c_int32, c_int32, vp, c_int32, vp, c_float, vp, vp, vp]
+        ),
+        "lk_funksvd_narrow_width": (c_int32, []),
+        "lk_funksvd_stage_samples": (c_int32, []),
+        "lk_funksvd_lds_column_bytes": (c_size_t, []),
+        "lk_funksvd_plan_levels": (c_int, [vp, vp, c_int64, c_int64, c_int64, vp, POINTER(c_int32)]),
+        "lk_funksvd_plan_order": (c_int, [vp, c_int64, c_int32, vp, vp, vp]),
+        "lk_funksvd_train_feature": (
+            c_int, [vp, vp, vp, vp, vp, vp, c_int32, vp, vp, c_int64, c_int64, c_int32, c_int32]
+            + [ctypes.c_double] * 5 + [c_int32, vp, vp]
         ),
         "lk_als_implicit_half_epoch_host": (
             c_int,

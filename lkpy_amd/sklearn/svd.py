@@ -14,7 +14,7 @@ The trained model is a factor model with biases, so it scores through
 :class:`lkpy_amd._factor_scoring.GlobalBiasPairScoring` like ``FlexMFExplicitScorer``.  One thing
 differs: the user bias of a query follows ``BiasModel.compute_for_items`` -- recomputed from the
 query's rated history where it has one, the stored bias otherwise -- so the user operand's bias
-column is set per query.
+column is set per query (:class:`lkpy_amd._factor_scoring.QueryUserBias`).
 """
 
 from __future__ import annotations
@@ -22,15 +22,13 @@ from __future__ import annotations
 from typing import Literal
 
 import numpy as np
-import torch
 from pydantic import AliasChoices, BaseModel, Field
 
 from .. import _device as D
-from .._factor_scoring import GlobalBiasPairScoring
-from .._queries import user_numbers
+from .._factor_scoring import GlobalBiasPairScoring, QueryUserBias
 from ..als import _scorer_state
-from ..basic import BiasModel, HistoryBatch, _damping
-from ..data import Dataset, RecQuery, Vocabulary
+from ..basic import BiasModel
+from ..data import Dataset, Vocabulary
 from ..pipeline import Component
 from ..training import Trainable, TrainingOptions
 
@@ -76,7 +74,7 @@ class Factorization:
         return np.asarray(X) @ self.components_
 
 
-class BiasedSVDScorer(GlobalBiasPairScoring, Component, Trainable):
+class BiasedSVDScorer(QueryUserBias, GlobalBiasPairScoring, Component, Trainable):
     """
     Biased matrix factorisation by truncated SVD of the bias residuals.  Learned state: ``bias``
     (:class:`BiasModel`), ``users``, ``items``, ``user_components`` [users x k] float32 (sklearn's
@@ -141,60 +139,3 @@ class BiasedSVDScorer(GlobalBiasPairScoring, Component, Trainable):
     # -- what the shared scoring reads -------------------------------------------------------
     user_embeddings = property(lambda self: self.user_components)
     item_embeddings = property(lambda self: self.factorization.item_factors)
-    user_bias = property(lambda self: self.bias.user_biases)
-    item_bias = property(lambda self: self.bias.item_biases)
-    global_bias = property(lambda self: self.bias.global_bias)
-
-    def _device_item_bias(self):
-        def upload():
-            ib = self.bias.item_biases
-            return None if ib is None else torch.from_numpy(
-                np.ascontiguousarray(ib, dtype=np.float32)).to(D.device())
-
-        return self._device_cache("item_bias", upload, self.bias)
-
-    def _history_user_bias(self, query: RecQuery):
-        """The user bias ``BiasModel.compute_for_items`` computes from the query's rated history
-        (bias.py:211-229), or None where it takes the stored one."""
-        hist = query.query_items
-        ratings = hist.field("rating") if hist is not None else None
-        if ratings is None:
-            return None
-        b = self.bias
-        uoff = np.asarray(ratings, dtype=np.float64) - b.global_bias
-        if b.item_biases is not None:
-            nums = hist.numbers(vocabulary=b.items, missing="negative")
-            known = nums >= 0
-            uoff[known] -= b.item_biases[nums[known]]
-        ub = np.sum(uoff) / (np.sum(np.isfinite(uoff)) + _damping(b.damping, "user"))
-        return np.float32(0.0 if np.isnan(ub) else ub)
-
-    def _query_rows(self, queries):
-        """The users' operand rows with the bias column as ``compute_for_items`` sets it: from
-        the query's ratings where it has some (a ``HistoryBatch``: ``lk_bias_user_offsets`` on
-        the training matrix in HBM), else the stored bias the row already carries."""
-        u, valid = self._user_rows(user_numbers(queries, self.users))
-        if self.bias.user_biases is None or len(valid) == 0:
-            return u, valid
-        col = self.config.embedding_size + 1  # [x_u, 1, b_u, 1]
-        dev = u.device
-        if isinstance(queries, HistoryBatch):
-            mat = queries.lookup._device_matrix()
-            if not mat["has_ratings"]:
-                return u, valid
-            nums = torch.from_numpy(np.ascontiguousarray(queries.user_nums, np.int32)).to(dev)
-            ub, add = D.bias_user_offsets(mat["csr"], nums, self.bias.global_bias,
-                                          self._device_item_bias(),
-                                          _damping(self.bias.damping, "user"))
-            u[:, col] = torch.where(add.bool(), ub, u[:, col])
-            return u, valid
-        own = [self._history_user_bias(q) for q in queries]
-        rows = [i for i, b in enumerate(own) if b is not None]
-        if rows:
-            vals = np.asarray([own[i] for i in rows], dtype=np.float32)
-            u[torch.from_numpy(np.asarray(rows)).to(dev), col] = torch.from_numpy(vals).to(dev)
-        return u, valid
-
-    def _pair_operand(self, queries: list[RecQuery]):
-        u, valid = self._query_rows(queries)
-        return u, np.where(valid, np.arange(len(valid)), -1)
