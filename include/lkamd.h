@@ -148,9 +148,16 @@ int lk_als_plan_create(lk_als_plan **out, const void *h_indptr, int indptr_is_64
  * LK_ALS_PLAN_REFERENCE_ORDER: the strict variant -- EVERY row of more than 256 entries in
  * 256-entry chunks and every dense row's y by the chain; takes y from
  * lk_als_plan_set_rhs_workspace ([n_rows x lk_padded_dim(k)], mandatory for it), no task control.
- * tests/test_gpu_als_rhs_order.py. */
+ * tests/test_gpu_als_rhs_order.py.
+ *
+ * LK_ALS_PLAN_BAND_UNITS (with either of the above or alone): the caller will list the work units
+ * band by band (lk_als_plan_order_units, below).  Hybrid plans at padded k = 64 then take a unit
+ * per 256-entry block whatever their size -- the bands are tightest and the epoch measured fastest
+ * that way; LK_ALS_REF_UNIT still overrides, and under LK_ALS_UNIT_ORDER=0 the
+ * flag does nothing.  Other plans ignore it. */
 #define LK_ALS_PLAN_REFERENCE_ORDER 1
 #define LK_ALS_PLAN_HYBRID_ORDER 2
+#define LK_ALS_PLAN_BAND_UNITS 4
 int lk_als_plan_create_ex(lk_als_plan **out, const void *h_indptr, int indptr_is_64,
                           int64_t n_rows, int32_t k, int32_t solver, int32_t flags);
 void lk_als_plan_destroy(lk_als_plan *plan);
@@ -164,6 +171,26 @@ int64_t lk_als_plan_long_rows(const lk_als_plan *plan);
  * -- unless LK_ALS_REF_UNIT says otherwise. */
 int64_t lk_als_plan_units(const lk_als_plan *plan);
 int32_t lk_als_plan_unit(const lk_als_plan *plan);
+/* Opt-in, once per plan at set-up, padded k <= 64: list the work units band by band instead of row
+ * by row, so that the chunk workgroups resident on one XCD gather the same band of `other` at the
+ * same time and share it in that XCD's L2.  A unit's key is the band it starts
+ * in: col_key[c] of its first column c (`d_col_key`, n_col_key int32 words), or c itself when
+ * d_col_key is NULL -- pass the map under which the rows' entries ascend (a relabelled engine
+ * lists a row's entries by ascending ORIGINAL column: the map is original-of-new; first columns
+ * outside the map keep c).  The units are sorted by (key, row, offset) and dealt so that the
+ * workgroups one XCD receives (physical workgroup b on XCD b % 8) hold one contiguous run of the
+ * sorted list, ascending along b; only the physically last workgroup may hold fewer than four
+ * units.  Only the unit table moves: slabs, slab groups, the row order and every sum are what they
+ * were, so no result changes by a bit.  Plans without long rows, plans of padded k > 64 and every
+ * plan under LK_ALS_UNIT_ORDER=0 are left as they are; calling it again gives the same table.
+ * Blocking (it waits for the device, copies the keys to the host and the table back): not for
+ * plans built per call.  `d_indices` is the array the half-epochs are given. */
+int lk_als_plan_order_units(lk_als_plan *plan, const int32_t *d_indices, const int32_t *d_col_key,
+                            int64_t n_col_key, void *stream);
+/* The unit table in launch order -- first CSR entry, entries and first slab of each of the
+ * lk_als_plan_units units (any pointer may be NULL) -- by a blocking copy: tests and tools. */
+int lk_als_plan_unit_table(const lk_als_plan *plan, int64_t *out_beg, int32_t *out_len,
+                           int32_t *out_slab);
 /* Hybrid plans: the right-hand sides of those rows as the last half-epoch run with workspace
  * `d_ws` formed them in the reference's order -- [lk_als_plan_long_rows x lk_padded_dim(k)]
  * floats, row t = the t-th longest row (device pointer into d_ws; NULL for other plans).

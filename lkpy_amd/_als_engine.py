@@ -457,7 +457,8 @@ class HipBackend:
             view = D.DeviceCSR(full.indptr[lo : hi + 1], full.indices, full.values,
                                (hi - lo, n_cols), h_ptr[lo : hi + 1])
             view.full_h_indptr = h_ptr  # offsets of ALL rows (every rank holds the full arrays)
-            return D.ALSPlan(view, self.k, self.solver, reference_order=self.order_mode)
+            return D.ALSPlan(view, self.k, self.solver, reference_order=self.order_mode,
+                             band_units=True)  # (order_units below)
 
         def plans(full, h_ptr, rngs, n_cols):
             if isinstance(rngs, tuple):
@@ -505,13 +506,31 @@ class HipBackend:
                 view = D.DeviceCSR(full.indptr[lo : hi + 1], full.indices, full.values,
                                    (hi - lo, n_cols), h_ptr[lo : hi + 1])
                 view.full_h_indptr = None  # no rank holds the offsets of all rows
-                ps.append(D.ALSPlan(view, self.k, self.solver, reference_order=self.order_mode))
+                ps.append(D.ALSPlan(view, self.k, self.solver, reference_order=self.order_mode,
+                                    band_units=True))  # (order_units below)
                 lo = hi
             return (ps[0] if len(ps) == 1 else D.ALSPlanGroup(ps, n_cols)), int(h_ptr[-1])
 
         up, unnz = plans(out["u"], ub, n_items_new)
         ip, innz = plans(out["i"], ib, len(u_old))
         return up, ip, (unnz, innz)
+
+    def order_units(self, u_plans, i_old, i_plans, u_old):
+        """
+        Once per plan at set-up (padded k <= 64): the long rows' work units band
+        by band per XCD.  The plans of ``make_plans_on_device`` / ``make_plans_sharded`` list a
+        row's entries by ascending ORIGINAL label of the other side, so a unit's band is the
+        original label of its first column (``accurate`` order: item rows ascend by new user).
+        """
+        if self.kp > 64:
+            return  # (the plans' band_units flag does nothing there either)
+        to = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.dev)  # noqa: E731
+        i_key = to(i_old)
+        for p in u_plans:
+            p.order_units(i_key)
+        u_key = None if self.order_mode == "accurate" else to(u_old)
+        for p in i_plans:
+            p.order_units(u_key)
 
     def upload(self, mat: np.ndarray) -> torch.Tensor:
         return self.D.to_device_padded(mat, self.dev)
@@ -667,6 +686,8 @@ class ImplicitALSEngine:
                     self.i_blocks[0] if S == 1 else self.i_blocks, ilen)
             self.u_plans = [self.u_plan] if S == 1 else self.u_plan.plans
             self.i_plans = [self.i_plan] if S == 1 else self.i_plan.plans
+            if hasattr(backend, "order_units"):
+                backend.order_units(self.u_plans, self.i_old, self.i_plans, self.u_old)
         elif self.sharded_setup:  # the same per-rank set-up on host tensors (gloo tests)
             assert not on_device
             out = shard_local_blocks(

@@ -310,8 +310,11 @@ class ALSPlan:
     "Row schedule + workspace of one CSR orientation (lk_als_plan)."
 
     def __init__(self, csr: DeviceCSR, k: int, solver: int = _native.SOLVER_AUTO,
-                 reference_order: "bool | str | None" = None):
-        """``reference_order`` -- how the two long sums of a row (normal matrix, right-hand side)
+                 reference_order: "bool | str | None" = None, band_units: bool = False):
+        """``band_units``: the caller will call :meth:`order_units` (LK_ALS_PLAN_BAND_UNITS: a
+        padded k = 64 plan then cuts its long rows into a unit per 256-entry block).
+
+        ``reference_order`` -- how the two long sums of a row (normal matrix, right-hand side)
         are ordered (include/lkamd.h, ``lk_als_plan_create_ex``; INTEGRATION.md, ``LK_ALS_RHS_ORDER``):
 
         * ``"auto"`` (the default): rows longer than ``LK_ALS_REF_LEN`` (2048) entries in the
@@ -334,6 +337,8 @@ class ALSPlan:
             self.order_mode = "accurate"  # (no reference arithmetic to reproduce / no slab path)
         self.reference_order = self.order_mode == "reference"
         flags = {"accurate": 0, "reference": 1, "auto": 2}[self.order_mode]
+        if band_units:
+            flags |= 4  # LK_ALS_PLAN_BAND_UNITS
         check(
             lib.lk_als_plan_create_ex(
                 ctypes.byref(self._h), hp.ctypes.data_as(ctypes.c_void_p),
@@ -403,6 +408,29 @@ class ALSPlan:
     def long_rows(self) -> int:
         "rows of the plan that are pre-reduced in chunks (the first tasks of the longest-first order)"
         return int(_native.load().lk_als_plan_long_rows(self._h))
+
+    def order_units(self, col_key: "torch.Tensor | None" = None):
+        """
+        Once at set-up (it blocks): list the long rows' work units band by band per XCD instead of
+        row by row (``lk_als_plan_order_units``).  ``col_key``: int32 device map
+        under which the rows' entries ascend (original-of-new for a relabelled matrix); None =
+        the columns themselves.  No result changes; ``LK_ALS_UNIT_ORDER=0`` keeps today's order.
+        """
+        if col_key is not None:
+            assert col_key.dtype == torch.int32 and col_key.is_contiguous()
+        check(_native.load().lk_als_plan_order_units(
+            self._h, _ptr(self.csr.indices), _ptr(col_key) if col_key is not None else None,
+            0 if col_key is None else col_key.numel(), _stream()), "lk_als_plan_order_units")
+
+    def unit_table(self):
+        "(first entry, entries, first slab) of the work units in launch order, as host arrays"
+        lib = _native.load()
+        n = int(lib.lk_als_plan_units(self._h))
+        beg, ln, slab = np.zeros(n, np.int64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        as_p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        check(lib.lk_als_plan_unit_table(self._h, as_p(beg), as_p(ln), as_p(slab)),
+              "lk_als_plan_unit_table")
+        return beg, ln, slab
 
     def yref_tasks(self) -> "torch.Tensor | None":
         """Hybrid plans: the right-hand sides the last half-epoch formed in the reference's order,

@@ -110,6 +110,8 @@ def _declare(lib):
         "lk_als_plan_long_rows": (c_int64, [vp]),
         "lk_als_plan_units": (c_int64, [vp]),
         "lk_als_plan_unit": (c_int32, [vp]),
+        "lk_als_plan_order_units": (c_int, [vp, vp, vp, c_int64, vp]),
+        "lk_als_plan_unit_table": (c_int, [vp, vp, vp, vp]),
         "lk_als_plan_yref": (vp, [vp, vp]),
         "lk_als_plan_woodbury_rows": (c_int64, [vp]),
         "lk_als_plan_set_z": (c_int, [vp, vp]),

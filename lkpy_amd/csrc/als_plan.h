@@ -91,7 +91,8 @@ struct lk_als_plan {
     // several blocks -- one wave / workgroup runs its gather ring across the 256-entry blocks of a
     // unit and stores a slab at every block boundary (d_chunk_slab = the unit's first slab).
     // k = 256: 1024 entries.  k = 64: 1024, 512 or 256, the largest for which the plan still has
-    // twice as many units as the device holds chunk waves (lk_als_plan_create_ex; LK_ALS_REF_UNIT
+    // twice as many units as the device holds chunk waves, or 256 for a plan whose units the
+    // caller orders band by band -- LK_ALS_PLAN_BAND_UNITS (lk_als_plan_create_ex; LK_ALS_REF_UNIT
     // overrides).  Everywhere else a unit is one chunk
     int32_t unit = LK_ALS_CHUNK;
     int64_t n_slabs = 0;                 // slabs of all long rows (n_chunks counts the UNITS)

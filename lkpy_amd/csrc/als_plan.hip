@@ -1,7 +1,8 @@
 // als_plan.hip -- the ALS plan object (als_plan.h): its construction, queries and settings, the
 // dispatch of a half-epoch to the solver families (als_chol.hip: padded k <= 64, als_blk.hip:
 // 128 / 256, als_big.hip: above 256, als_cg.hip: the CG option), the status read and the
-// host-buffer entries.  Host code only: every kernel is launched from the family's own file.
+// host-buffer entries.  Host code but for the key read of lk_als_plan_order_units: every kernel of
+// a half-epoch is launched from the family's own file.
 //
 // Which kernel takes which task range is decided here, once, when the plan is created: the
 // switches that choose them (LK_ALS_WB*, LK_ALS_SIDE_STREAM, LK_BLK_CHUNK_DMA, LK_ALS_CG_HYBRID;
@@ -178,7 +179,8 @@ extern "C" int lk_als_plan_create_ex(lk_als_plan **out, const void *h_indptr, in
                                      int64_t n_rows, int32_t k, int32_t solver, int32_t flags)
 {
     LK_REQUIRE(out != nullptr && h_indptr != nullptr, "lk_als_plan_create: null pointer");
-    LK_REQUIRE((flags & ~(LK_ALS_PLAN_REFERENCE_ORDER | LK_ALS_PLAN_HYBRID_ORDER)) == 0,
+    LK_REQUIRE((flags & ~(LK_ALS_PLAN_REFERENCE_ORDER | LK_ALS_PLAN_HYBRID_ORDER |
+                          LK_ALS_PLAN_BAND_UNITS)) == 0,
                "lk_als_plan_create_ex: unknown flags");
     LK_REQUIRE((flags & (LK_ALS_PLAN_REFERENCE_ORDER | LK_ALS_PLAN_HYBRID_ORDER)) !=
                    (LK_ALS_PLAN_REFERENCE_ORDER | LK_ALS_PLAN_HYBRID_ORDER),
@@ -323,7 +325,12 @@ extern "C" int lk_als_plan_create_ex(lk_als_plan **out, const void *h_indptr, in
     if (p->hybrid && (KP == 64 || p->chunk_dma)) {
         const char *e = getenv("LK_ALS_REF_UNIT");
         int u = e ? atoi(e) : LK_ALS_CHUNK;
-        if (!e && KP == 64) {
+        // LK_ALS_PLAN_BAND_UNITS: the caller orders the units band by band
+        // (lk_als_plan_order_units) -- a unit per block keeps the bands tightest and measured
+        // fastest; LK_ALS_UNIT_ORDER=0 keeps today's rule with today's order
+        if (!e && KP == 64 && (flags & LK_ALS_PLAN_BAND_UNITS) && switch_on("LK_ALS_UNIT_ORDER"))
+            u = p->chunk;
+        else if (!e && KP == 64) {
             // als_chunk_kernel runs one wave per unit: the largest unit of 1024 / 512 / 256 entries
             // that still gives every chunk wave the device holds two units (a plan with fewer
             // long-row entries than that fills the machine only with a unit per block: ML-25M's
@@ -565,6 +572,109 @@ extern "C" int64_t lk_als_plan_long_rows(const lk_als_plan *p) { return p ? p->n
 extern "C" int64_t lk_als_plan_units(const lk_als_plan *p) { return p ? p->n_chunks : 0; }
 extern "C" int32_t lk_als_plan_unit(const lk_als_plan *p) { return p ? p->unit : 0; }
 
+// ---- the order of the work units ----
+namespace {
+struct DevBuf {
+    void *p = nullptr;
+    ~DevBuf()
+    {
+        if (p) (void)hipFree(p);
+    }
+    int alloc(size_t bytes)
+    {
+        LK_HIP_CHECK(hipMalloc(&p, bytes ? bytes : 1));
+        return LK_OK;
+    }
+};
+
+// keys[u] = the band unit u starts in: its first column, through col_key where the map covers it
+__global__ __launch_bounds__(256) void unit_key_kernel(const int32_t *__restrict__ indices,
+                                                       const int64_t *__restrict__ chunk_beg,
+                                                       int64_t n_units,
+                                                       const int32_t *__restrict__ col_key,
+                                                       int64_t n_col_key, int32_t *__restrict__ keys)
+{
+    const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (u >= n_units) return;
+    const int32_t c = indices[chunk_beg[u]];  // (a unit has at least one entry)
+    keys[u] = (col_key && c >= 0 && c < n_col_key) ? col_key[c] : c;
+}
+}  // namespace
+
+extern "C" int lk_als_plan_order_units(lk_als_plan *p, const int32_t *d_indices,
+                                       const int32_t *d_col_key, int64_t n_col_key, void *stream)
+{
+    LK_REQUIRE(p != nullptr, "lk_als_plan_order_units: null plan");
+    // (padded k > 64: als_blk.hip's register-ring launch takes slab = unit, in table order)
+    if (p->n_chunks == 0 || p->KP > 64 || !switch_on("LK_ALS_UNIT_ORDER")) return LK_OK;
+    LK_REQUIRE(d_indices != nullptr, "lk_als_plan_order_units: null indices");
+    LK_REQUIRE(d_col_key == nullptr || n_col_key > 0, "lk_als_plan_order_units: empty key map");
+    hipStream_t st = lk::as_stream(stream);
+    const size_t n = (size_t)p->n_chunks;
+    // no launch of the plan may read the table while it is rewritten (side streams included)
+    LK_HIP_CHECK(hipDeviceSynchronize());
+    DevBuf d_keys;
+    int rc = d_keys.alloc(n * sizeof(int32_t));
+    if (rc != LK_OK) return rc;
+    hipLaunchKernelGGL(unit_key_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                       d_indices, p->d_chunk_beg, (int64_t)n, d_col_key, n_col_key,
+                       static_cast<int32_t *>(d_keys.p));
+    LK_HIP_CHECK(hipGetLastError());
+    std::vector<int32_t> key(n), row(n), len(n), slab(n);
+    std::vector<int64_t> beg(n);
+    LK_HIP_CHECK(hipMemcpyAsync(key.data(), d_keys.p, n * 4, hipMemcpyDeviceToHost, st));
+    LK_HIP_CHECK(hipMemcpyAsync(row.data(), p->d_chunk_row, n * 4, hipMemcpyDeviceToHost, st));
+    LK_HIP_CHECK(hipMemcpyAsync(len.data(), p->d_chunk_len, n * 4, hipMemcpyDeviceToHost, st));
+    LK_HIP_CHECK(hipMemcpyAsync(slab.data(), p->d_chunk_slab, n * 4, hipMemcpyDeviceToHost, st));
+    LK_HIP_CHECK(hipMemcpyAsync(beg.data(), p->d_chunk_beg, n * 8, hipMemcpyDeviceToHost, st));
+    LK_HIP_CHECK(hipStreamSynchronize(st));
+    // (key, row, offset): a total order of the units, whatever order the table is in now -- a
+    // second call sorts the same list
+    std::vector<int64_t> sorted(n);
+    for (size_t u = 0; u < n; ++u) sorted[u] = (int64_t)u;
+    std::sort(sorted.begin(), sorted.end(), [&](int64_t a, int64_t b) {
+        if (key[a] != key[b]) return key[a] < key[b];
+        if (row[a] != row[b]) return row[a] < row[b];
+        return beg[a] < beg[b];
+    });
+    // XCD x receives the physical workgroups b = x, x + 8, ...: they take the next units of the
+    // sorted list, four each; the physically last workgroup, wherever it falls, takes what is
+    // left of four
+    const int64_t n_wg = ((int64_t)n + 3) / 4;
+    std::vector<int32_t> o_row(n), o_len(n), o_slab(n);
+    std::vector<int64_t> o_beg(n);
+    size_t next = 0;
+    for (int64_t x = 0; x < (int64_t)lk::XCD_COUNT; ++x)
+        for (int64_t b = x; b < n_wg; b += lk::XCD_COUNT)
+            for (size_t at = (size_t)b * 4; at < std::min<size_t>((size_t)b * 4 + 4, n); ++at) {
+                const size_t u = (size_t)sorted[next++];
+                o_row[at] = row[u];
+                o_len[at] = len[u];
+                o_slab[at] = slab[u];
+                o_beg[at] = beg[u];
+            }
+    LK_HIP_CHECK(hipMemcpyAsync(p->d_chunk_row, o_row.data(), n * 4, hipMemcpyHostToDevice, st));
+    LK_HIP_CHECK(hipMemcpyAsync(p->d_chunk_len, o_len.data(), n * 4, hipMemcpyHostToDevice, st));
+    LK_HIP_CHECK(hipMemcpyAsync(p->d_chunk_slab, o_slab.data(), n * 4, hipMemcpyHostToDevice, st));
+    LK_HIP_CHECK(hipMemcpyAsync(p->d_chunk_beg, o_beg.data(), n * 8, hipMemcpyHostToDevice, st));
+    // (the half-epochs may run on other streams than `st`, and the host arrays end here)
+    LK_HIP_CHECK(hipDeviceSynchronize());
+    return LK_OK;
+}
+
+extern "C" int lk_als_plan_unit_table(const lk_als_plan *p, int64_t *out_beg, int32_t *out_len,
+                                      int32_t *out_slab)
+{
+    LK_REQUIRE(p != nullptr, "lk_als_plan_unit_table: null plan");
+    const size_t n = (size_t)p->n_chunks;
+    if (n == 0) return LK_OK;
+    LK_HIP_CHECK(hipDeviceSynchronize());
+    if (out_beg) LK_HIP_CHECK(hipMemcpy(out_beg, p->d_chunk_beg, n * 8, hipMemcpyDeviceToHost));
+    if (out_len) LK_HIP_CHECK(hipMemcpy(out_len, p->d_chunk_len, n * 4, hipMemcpyDeviceToHost));
+    if (out_slab) LK_HIP_CHECK(hipMemcpy(out_slab, p->d_chunk_slab, n * 4, hipMemcpyDeviceToHost));
+    return LK_OK;
+}
+
 extern "C" const float *lk_als_plan_yref(const lk_als_plan *p, const void *d_ws)
 {
     if (!p || !d_ws || !p->hybrid) return nullptr;
@@ -761,21 +871,6 @@ extern "C" int lk_als_check_status(const lk_als_plan *plan, void *d_ws, void *st
     }
     return LK_OK;
 }
-
-namespace {
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf()
-    {
-        if (p) (void)hipFree(p);
-    }
-    int alloc(size_t bytes)
-    {
-        LK_HIP_CHECK(hipMalloc(&p, bytes ? bytes : 1));
-        return LK_OK;
-    }
-};
-}  // namespace
 
 extern "C" int lk_als_implicit_half_epoch_host_ctl(const void *h_indptr, int indptr_is_64,
                                                    const int32_t *h_indices,

@@ -160,9 +160,10 @@ struct PerDeviceOnce {
 // the same XCD (dispatcher places physical block b on XCD b % 8), so blocks
 // that share operand panels share an L2.  Bijective for any grid size
 // (cdna_hip_programming.md, "XCD swizzle must be bijective").
+constexpr unsigned XCD_COUNT = 8;  // (host code that lays work out per XCD reads it too)
 __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg)
 {
-    const unsigned nx = 8;
+    const unsigned nx = XCD_COUNT;
     unsigned q = nwg / nx, r = nwg % nx;
     unsigned xcd = bid % nx, pos = bid / nx;
     unsigned base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
