@@ -238,7 +238,8 @@ class TaskCtl:
     def progress(self) -> tuple[int, int]:
         "(rows done, rows total) of the call in flight (or of the last finished one)"
         d, t = ctypes.c_int64(0), ctypes.c_int64(0)
-        check(_native.load().lk_task_ctl_progress(self._h, ctypes.byref(d), ctypes.byref(t)))
+        check(_native.load().lk_task_ctl_progress(self._h, ctypes.byref(d), ctypes.byref(t)),
+              "lk_task_ctl_progress")
         return int(d.value), int(t.value)
 
     def __del__(self):
@@ -336,15 +337,16 @@ class ALSPlan:
         if int(solver) == _native.SOLVER_CG or self.kp > 256:
             self.order_mode = "accurate"  # (no reference arithmetic to reproduce / no slab path)
         self.reference_order = self.order_mode == "reference"
-        flags = {"accurate": 0, "reference": 1, "auto": 2}[self.order_mode]
+        flags = {"accurate": 0, "reference": _native.H["LK_ALS_PLAN_REFERENCE_ORDER"],
+                 "auto": _native.H["LK_ALS_PLAN_HYBRID_ORDER"]}[self.order_mode]
         if band_units:
-            flags |= 4  # LK_ALS_PLAN_BAND_UNITS
+            flags |= _native.H["LK_ALS_PLAN_BAND_UNITS"]
         check(
             lib.lk_als_plan_create_ex(
                 ctypes.byref(self._h), hp.ctypes.data_as(ctypes.c_void_p),
                 1 if hp.dtype == np.int64 else 0, csr.shape[0], self.k, int(solver), flags
             ),
-            "lk_als_plan_create",
+            "lk_als_plan_create_ex",
         )  # fmt: skip
         dev = csr.indices.device
         self.ws = torch.empty(lib.lk_als_plan_workspace_bytes(self._h), dtype=torch.uint8,
@@ -468,10 +470,12 @@ class ALSPlan:
     def set_ctl(self, ctl: "TaskCtl | None"):
         "Attach (or detach) a cancel / progress block; check_status then reports a cancel."
         self._ctl = ctl  # keep it alive as long as the plan refers to it
-        check(_native.load().lk_als_plan_set_ctl(self._h, ctl._h if ctl is not None else None))
+        check(_native.load().lk_als_plan_set_ctl(self._h, ctl._h if ctl is not None else None),
+              "lk_als_plan_set_ctl")
 
     def set_cg(self, tol: float, max_iter: int = 0):
-        check(_native.load().lk_als_plan_set_cg(self._h, float(tol), int(max_iter)))
+        check(_native.load().lk_als_plan_set_cg(self._h, float(tol), int(max_iter)),
+              "lk_als_plan_set_cg")
 
     def cg_stats(self):
         "(CG iterations, non-empty rows) of the last CG half-epoch on this plan (blocking)"
@@ -479,7 +483,8 @@ class ALSPlan:
 
         it, rows = ctypes.c_int64(0), ctypes.c_int64(0)
         check(_native.load().lk_als_plan_cg_stats(self._h, _ptr(self.ws), _stream(),
-                                                   ctypes.byref(it), ctypes.byref(rows)))
+                                                   ctypes.byref(it), ctypes.byref(rows)),
+              "lk_als_plan_cg_stats")
         return int(it.value), int(rows.value)
 
     def half_epoch(self, this: torch.Tensor, other: torch.Tensor, otor: torch.Tensor):
@@ -538,7 +543,8 @@ class ALSPlan:
         return self.frob
 
     def enable_timing(self, enable: bool = True):
-        check(_native.load().lk_als_plan_enable_timing(self._h, 1 if enable else 0))
+        check(_native.load().lk_als_plan_enable_timing(self._h, 1 if enable else 0),
+              "lk_als_plan_enable_timing")
 
     def get_timing(self):
         "-> (ms in the chunk kernel, ms in the solve kernel, half-epochs recorded); resets."
@@ -546,13 +552,15 @@ class ALSPlan:
         check(
             _native.load().lk_als_plan_get_timing(
                 self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(n)
-            )
+            ),
+            "lk_als_plan_get_timing",
         )
         return a.value, b.value, n.value
 
     def check_status(self):
         "Synchronise and raise RuntimeError('ALS solve error: ...') on a failed solve."
-        check(_native.load().lk_als_check_status(self._h, _ptr(self.ws), _stream()))
+        check(_native.load().lk_als_check_status(self._h, _ptr(self.ws), _stream()),
+              "lk_als_check_status")
 
     def __del__(self):
         try:
@@ -773,7 +781,8 @@ def iknn_build(ui: DeviceCSR, iu: DeviceCSR, min_sim: float, save_nbrs=None,
         torch.cuda.current_stream().synchronize()
         if timing is not None:
             ms, nl = ctypes.c_double(0), ctypes.c_int32(0)
-            check(lib.lk_iknn_plan_get_timing(h, ctypes.byref(ms), ctypes.byref(nl)))
+            check(lib.lk_iknn_plan_get_timing(h, ctypes.byref(ms), ctypes.byref(nl)),
+                  "lk_iknn_plan_get_timing")
             timing["build_kernel_ms"] = ms.value
             timing["build_kernel_launches"] = nl.value
     finally:

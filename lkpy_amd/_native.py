@@ -1,6 +1,14 @@
 """
 ctypes binding of the C ABI declared in ``include/lkamd.h`` (``lkpy_amd/_lkamd.so``).
 
+The header is the only description of the ABI: :func:`parse_header` reads every ``lk_*``
+prototype and every integer ``#define LK_*`` from it when this module is imported, and
+:func:`load` sets each function's ``restype`` / ``argtypes`` from that.  A new entry point
+needs its prototype in the header, its wrapper in ``_device.py`` and its mention in
+``INTEGRATION.md``, nothing here; a new constant needs its ``#define`` and, if Python names
+it, one line below.  Only the two ``lk_flexmf_*`` structs are written out again
+(tests/test_native_abi.py pins them to the header).
+
 The product path has NO CPU fallback: if the HIP library is missing or there is no
 GPU, the calls raise (:class:`BackendUnavailable`).  Loading the library and listing
 its symbols works without a GPU (used by the CPU-only tests).
@@ -11,7 +19,7 @@ from __future__ import annotations
 import ctypes
 import os
 import re
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import c_char_p, c_int32, c_int64, c_void_p
 from pathlib import Path
 
 _PKG = Path(__file__).resolve().parent
@@ -19,39 +27,91 @@ _PKG = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("LK_AMD_LIBRARY", _PKG / "_lkamd.so"))
 HEADER_PATH = _PKG.parent / "include" / "lkamd.h"
 
-LK_OK = 0
-LK_E_INVALID = -1
-LK_E_HIP = -2
-LK_E_NOT_SPD = -3
-LK_E_NAN_SIM = -4
-LK_E_NOMEM = -5
-LK_E_CANCELLED = -6
-
-SOLVER_CHOLESKY = 0
-SOLVER_CG = 1
-SOLVER_AUTO = 2
+_SCALARS = {"int": ctypes.c_int, "int32_t": c_int32, "int64_t": c_int64,
+            "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double,
+            "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64}
+_DEFINE = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(LK_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", re.M)
+_SYMBOL = re.compile(r"\b(lk_[a-z0-9_]+)\s*\(")
+# result type, name, parameter list of `<type> lk_name(<parameters>);` at statement level
+_PROTOTYPE = re.compile(
+    r"(?:\A|(?<=[;{}]))\s*([A-Za-z_][\w\s*]*?)" + _SYMBOL.pattern + r"([^;{}]*)\)\s*;")
 
 
-FLEXMF_LOSSES = {"logistic": 0, "pairwise": 1, "warp": 2}
-FLEXMF_MSE = 3  # lk_flexmf_step_explicit's loss
-FLEXMF_ADAMW = 0
-FLEXMF_SPARSE_ADAM = 1
-FLEXMF_MAX_K = 256
+def _ctype(decl: str, result: bool = False):
+    "The ctypes type of one parameter declaration (or result type); no guess at an unknown one."
+    if re.search(r"[\[()]|\.\.\.", decl):
+        raise ValueError(f"lkamd.h: array, function pointer or variable arguments in {decl!r}")
+    words = [w for w in decl.replace("*", " * ").split() if w != "const"]
+    if "*" in words:
+        return c_char_p if result and words == ["char", "*"] else c_void_p
+    base = " ".join(words if result or len(words) == 1 else words[:-1])  # less the parameter's name
+    if result and base == "void":
+        return None
+    if base not in _SCALARS:
+        raise ValueError(f"lkamd.h: unknown type {base!r} in {decl!r}")
+    return _SCALARS[base]
 
-STOCHASTIC_TRANSFORMS = {None: 0, "softmax": 1, "linear": 2}
 
-FAIR_MAX_N = 1024  # LK_FAIR_MAX_N (lk_fair_max_n()): the list length lk_fair_rerank's LDS holds
+def parse_header(text: str):
+    """
+    ``(prototypes, defines)`` of a header text: ``{name: (restype, argtypes)}`` of every ``lk_*``
+    function and ``{LK_NAME: int}`` of every integer ``#define``.  Every pointer is a
+    ``c_void_p`` (handles, ``T **out``, device and host arrays, the structs), but a ``char *``
+    result is a ``c_char_p``.  Raises ``ValueError`` on anything outside that.
+    """
+    text = re.sub(r"#if 0.*?#endif /\* planned \*/", "", text, flags=re.S)
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    defines = {name: int(value) for name, value in _DEFINE.findall(text)}
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    prototypes = {}
+    for res, name, params in _PROTOTYPE.findall(text):
+        params = params.strip()
+        args = [] if params in ("", "void") else [_ctype(p) for p in params.split(",")]
+        prototypes[name] = (_ctype(res, result=True), args)
+    skipped = set(_SYMBOL.findall(text)) - set(prototypes)
+    if skipped:
+        raise ValueError(f"lkamd.h: not a prototype this binding can read: {sorted(skipped)}")
+    return prototypes, defines
 
-BMF_INVALID, BMF_FOLD, BMF_STORED = 0, 1, 2  # LK_BMF_*: a query's branch of BiasedMFScorer.__call__
 
-ASSOC_METHODS = {"probability": 0, "lift": 1}  # LK_ASSOC_PROBABILITY / LK_ASSOC_LIFT
-ASSOC_REDUCTIONS = {"mean": 0, "max": 1}  # LK_ASSOC_MEAN / LK_ASSOC_MAX
-SPARSE_REDUCTIONS = {"sum": 0, "mean": 1, "max": 2}  # LK_SPARSE_SUM / _MEAN / _MAX
-# lk_gemm_f32's tile mask: LK_GEMM_LOWER / LK_GEMM_K_FROM_COL / LK_GEMM_K_FROM_ROW
-GEMM_LOWER = 1
-GEMM_K_FROM_COL = 2
-GEMM_K_FROM_ROW = 4
-FUNKSVD_GLOBAL_COLUMNS = 1  # LK_FUNKSVD_GLOBAL_COLUMNS: lk_funksvd_train_feature's flag
+PROTOTYPES, H = parse_header(HEADER_PATH.read_text())
+
+LK_OK = H["LK_OK"]
+LK_E_INVALID = H["LK_E_INVALID"]
+LK_E_HIP = H["LK_E_HIP"]
+LK_E_NOT_SPD = H["LK_E_NOT_SPD"]
+LK_E_NAN_SIM = H["LK_E_NAN_SIM"]
+LK_E_NOMEM = H["LK_E_NOMEM"]
+LK_E_CANCELLED = H["LK_E_CANCELLED"]
+
+SOLVER_CHOLESKY = H["LK_SOLVER_CHOLESKY"]
+SOLVER_CG = H["LK_SOLVER_CG"]
+SOLVER_AUTO = H["LK_SOLVER_AUTO"]
+
+FLEXMF_LOSSES = {"logistic": H["LK_FLEXMF_LOGISTIC"], "pairwise": H["LK_FLEXMF_PAIRWISE"],
+                 "warp": H["LK_FLEXMF_WARP"]}
+FLEXMF_MSE = H["LK_FLEXMF_MSE"]  # lk_flexmf_step_explicit's loss
+FLEXMF_ADAMW = H["LK_FLEXMF_ADAMW"]
+FLEXMF_SPARSE_ADAM = H["LK_FLEXMF_SPARSE_ADAM"]
+FLEXMF_MAX_K = H["LK_FLEXMF_MAX_K"]
+
+STOCHASTIC_TRANSFORMS = {None: H["LK_STOCHASTIC_NONE"], "softmax": H["LK_STOCHASTIC_SOFTMAX"],
+                         "linear": H["LK_STOCHASTIC_LINEAR"]}
+
+FAIR_MAX_N = H["LK_FAIR_MAX_N"]  # (lk_fair_max_n()): the list length lk_fair_rerank's LDS holds
+
+# a query's branch of BiasedMFScorer.__call__
+BMF_INVALID, BMF_FOLD, BMF_STORED = H["LK_BMF_INVALID"], H["LK_BMF_FOLD"], H["LK_BMF_STORED"]
+
+ASSOC_METHODS = {"probability": H["LK_ASSOC_PROBABILITY"], "lift": H["LK_ASSOC_LIFT"]}
+ASSOC_REDUCTIONS = {"mean": H["LK_ASSOC_MEAN"], "max": H["LK_ASSOC_MAX"]}
+SPARSE_REDUCTIONS = {"sum": H["LK_SPARSE_SUM"], "mean": H["LK_SPARSE_MEAN"],
+                     "max": H["LK_SPARSE_MAX"]}
+# lk_gemm_f32's tile mask
+GEMM_LOWER = H["LK_GEMM_LOWER"]
+GEMM_K_FROM_COL = H["LK_GEMM_K_FROM_COL"]
+GEMM_K_FROM_ROW = H["LK_GEMM_K_FROM_ROW"]
+FUNKSVD_GLOBAL_COLUMNS = H["LK_FUNKSVD_GLOBAL_COLUMNS"]  # lk_funksvd_train_feature's flag
 
 
 class FlexMFTables(ctypes.Structure):
@@ -77,374 +137,12 @@ _lib = None
 
 
 def _declare(lib):
-    vp = c_void_p
-    sigs = {
-        "lk_last_error": (c_char_p, []),
-        "lk_version": (c_char_p, []),
-        "lk_device_count": (c_int, []),
-        "lk_padded_dim": (c_int32, [c_int32]),
-        "lk_pad_rows": (c_int, [vp, c_int64, c_int32, c_int32, vp, c_int32, vp]),
-        "lk_unpad_rows": (c_int, [vp, c_int64, c_int32, c_int32, vp, c_int32, vp]),
-        "lk_task_ctl_create": (c_int, [POINTER(vp)]),
-        "lk_task_ctl_destroy": (None, [vp]),
-        "lk_task_ctl_cancel": (None, [vp]),
-        "lk_task_ctl_cancelled": (c_int, [vp]),
-        "lk_task_ctl_reset": (None, [vp]),
-        "lk_task_ctl_progress": (c_int, [vp, POINTER(c_int64), POINTER(c_int64)]),
-        "lk_als_plan_set_ctl": (c_int, [vp, vp]),
-        "lk_iknn_plan_set_ctl": (c_int, [vp, vp]),
-        "lk_iknn_plan_enable_timing": (c_int, [vp, c_int]),
-        "lk_iknn_plan_get_timing": (c_int, [vp, POINTER(ctypes.c_double), POINTER(c_int32)]),
-        "lk_argtopn_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
-        "lk_gramian_workspace_bytes": (c_size_t, [c_int32]),
-        "lk_gramian": (c_int, [vp, c_int64, c_int32, c_int32, c_float, vp, c_int32, vp, vp]),
-        "lk_als_plan_create": (c_int, [POINTER(vp), vp, c_int, c_int64, c_int32, c_int32]),
-        "lk_als_plan_create_ex": (c_int, [POINTER(vp), vp, c_int, c_int64, c_int32, c_int32,
-                                          c_int32]),
-        "lk_als_plan_destroy": (None, [vp]),
-        "lk_als_plan_workspace_bytes": (c_size_t, [vp]),
-        "lk_als_plan_solver": (c_int32, [vp]),
-        "lk_als_plan_set_cg": (c_int, [vp, c_float, c_int32]),
-        "lk_als_plan_cg_stats": (c_int, [vp, vp, vp, POINTER(c_int64), POINTER(c_int64)]),
-        "lk_als_plan_short_rows": (c_int64, [vp]),
-        "lk_als_plan_long_rows": (c_int64, [vp]),
-        "lk_als_plan_units": (c_int64, [vp]),
-        "lk_als_plan_unit": (c_int32, [vp]),
-        "lk_als_plan_order_units": (c_int, [vp, vp, vp, c_int64, vp]),
-        "lk_als_plan_unit_table": (c_int, [vp, vp, vp, vp]),
-        "lk_als_plan_yref": (vp, [vp, vp]),
-        "lk_als_plan_woodbury_rows": (c_int64, [vp]),
-        "lk_als_plan_set_z": (c_int, [vp, vp]),
-        "lk_als_plan_set_z_workspace": (c_int, [vp, vp]),
-        "lk_als_plan_set_rhs_workspace": (c_int, [vp, vp]),
-        "lk_als_plan_set_z_shared": (c_int, [vp, vp, vp]),
-        "lk_als_plan_set_z_leader": (c_int, [vp, c_int]),
-        "lk_als_plan_z_flag": (vp, [vp, vp]),
-        "lk_spd_inverse_workspace_bytes": (c_size_t, [c_int32]),
-        "lk_spd_inverse": (c_int, [vp, c_int32, c_int32, vp, vp, vp, vp]),
-        "lk_als_implicit_half_epoch": (
-            c_int,
-            [vp, vp, vp, vp, c_int64, c_int64, c_int32, vp, c_int32, vp, c_int32, vp, c_int32, vp,
-             vp, vp],
-        ),
-        "lk_als_implicit_epoch": (
-            c_int,
-            [vp, vp, vp, vp, vp, vp, vp, vp, c_int32, vp, vp, vp, c_int32, c_float, vp, c_int32,
-             c_float, vp, vp, vp, vp, vp],
-        ),
-        "lk_als_explicit_half_epoch": (
-            c_int,
-            [vp, vp, vp, vp, c_int64, c_int64, c_int32, vp, c_int32, vp, c_int32, c_float, vp, vp,
-             vp],
-        ),
-        "lk_als_check_status": (c_int, [vp, vp, vp]),
-        "lk_als_plan_enable_timing": (c_int, [vp, c_int]),
-        "lk_als_plan_get_timing": (
-            c_int, [vp, POINTER(ctypes.c_double), POINTER(ctypes.c_double), POINTER(c_int32)]
-        ),
-        "lk_iknn_plan_create": (c_int, [POINTER(vp), vp, vp, c_int, c_int64, c_int64]),
-        "lk_iknn_plan_create_rows": (
-            c_int, [POINTER(vp), vp, vp, c_int, c_int64, c_int64, c_int64, c_int64]
-        ),
-        "lk_iknn_plan_destroy": (None, [vp]),
-        "lk_iknn_plan_workspace_bytes": (c_size_t, [vp]),
-        "lk_iknn_build_count": (
-            c_int, [vp, vp, vp, vp, vp, vp, vp, c_float, c_int64, vp, vp, POINTER(c_int64), vp]
-        ),
-        "lk_iknn_build_fill": (
-            c_int, [vp, vp, vp, vp, vp, vp, vp, c_float, c_int64, vp, vp, vp, vp, vp]
-        ),
-        "lk_iknn_truncate_workspace_bytes": (c_size_t, [c_int64, c_int64]),
-        "lk_iknn_truncate_count": (
-            c_int,
-            [vp, vp, vp, vp, c_int, vp, c_int64, c_int64, c_int64, c_int64, vp, vp,
-             POINTER(c_int64), vp],
-        ),
-        "lk_iknn_truncate_fill": (c_int, [vp, vp, vp, c_int64, c_int64, vp, vp, vp, vp, vp]),
-        "lk_iknn_score_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
-        "lk_iknn_recommend_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int32,
-                                                         c_int32]),
-        "lk_iknn_recommend": (c_int, [vp, vp, vp, c_int64, c_int64, vp, vp, vp, vp, c_int32,
-                                      c_int32, c_int32, c_int, vp, c_int64, vp, vp, vp, vp]),
-        "lk_knn_score_last_stats": (None, [POINTER(c_int64)]),
-        "lk_iknn_recommend_last_packed": (c_int, []),
-        "lk_iknn_score_batch": (
-            c_int,
-            [vp, vp, vp, c_int64, c_int64, vp, vp, vp, vp, vp, c_int32, c_int32, vp, vp, vp, vp],
-        ),
-        "lk_bias_user_offsets": (
-            c_int,
-            [vp, c_int, vp, vp, c_int64, c_int64, c_int64, vp, ctypes.c_double, vp,
-             ctypes.c_double, vp, vp, vp],
-        ),
-        "lk_predict_merge": (
-            c_int,
-            [c_int64, vp, vp, c_int64, c_int64, vp, vp, c_int, ctypes.c_double, vp, vp, vp, vp,
-             vp],
-        ),
-        "lk_bias_fit_short_max": (c_int32, []),
-        "lk_bias_fit_chunk": (c_int32, []),
-        "lk_bias_fit_pass": (
-            c_int,
-            [vp, c_int, vp, vp, c_int64, ctypes.c_double, vp, c_int64, ctypes.c_double, vp, vp],
-        ),
-        "lk_bias_score_panel": (
-            c_int,
-            [c_int64, c_int64, ctypes.c_double, vp, vp, vp, vp, c_int64, vp, c_int, vp, c_int64,
-             vp, vp],
-        ),
-        "lk_bias_score_ragged": (
-            c_int, [c_int64, vp, vp, c_int64, c_int64, ctypes.c_double, vp, vp, vp, vp, vp]
-        ),
-        "lk_bmf_residual_rows": (
-            c_int,
-            [vp, c_int, vp, vp, c_int64, c_int64, c_int64, vp, vp, ctypes.c_double, vp,
-             ctypes.c_double, vp, vp, vp, vp],
-        ),
-        "lk_bmf_finish_panel": (
-            c_int, [vp, c_int64, c_int64, c_int64, vp, vp, ctypes.c_double, vp, vp, vp, vp]
-        ),
-        "lk_bmf_finish_pairs": (
-            c_int,
-            [vp, c_int64, c_int64, c_int64, vp, vp, ctypes.c_double, vp, vp, vp, c_int64, c_int64,
-             vp, vp],
-        ),
-        "lk_bmf_finish_ragged": (
-            c_int,
-            [vp, c_int64, c_int64, vp, vp, ctypes.c_double, vp, vp, vp, c_int64, vp, vp],
-        ),
-        "lk_uknn_score_batch": (
-            c_int,
-            [vp, vp, vp, c_int64, c_int64, c_int64, vp, vp, vp, vp, vp, c_int32, c_int32, vp, vp,
-             vp, vp],
-        ),
-        "lk_csr_rows_dot": (
-            c_int, [vp, c_int, vp, vp, c_int64, vp, c_int64, c_int64, vp, c_int64, vp]
-        ),
-        "lk_uknn_query_panel": (c_int, [vp, vp, vp, vp, c_int64, c_int64, vp, c_int64, vp]),
-        "lk_uknn_sims_panel": (
-            c_int, [vp, c_int, vp, vp, c_int64, vp, c_int64, c_int64, vp, vp, c_int64, vp]
-        ),
-        "lk_uknn_score_panel_lds_max_nbrs": (c_int32, []),
-        "lk_uknn_score_panel_workspace_bytes": (c_size_t, [c_int32, c_int64]),
-        "lk_uknn_score_panel": (
-            c_int,
-            [vp, vp, vp, c_int64, c_int64, c_int64, vp, vp, c_int64, c_int64, c_float, c_int32,
-             c_int32, vp, vp, vp, c_int, vp, vp, c_int64, vp],
-        ),
-        "lk_uknn_score_pairs_lds_max_nbrs": (c_int32, []),
-        "lk_uknn_score_pairs_workspace_bytes": (c_size_t, [c_int32, c_int64]),
-        "lk_uknn_score_pairs": (
-            c_int,
-            [vp, vp, vp, c_int64, c_int64, c_int64, vp, c_int64, c_int, c_int64, vp, vp, vp,
-             c_int64, c_int64, c_float, c_int32, c_int32, vp, vp, vp, vp],
-        ),
-        "lk_download": (c_int, [vp, vp, c_size_t, c_int32, vp]),
-        "lk_download_warmup": (c_int, []),
-        "lk_download_i32_narrow": (c_int, [vp, vp, c_int64, vp, c_int32, vp]),
-        "lk_ease_gram": (c_int, [vp, vp, vp, vp, c_int64, c_float, vp, c_int64, vp]),
-        "lk_ease_score_batch": (
-            c_int, [vp, vp, c_int64, vp, c_int64, c_int64, vp, c_int64, vp]
-        ),
-        "lk_ease_score_panel": (
-            c_int, [vp, vp, c_int64, vp, c_int64, c_int64, vp, c_int64, c_int, vp]
-        ),
-        "lk_gemm_tile": (c_int32, []),
-        "lk_gemm_f32": (
-            c_int, [c_int, c_int, c_int64, c_int64, c_int64, c_float, vp, c_int64, vp, c_int64,
-                    c_float, vp, c_int64, c_int, vp]
-        ),
-        "lk_spd_inverse_blocked_max_n": (c_int64, []),
-        "lk_spd_inverse_blocked_workspace_bytes": (c_size_t, [c_int64]),
-        "lk_spd_inverse_blocked": (c_int, [vp, c_int64, c_int64, vp, c_size_t, vp, vp]),
-        "lk_spd_inverse_blocked_phases": (
-            c_int, [vp, c_int64, c_int64, vp, c_size_t, vp, c_int, vp]
-        ),
-        "lk_slim_train_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
-        "lk_slim_train_count": (
-            c_int,
-            [vp, vp, vp, vp, c_int, c_int64, c_int64, vp, c_float, c_float, c_int32, c_int64, vp,
-             c_int64, vp, vp, vp, POINTER(c_int64), POINTER(c_int64), vp],
-        ),
-        "lk_slim_train_fill": (c_int, [c_int64, c_int64, c_int64, c_int64, vp, vp, vp, vp, vp]),
-        "lk_slim_score_batch": (
-            c_int, [vp, vp, c_int64, vp, vp, vp, c_int64, vp, c_int64, c_int, vp]
-        ),
-        "lk_take_scores": (c_int, [vp, c_int64, c_int64, vp, c_int64, vp, vp]),
-        "lk_shared_order_topn": (
-            c_int, [vp, vp, c_int64, vp, c_int, vp, c_int64, vp, c_int64, c_int64, vp, vp, vp]
-        ),
-        "lk_assoc_window": (c_int32, []),
-        "lk_assoc_scale": (
-            c_int, [vp, vp, vp, vp, c_int64, c_int64, c_int, ctypes.c_double, vp]
-        ),
-        "lk_assoc_score_batch": (
-            c_int, [vp, vp, c_int64, vp, vp, vp, c_int64, c_int, vp, c_int64, c_int, vp]
-        ),
-        "lk_score_topk_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
-        "lk_score_topk": (
-            c_int,
-            [vp, c_int32, c_int64, vp, c_int32, c_int64, c_int32, c_int32, vp, vp, vp, vp, vp, vp],
-        ),
-        "lk_score_topk_last_report": (c_int32, [POINTER(c_int64), POINTER(c_int32), c_int32]),
-        "lk_score_dense": (
-            c_int, [vp, c_int32, c_int64, vp, c_int32, c_int64, c_int32, vp, c_int64, vp]
-        ),
-        "lk_argtopn": (c_int, [vp, c_int64, c_int64, c_int32, vp, vp, vp]),
-        "lk_iknn_prep_center": (c_int, [vp, c_int, vp, vp, c_int64, vp, vp, vp, vp]),
-        "lk_iknn_prep_scale": (c_int, [vp, c_int, vp, vp, vp, c_int64, vp, vp, vp]),
-        "lk_csr_transpose_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
-        "lk_csr_transpose": (
-            c_int, [vp, c_int, vp, c_int64, c_int64, c_int64, vp, vp, vp, vp, c_size_t, vp]
-        ),
-        "lk_synth_zipf_rows": (c_int, [vp, c_int64, c_int64, ctypes.c_uint64, vp, c_int64, vp, vp]),
-        "lk_csr_relabel": (c_int, [vp, c_int, vp, vp, c_int64, vp, vp, vp, vp, vp, vp]),
-        "lk_csr_gather_rows": (
-            c_int, [vp, c_int, vp, vp, c_int64, vp, vp, vp, c_float, vp, vp, vp]
-        ),
-        "lk_rank_stats": (
-            c_int, [vp, c_int64, c_int64, c_int64, vp, vp, vp, vp, c_int32, vp, c_int32, c_int64,
-                    vp, vp, vp]
-        ),
-        "lk_ideal_gain_workspace_bytes": (c_size_t, [c_int64, c_int64]),
-        "lk_ideal_gain": (
-            c_int, [vp, vp, c_int64, vp, c_int64, c_int64, vp, vp, vp, c_int32, vp, c_int32,
-                    c_int64, vp, vp, vp]
-        ),
-        "lk_predict_errors": (c_int, [c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "lk_list_category_max": (c_int32, []),
-        "lk_item_exposure_workspace_bytes": (c_size_t, [c_int64, c_int64]),
-        "lk_item_exposure": (
-            c_int, [vp, c_int64, c_int64, c_int64, c_int32, vp, c_int64, c_int32, vp, vp, vp]
-        ),
-        "lk_list_category_stats": (
-            c_int, [vp, c_int64, c_int64, c_int64, c_int32, c_int32, vp, vp, vp, c_int32, vp,
-                    c_int64, vp, vp, vp]
-        ),
-        "lk_list_gather_mean": (
-            c_int, [vp, c_int64, c_int64, c_int64, c_int32, vp, c_int32, vp, vp, vp]
-        ),
-        "lk_list_pair_stats": (
-            c_int, [c_int64, vp, vp, vp, vp, vp, c_int32, vp, vp, vp, vp, vp]
-        ),
-        "lk_flexmf_sample_negatives": (
-            c_int, [vp, vp, c_int64, c_int64, vp, c_int64, c_int32, c_int, c_int, c_int32,
-                    ctypes.c_uint64, ctypes.c_uint64, vp, vp]
-        ),
-        "lk_flexmf_gather_batch": (c_int, [vp, c_int64, vp, vp, vp, vp, vp]),
-        "lk_flexmf_warp_search": (
-            c_int, [POINTER(FlexMFTables), vp, vp, vp, c_int64, c_int32, vp, vp, vp, vp]
-        ),
-        "lk_flexmf_step_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
-        "lk_flexmf_step": (
-            c_int, [POINTER(FlexMFTables), POINTER(FlexMFHyper), vp, vp, vp, vp, c_int64, vp, vp,
-                    vp, vp, vp]
-        ),
-        "lk_flexmf_gather_values": (c_int, [vp, c_int64, vp, vp, vp]),
-        "lk_flexmf_step_explicit_workspace_bytes": (c_size_t, [c_int64, c_int32]),
-        "lk_flexmf_step_explicit": (
-            c_int, [POINTER(FlexMFTables), POINTER(FlexMFHyper), vp, vp, vp, c_int64, vp, vp, vp,
-                    vp, vp]
-        ),
-        "lk_mf_score_pairs": (
-            c_int, [vp, c_int32, c_int64, vp, c_int32, c_int64, c_int32, vp, c_int64, vp, vp,
-                    c_int64, vp, vp]
-        ),
-        "lk_score_candidates": (
-            c_int, [vp, c_int32, c_int64, vp, c_int32, c_int64, c_int32, vp, c_int64, vp, vp,
-                    c_int64, vp, vp]
-        ),
-        "lk_panel_take_ragged": (c_int, [vp, c_int64, c_int64, c_int64, vp, vp, c_int64, vp, vp]),
-        "lk_ragged_topn_wave_max": (c_int32, []),
-        "lk_ragged_topn_block_max": (c_int32, []),
-        "lk_ragged_topn_workspace_bytes": (c_size_t, [c_int64, c_int64]),
-        "lk_ragged_topn": (
-            c_int, [c_int64, vp, vp, vp, c_int64, c_int32, c_int64, vp, vp, vp, vp]
-        ),
-        "lk_sparse_score_candidates": (
-            c_int, [vp, vp, c_int64, c_int64, vp, c_int64, vp, vp, vp, c_int64, c_int64, vp, vp,
-                    c_int64, c_int, vp, vp]
-        ),
-        "lk_stochastic_row_stats": (
-            c_int, [vp, c_int64, c_int64, c_int64, vp, vp, c_int32, c_float, vp, vp]
-        ),
-        "lk_stochastic_keys": (
-            c_int, [vp, c_int64, c_int64, c_int64, vp, vp, c_int32, c_float, vp, ctypes.c_uint64,
-                    vp, ctypes.c_uint32, vp, c_int64, vp]
-        ),
-        "lk_stochastic_key_of_bits": (c_int, [vp, vp, c_int64, vp, vp]),
-        "lk_ragged_stochastic_chunk": (c_int32, []),
-        "lk_ragged_stochastic_keys": (
-            c_int, [c_int64, vp, vp, vp, c_int64, vp, vp, c_int32, c_float, ctypes.c_uint64,
-                    ctypes.c_uint32, c_int32, vp, vp, vp]
-        ),
-        "lk_fair_max_n": (c_int32, []),
-        "lk_fair_rerank": (
-            c_int, [vp, c_int64, c_int64, c_int64, vp, vp, vp, c_int64, vp, c_int32, c_int32, vp,
-                    vp, vp, vp]
-        ),
-        "lk_spmm_split": (c_int32, []),
-        "lk_csr_spmm": (
-            c_int, [vp, c_int, vp, vp, c_int64, c_int64, c_int64, vp, c_int32, c_int32, vp,
-                    c_int32, vp]
-        ),
-        "lk_chol_max_l": (c_int32, []),
-        "lk_chol_upper_inverse": (
-            c_int, [vp, c_int32, c_int32, vp, vp, c_int32, vp, c_int32, vp]
-        ),
-        "lk_lgcn_propagate": (
-            c_int, [vp, vp, vp, c_int64, c_int64, ctypes.c_float, vp, ctypes.c_float, vp, c_int32,
-                    c_int32, vp, vp]
-        ),
-        "lk_lgcn_pair_grad_workspace_bytes": (c_size_t, [c_int64]),
-        "lk_lgcn_pair_grad": (
-            c_int, [vp, c_int64, c_int32, c_int32, c_int32, vp, vp, vp, c_int64, vp, vp, vp, vp, vp]
-        ),
-        "lk_adamw_dense": (
-            c_int, [vp, vp, vp, vp, c_int64, c_int32, c_int32] + [ctypes.c_double] * 7 + [vp]
-        ),
-        "lk_hpf_expect_log": (c_int, [vp, vp, c_int64, c_int32, c_int32, vp, vp]),
-        "lk_hpf_shape_pass": (
-            c_int, [vp, c_int, vp, vp, c_int64, c_int64, c_int64, vp, vp, c_int32, c_int32,
-                    c_float, vp, vp]
-        ),
-        "lk_hpf_rates_block": (c_int32, []),
-        "lk_hpf_rates_workspace_bytes": (c_size_t, [c_int64, c_int32]),
-        "lk_hpf_rates": (
-            c_int, [vp, c_int64, c_int32, c_int32, ctypes.c_double, ctypes.c_double, vp, vp, vp,
-                    vp, vp, vp, vp]
-        ),
-        "lk_hpf_loglik_rows": (
-            c_int, [vp, c_int, vp, vp, c_int64, c_int64, c_int64, vp, vp, c_int32, c_int32, vp, vp]
-        ),
-        "lk_nmf_max_k": (c_int32, []),
-        "lk_nmf_workspace_bytes": (c_size_t, [c_int64]),
-        "lk_nmf_cd_sweep": (
-            c_int, [vp, c_int64, c_int32, c_int32, vp, c_int32, vp, c_float, vp, vp, vp]
-        ),
-        "lk_funksvd_narrow_width": (c_int32, []),
-        "lk_funksvd_stage_samples": (c_int32, []),
-        "lk_funksvd_lds_column_bytes": (c_size_t, []),
-        "lk_funksvd_plan_levels": (c_int, [vp, vp, c_int64, c_int64, c_int64, vp, POINTER(c_int32)]),
-        "lk_funksvd_plan_order": (c_int, [vp, c_int64, c_int32, vp, vp, vp]),
-        "lk_funksvd_train_feature": (
-            c_int, [vp, vp, vp, vp, vp, vp, c_int32, vp, vp, c_int64, c_int64, c_int32, c_int32]
-            + [ctypes.c_double] * 5 + [c_int32, vp, vp]
-        ),
-        "lk_als_implicit_half_epoch_host": (
-            c_int,
-            [vp, c_int, vp, vp, c_int64, c_int64, c_int32, vp, vp, vp, c_int32, vp],
-        ),
-        "lk_als_implicit_half_epoch_host_ctl": (
-            c_int,
-            [vp, c_int, vp, vp, c_int64, c_int64, c_int32, vp, vp, vp, c_int32, vp, vp],
-        ),
-    }  # fmt: skip
-    for name, (res, args) in sigs.items():
+    "Give every function of the header its types on ``lib``; returns name -> (restype, argtypes)."
+    for name, (res, args) in PROTOTYPES.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
-    return sigs
+    return PROTOTYPES
 
 
 def load(build_if_missing: bool = False):
@@ -481,10 +179,7 @@ def load(build_if_missing: bool = False):
 
 def declared_symbols() -> list[str]:
     "Every function ``include/lkamd.h`` declares (used by the export test)."
-    text = HEADER_PATH.read_text()
-    text = re.sub(r"#if 0.*?#endif /\* planned \*/", "", text, flags=re.S)
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(lk_[a-z0-9_]+)\s*\(", text)))
+    return sorted(PROTOTYPES)
 
 
 def last_error() -> str:
